@@ -11,7 +11,17 @@ guidance embedding on) followed by the Euler scheduler update, on synthetic inpu
 weights of the FLUX.1-dev architecture (no checkpoints exist in this environment).  All 57 blocks
 and every operator run inside the timed region; inputs are resident in HBM before it starts.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line: the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds
+of one timed step), the replicas' own rates and the configuration.  A plain run does nothing else: set up, warm up, time
+the K steps, print.  --dump-outputs DIR then writes the latents the last timed step returned (float32, DIR/latents.npy;
+rank r > 0: DIR/latents_rank<r>.npy) on seeded inputs, so that two builds can be compared output for output.  The library's
+default low-rank sums are fp32 atomics, whose order changes from run to run (two forwards differ by up to 2 %), so
+a run that writes outputs times the steps in deterministic mode, level "runs", unless --deterministic says otherwise: the same
+arguments then give bit-equal outputs.  The line's config.deterministic names the mode that was timed.  --deterministic off dumps
+the default path; two such runs of the headline config (20 + 5 steps) differ by 2.8 % relative L2 in the latents, so compare those
+within a tolerance.
+
+With --full the same line also carries (measured AFTER the timed region, which stays as in a plain run)
   roofline     -- the dominant kernel (gemm_w4a4): algorithmic ops / summed kernel time, measured
                   live with HIP events recorded around every launch on the launch stream
                   (svdq_prof_*, include/svdq_amd.h) during the timed steps, against the dense INT8
@@ -19,6 +29,7 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
                   codes on the FP6 matrix path, DESIGN.md section 2);
   cpu_baseline -- the CPU oracle (a numpy port; the reference ships no CPU path) timed on a bounded
                   sample of the same workload on this box's host cores (rank 0, N=1 only).
+In a plain run ms_per_step_instrumented, roofline and cpu_baseline are null.
 """
 
 import argparse
@@ -102,6 +113,25 @@ def committed_epilogue_share():
         return d
     except Exception:
         return None
+
+
+# --dump-outputs: all files of one run together stay below this; a larger output is replaced by a fixed, seeded sample
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict, budget_bytes: int):
+    """Write every tensor of ``arrays`` as out_dir/<name>.npy in float32.  A tensor larger than its share of the budget is
+    written as a sample: the elements at a fixed set of flat indices (seed 0, ascending), the same on every run."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget_bytes // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 class ClockSampler:
@@ -208,6 +238,118 @@ def cpu_baseline(max_seconds: float = 30.0):
     }
 
 
+def measure_full(args, model, step, eager_step, latents, total, clock, clock_ghz, lib, rank, world):
+    """--full: P instrumented steps and three per-kernel steps run AFTER the timed region -> the roofline object; the CPU baseline.
+    Returns the keys they add to rank 0's line (an empty dict on the other ranks)."""
+    from nunchaku_amd import _lib
+
+    n_gemm = sum(1 for _ in model.svdq_layers())
+    prof_steps = 0 if (args.no_prof or args.graph) else max(0, args.prof_steps)
+    ms_instrumented = None
+    if prof_steps:
+        _lib.check(lib.svdq_prof_select(1 << 0), "svdq_prof_select")
+        _lib.check(lib.svdq_prof_enable(max(1, 2 * n_gemm * (prof_steps + 1) + 64)), "svdq_prof_enable")
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        lat_p = latents
+        for i in range(prof_steps):
+            lat_p = step(total - 1 - (i % max(1, args.steps)), lat_p)
+        torch.cuda.synchronize()
+        ms_instrumented = (time.perf_counter() - t1) / prof_steps * 1e3
+    clock_ghz_prof = clock.stop()  # ... of the event-bracketed steps the roofline object was measured on
+
+    def prof(cls):
+        n, ms, work = C.c_int64(), C.c_double(), C.c_double()
+        _lib.check(lib.svdq_prof_read(cls, C.byref(n), C.byref(ms), C.byref(work)), "svdq_prof_read")
+        return n.value, ms.value, work.value
+
+    if args.graph:  # per-launch events cannot live inside a graph: bracket one extra eager step instead
+        step = eager_step
+        _lib.check(lib.svdq_prof_select(1 << 0), "svdq_prof_select")
+        _lib.check(lib.svdq_prof_enable(max(1, 4 * n_gemm + 64)), "svdq_prof_enable")
+        step(total - 1, latents.clone())
+        torch.cuda.synchronize()
+    n_g, ms_g, ops_g = prof(0)
+    prof_steps = 1 if args.graph else max(prof_steps, 1)
+    per_variant = {}
+    for name, fuse in (("default", 0), ("silu", 1), ("gelu_quant", 2), ("rmsnorm_rope", 3)):
+        n_v_, ms_v_, ops_v_ = prof(0 | ((fuse + 1) << 8))  # SVDQ_PROF_GEMM_VARIANT(fuse), include/svdq_amd.h
+        if n_v_:
+            tops = ops_v_ / (ms_v_ * 1e-3) / 1e12
+            per_variant[name] = {"launches_per_step": n_v_ / prof_steps, "avg_launch_us": ms_v_ * 1e3 / n_v_, "ms_per_step": ms_v_ / prof_steps,
+                                 "TOPs": tops, "frac": tops / INT8_PEAK_TOPS}
+    # the quantiser's numbers come from ONE extra, untimed step bracketed on its class only
+    lib.svdq_prof_select(1 << 1)
+    lib.svdq_prof_reset()
+    step(total - 1, latents)
+    torch.cuda.synchronize()
+    n_q, ms_q, bytes_q = prof(1)
+    # ... and the attention kernel's from another one
+    lib.svdq_prof_select(1 << 2)
+    lib.svdq_prof_reset()
+    step(total - 1, latents)
+    torch.cuda.synchronize()
+    n_a, ms_a, flops_a = prof(2)
+    # ... and the AWQ GEMV's (the modulation projections: one batched launch per step) from a third
+    lib.svdq_prof_select(1 << 3)
+    lib.svdq_prof_reset()
+    step(total - 1, latents)
+    torch.cuda.synchronize()
+    n_v, ms_v, bytes_v = prof(3)
+    lib.svdq_prof_enable(0)
+    lib.svdq_prof_select(0xFFFFFFFF)
+
+    if rank != 0:
+        return {}
+    achieved = ops_g / (ms_g * 1e-3) / 1e12 if ms_g > 0 else 0.0
+    traffic, traffic_file, traffic_fresh = committed_traffic()
+    roofline = {
+        "kernel": "svdq::gemm_w4a4_kernel (all epilogue variants)",
+        "bound": "mfma",
+        "achieved": achieved,
+        "peak": INT8_PEAK_TOPS,
+        "unit": "TOP/s",
+        "frac": achieved / INT8_PEAK_TOPS,
+        "frac_int8": achieved / INT8_PEAK_TOPS,   # BASELINE.json's yardstick
+        "frac_fp6": achieved / FP6_PEAK_TOPS,     # the matrix pipe the 4-bit product actually runs on
+        "traffic": traffic,
+        "traffic_source": f"committed: {traffic_file} (rocprofv3 PMC passes of this command: "
+                          "2*FETCH_SIZE + WRITE_SIZE per gemm_w4a4 dispatch); not measured in this run",
+        "traffic_stale": not traffic_fresh,   # true: the kernel sources changed since that file was measured
+        "mfma_util": committed_mfma_util(),
+        # share of a tile's cycles behind the main loop per epilogue variant (committed probe measurement, VERDICT r4 #5): what the launch-level
+        # fraction loses against the loop's own
+        "epilogue_share": committed_epilogue_share(),
+        # shader clock during the timed region (pp_dpm_sclk sampled every 50 ms on rank 0): the chip runs these kernels at its power
+        # limit; profiles/r4_clock_instrument.txt ties this reading to GRBM_GUI_ACTIVE / dispatch duration
+        "effective_clock_ghz": clock_ghz,
+        "effective_clock_ghz_prof_steps": clock_ghz_prof,   # the same reading over the instrumented steps (where `achieved` was measured)
+        "per_variant": per_variant,
+        # the three per-variant fractions once more as flat keys (the driver's record keeps scalars of this object and drops nested ones)
+        **{f"frac_{k}": v["frac"] for k, v in per_variant.items()},
+        **{f"avg_launch_us_{k}": v["avg_launch_us"] for k, v in per_variant.items()},
+        "launches": n_g,
+        "prof_steps": prof_steps,
+        "avg_launch_us": ms_g * 1e3 / max(n_g, 1),
+        "gemm_ms_per_step": ms_g / prof_steps,
+        "measured_on": "one extra eager step (graph replay in the timed region)" if args.graph else
+                       f"{prof_steps} steps run right behind the timed region with HIP events around every gemm_w4a4 launch (the timed region itself carries none)",
+        "quantize": {"launches": n_q, "ms_per_step": ms_q, "measured_on": "one extra untimed step",
+                     "GBps": bytes_q / (ms_q * 1e-3) / 1e9 if ms_q > 0 else 0.0, "bound": "hbm"},
+        "attention": {"launches": n_a, "ms_per_step": ms_a, "measured_on": "one extra untimed step",
+                      "TFLOPs": flops_a / (ms_a * 1e-3) / 1e12 if ms_a > 0 else 0.0, "bound": "mfma",
+                      "frac_bf16": (flops_a / (ms_a * 1e-3) / 1e12 / BF16_PEAK_TFLOPS) if ms_a > 0 else 0.0},
+        "gemv_awq": {"launches": n_v, "ms_per_step": ms_v, "measured_on": "one extra untimed step",
+                     "GBps": bytes_v / (ms_v * 1e-3) / 1e9 if ms_v > 0 else 0.0, "bound": "hbm by bytes, VALU in practice"},
+    }
+    full = {"ms_per_step_instrumented": ms_instrumented, "roofline": roofline}
+    # ... and at the top level of the contract line (VERDICT r5 #8)
+    for k, v in per_variant.items():
+        full[f"roofline_frac_{k}"] = v["frac"]
+    full["cpu_baseline"] = cpu_baseline() if world == 1 and not args.no_cpu_baseline else None
+    return full
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -238,11 +380,17 @@ def main():
     ap.add_argument("--lora", type=int, default=0, metavar="r",
                     help="attach a runtime LoRA of rank r to every SVDQuant linear (set_lora: the low-rank branch becomes rank R + r with per-16-rank "
                          "scales -- the reference's update_lora_params, transformer_flux.py:783-855)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, measure the roofline object (instrumented and per-kernel steps after the timed region, "
+                         "shader clock) and the CPU baseline; a plain run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the latents the last one returned as DIR/latents.npy (float32; at most 64 MB in all); "
+                         "the steps then run in deterministic mode 'runs' unless --deterministic is given")
     ap.add_argument("--prof-steps", type=int, default=10, metavar="P",
-                    help="steps bracketed with per-launch HIP events AFTER the timed region (the roofline object); 0 = none")
+                    help="--full: steps bracketed with per-launch HIP events AFTER the timed region (the roofline object); 0 = none")
     ap.add_argument("--no-prof", action="store_true", help="same as --prof-steps 0")
     ap.add_argument("--layers", type=int, nargs=2, default=(19, 38), help=argparse.SUPPRESS)  # debugging only
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--attention-geometry", type=int, default=0, choices=[0, 1, 2],
                     help="workgroup geometry of the attention kernel (svdq_attention_args.geometry): 0 = the library's choice (4 waves x 64 "
                          "rows on the prescaled Q the QKV GEMM emits), 1 = 8 waves x 32 rows, 2 = 4 x 64 with its persistent schedule (same-box A/B)")
@@ -256,9 +404,10 @@ def main():
     ap.add_argument("--no-attention-split", action="store_true",
                     help="A/B: keep the low-rank down projection of the attention epilogue's quantiser inside the epilogue at every rank (rank 48 .. 160 "
                          "runs it as a contraction kernel behind the attention kernel by default)")
-    ap.add_argument("--deterministic", nargs="?", const="strict", default=False, choices=["strict", "runs"],
+    ap.add_argument("--deterministic", nargs="?", const="strict", default=None, choices=["strict", "runs", "off"],
                     help="fixed-point low-rank accumulation (nunchaku_amd.mode): bit-reproducible steps; 'strict' (default of the flag): independent of the "
-                         "launch configuration; 'runs': a GELU_QUANT workgroup sums its run of column tiles in fp32 in a fixed order first (ABI 22)")
+                         "launch configuration; 'runs': a GELU_QUANT workgroup sums its run of column tiles in fp32 in a fixed order first (ABI 22); "
+                         "'off': the library's default fp32 atomics.  Without the flag: 'runs' with --dump-outputs, 'off' otherwise")
     ap.add_argument("--graph", action="store_true",
                     help="replay the step as one captured HIP graph (no per-launch events: the roofline object is then "
                          "measured on one extra eager step after the timed region)")
@@ -269,6 +418,12 @@ def main():
         ap.error("--offload needs --config qwen1024")
     if qwen and "--steps" not in " ".join(sys.argv):
         args.steps, args.warmup = 10, 2
+    if args.deterministic is None:  # outputs that are written must be reproducible: the fp32-atomic default is not
+        args.deterministic = "runs" if args.dump_outputs else "off"
+    if args.deterministic == "off":
+        args.deterministic = False
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps takes a positive number, --warmup a non-negative one")
     if args.resolution is None:
         args.resolution = [512 if schnell else 1024]
     if len(args.resolution) > 2 or any(r <= 0 or r % 16 for r in args.resolution):
@@ -347,6 +502,7 @@ def main():
     for i in range(args.warmup):
         latents = step(i, latents)
 
+    eager_step = step
     if args.graph:
         from nunchaku_amd.graph import CapturedStep
 
@@ -355,88 +511,34 @@ def main():
             return lat + dsig.to(v.dtype) * v
 
         captured = CapturedStep(graph_fn, [latents, sigmas[0].reshape(1), (sigmas[1] - sigmas[0]).reshape(1)])
-        eager_step = step
 
         def step(i, lat):  # noqa: F811
             return captured(lat, sigmas[i].reshape(1), (sigmas[i + 1] - sigmas[i]).reshape(1))
 
-    n_gemm = sum(1 for _ in model.svdq_layers())
     # The timed region carries NO instrumentation (an event pair around a launch serialises the queue for ~3 us; 228 GEMM launches
-    # per step were ~1.3 % of the reported step).  The roofline object is measured right behind it: P more steps of the same loop with HIP events
-    # around every gemm_w4a4 launch (and nothing else), timed as well -> ms_per_step_instrumented.
-    prof_steps = 0 if (args.no_prof or args.graph) else max(0, args.prof_steps)
-    clock = ClockSampler(local_rank)
+    # per step were ~1.3 % of the reported step).  With --full the roofline object is measured right behind it: P more steps of the same loop
+    # with HIP events around every gemm_w4a4 launch (and nothing else), timed as well -> ms_per_step_instrumented.
+    clock = ClockSampler(local_rank) if args.full else None
     replica.barrier()
     torch.cuda.synchronize()
-    clock.start()
+    if clock:
+        clock.start()
     t0 = time.perf_counter()
     for i in range(args.warmup, total):
         latents = step(i, latents)
     torch.cuda.synchronize()
     own = time.perf_counter() - t0          # this replica's own time for its K steps (before it waits for the others)
-    clock_ghz = clock.mark()                # the shader clock of the TIMED region only (the instrumented steps behind it are a region of their own)
+    clock_ghz = clock.mark() if clock else None  # the shader clock of the TIMED region only (the instrumented steps behind it are a region of their own)
     replica.barrier()
     elapsed = time.perf_counter() - t0
     elapsed = replica.max_over_ranks(elapsed, dev)
     own_max, own_min = replica.max_over_ranks(own, dev), -replica.max_over_ranks(-own, dev)
     finite = bool(torch.isfinite(latents.float()).all())
-    ms_instrumented = None
-    if prof_steps:
-        _lib.check(lib.svdq_prof_select(1 << 0), "svdq_prof_select")
-        _lib.check(lib.svdq_prof_enable(max(1, 2 * n_gemm * (prof_steps + 1) + 64)), "svdq_prof_enable")
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        lat_p = latents
-        for i in range(prof_steps):
-            lat_p = step(total - 1 - (i % max(1, args.steps)), lat_p)
-        torch.cuda.synchronize()
-        ms_instrumented = (time.perf_counter() - t1) / prof_steps * 1e3
-    clock_ghz_prof = clock.stop()  # ... of the event-bracketed steps the roofline object was measured on
-
-    def prof(cls):
-        n, ms, work = C.c_int64(), C.c_double(), C.c_double()
-        _lib.check(lib.svdq_prof_read(cls, C.byref(n), C.byref(ms), C.byref(work)), "svdq_prof_read")
-        return n.value, ms.value, work.value
-
-    if args.graph:  # per-launch events cannot live inside a graph: bracket one extra eager step instead
-        step = eager_step
-        _lib.check(lib.svdq_prof_select(1 << 0), "svdq_prof_select")
-        _lib.check(lib.svdq_prof_enable(max(1, 4 * n_gemm + 64)), "svdq_prof_enable")
-        step(total - 1, latents.clone())
-        torch.cuda.synchronize()
-    n_g, ms_g, ops_g = prof(0)
-    prof_steps = 1 if args.graph else max(prof_steps, 1)
-    per_variant = {}
-    for name, fuse in (("default", 0), ("silu", 1), ("gelu_quant", 2), ("rmsnorm_rope", 3)):
-        n_v_, ms_v_, ops_v_ = prof(0 | ((fuse + 1) << 8))  # SVDQ_PROF_GEMM_VARIANT(fuse), include/svdq_amd.h
-        if n_v_:
-            tops = ops_v_ / (ms_v_ * 1e-3) / 1e12
-            per_variant[name] = {"launches_per_step": n_v_ / prof_steps, "avg_launch_us": ms_v_ * 1e3 / n_v_, "ms_per_step": ms_v_ / prof_steps,
-                                 "TOPs": tops, "frac": tops / INT8_PEAK_TOPS}
-    # the quantiser's numbers come from ONE extra, untimed step bracketed on its class only
-    lib.svdq_prof_select(1 << 1)
-    lib.svdq_prof_reset()
-    step(total - 1, latents)
-    torch.cuda.synchronize()
-    n_q, ms_q, bytes_q = prof(1)
-    # ... and the attention kernel's from another one
-    lib.svdq_prof_select(1 << 2)
-    lib.svdq_prof_reset()
-    step(total - 1, latents)
-    torch.cuda.synchronize()
-    n_a, ms_a, flops_a = prof(2)
-    # ... and the AWQ GEMV's (the modulation projections: one batched launch per step) from a third
-    lib.svdq_prof_select(1 << 3)
-    lib.svdq_prof_reset()
-    step(total - 1, latents)
-    torch.cuda.synchronize()
-    n_v, ms_v, bytes_v = prof(3)
-    lib.svdq_prof_enable(0)
-    lib.svdq_prof_select(0xFFFFFFFF)
+    if args.dump_outputs:  # before anything else runs: under --graph the latents are the graph's output buffer
+        dump_outputs(args.dump_outputs, {"latents" if rank == 0 else f"latents_rank{rank}": latents}, DUMP_BUDGET_BYTES // world)
+    full = measure_full(args, model, step, eager_step, latents, total, clock, clock_ghz, lib, rank, world) if args.full else {}
 
     if rank == 0:
-        achieved = ops_g / (ms_g * 1e-3) / 1e12 if ms_g > 0 else 0.0
-        traffic, traffic_file, traffic_fresh = committed_traffic()
         if qwen:
             workload = (f"Qwen-Image-shaped transformer step, {res_name} ({t_img} image + {t_txt} text tokens), bs=1 "
                         f"per GPU, {len(model.transformer_blocks)} dual-stream blocks, int4 rank-{args.rank}" + (f" + rank-{args.lora} runtime LoRA" if args.lora else "") + ", random-init weights, " +
@@ -457,8 +559,8 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
-            # the same loop with HIP events around every gemm_w4a4 launch (the steps the roofline object was measured on; null: --no-prof / --graph)
-            "ms_per_step_instrumented": ms_instrumented,
+            # the same loop with HIP events around every gemm_w4a4 launch (the steps the roofline object was measured on; null: no --full, --no-prof, --graph)
+            "ms_per_step_instrumented": None,
             "higher_is_better": True,
             "scaling": "weak",
             # aggregate steps/s (value) and the slowest / fastest replica's own rate over its K steps
@@ -476,53 +578,10 @@ def main():
                                f"({bcast_bytes / 1e9:.2f} GB)" + ("; step replayed as one HIP graph" if args.graph else ""),
                 "output_finite": finite,
             },
-            "roofline": {
-                "kernel": "svdq::gemm_w4a4_kernel (all epilogue variants)",
-                "bound": "mfma",
-                "achieved": achieved,
-                "peak": INT8_PEAK_TOPS,
-                "unit": "TOP/s",
-                "frac": achieved / INT8_PEAK_TOPS,
-                "frac_int8": achieved / INT8_PEAK_TOPS,   # BASELINE.json's yardstick
-                "frac_fp6": achieved / FP6_PEAK_TOPS,     # the matrix pipe the 4-bit product actually runs on
-                "traffic": traffic,
-                "traffic_source": f"committed: {traffic_file} (rocprofv3 PMC passes of this command: "
-                                  "2*FETCH_SIZE + WRITE_SIZE per gemm_w4a4 dispatch); not measured in this run",
-                "traffic_stale": not traffic_fresh,   # true: the kernel sources changed since that file was measured
-                "mfma_util": committed_mfma_util(),
-                # share of a tile's cycles behind the main loop per epilogue variant (committed probe measurement): what the launch-level
-                # fraction loses against the loop's own
-                "epilogue_share": committed_epilogue_share(),
-                # shader clock during the timed region (pp_dpm_sclk sampled every 50 ms on rank 0): the chip runs these kernels at its power
-                # limit; profiles/r4_clock_instrument.txt ties this reading to GRBM_GUI_ACTIVE / dispatch duration
-                "effective_clock_ghz": clock_ghz,
-                "effective_clock_ghz_prof_steps": clock_ghz_prof,   # the same reading over the instrumented steps (where `achieved` was measured)
-                "per_variant": per_variant,
-                # the three per-variant fractions once more as flat keys (the driver's record keeps scalars of this object and drops nested ones)
-                **{f"frac_{k}": v["frac"] for k, v in per_variant.items()},
-                **{f"avg_launch_us_{k}": v["avg_launch_us"] for k, v in per_variant.items()},
-                "launches": n_g,
-                "prof_steps": prof_steps,
-                "avg_launch_us": ms_g * 1e3 / max(n_g, 1),
-                "gemm_ms_per_step": ms_g / prof_steps,
-                "measured_on": "one extra eager step (graph replay in the timed region)" if args.graph else
-                               f"{prof_steps} steps run right behind the timed region with HIP events around every gemm_w4a4 launch (the timed region itself carries none)",
-                "quantize": {"launches": n_q, "ms_per_step": ms_q, "measured_on": "one extra untimed step",
-                             "GBps": bytes_q / (ms_q * 1e-3) / 1e9 if ms_q > 0 else 0.0, "bound": "hbm"},
-                "attention": {"launches": n_a, "ms_per_step": ms_a, "measured_on": "one extra untimed step",
-                              "TFLOPs": flops_a / (ms_a * 1e-3) / 1e12 if ms_a > 0 else 0.0, "bound": "mfma",
-                              "frac_bf16": (flops_a / (ms_a * 1e-3) / 1e12 / BF16_PEAK_TFLOPS) if ms_a > 0 else 0.0},
-                "gemv_awq": {"launches": n_v, "ms_per_step": ms_v, "measured_on": "one extra untimed step",
-                             "GBps": bytes_v / (ms_v * 1e-3) / 1e9 if ms_v > 0 else 0.0, "bound": "hbm by bytes, VALU in practice"},
-            },
+            "roofline": None,       # --full
+            "cpu_baseline": None,   # --full
         }
-        # ... and at the top level of the contract line
-        for k, v in per_variant.items():
-            line[f"roofline_frac_{k}"] = v["frac"]
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline()
-        else:
-            line["cpu_baseline"] = None
+        line.update(full)
         print(json.dumps(line), flush=True)
 
     if world > 1:

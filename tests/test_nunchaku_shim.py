@@ -1,17 +1,12 @@
 """The ``nunchaku`` import surface: the reference's package layout resolves to the MI355X
-implementation, and -- where the reference tree is present (this container; not the GPU box) -- the reference's OWN,
-UNMODIFIED ``ops/*.py`` and ``models/linear.py`` import and run against the shim ``nunchaku._C`` up to the first kernel
-launch (which needs a GPU: the call must arrive in this library with the reference's positional arguments)."""
-import importlib
-import importlib.util
+implementation, and the calls the reference's OWN, UNMODIFIED ``ops/*.py`` and ``models/linear.py`` make into ``nunchaku._C``
+(recorded once from those files: tests/golden/reference_shim_calls.json) run against the shim up to the first kernel launch
+(which needs a GPU: the call must arrive in this library with the reference's positional arguments)."""
+import json
 import os
-import sys
-import types
 
 import pytest
 import torch
-
-REF = "/root/reference/nunchaku"
 
 
 def test_reference_import_paths_resolve():
@@ -38,56 +33,29 @@ def test_reference_import_paths_resolve():
     assert CPUOffloadManager.__name__ == "CPUOffloadManager" and AWQW4A16Linear and NunchakuQwenImageTransformer2DModel and nunchaku.__all__
 
 
-def _load_reference_as(pkg_name: str):
-    """A synthetic package ``pkg_name`` whose ``_C`` is this repo's shim and whose ``utils``, ``ops.*`` and ``models.linear``
-    are the reference's files, loaded by path, unmodified."""
-    import nunchaku._C as shim_c
-
-    def module(name, path=None, is_pkg=False):
-        if path is None:
-            m = types.ModuleType(name)
-            m.__path__ = []
-        else:
-            spec = importlib.util.spec_from_file_location(name, path, submodule_search_locations=[] if is_pkg else None)
-            m = importlib.util.module_from_spec(spec)
-        sys.modules[name] = m
-        return m
-
-    module(pkg_name)
-    sys.modules[pkg_name + "._C"] = shim_c
-    sys.modules[pkg_name]._C = shim_c
-    u = module(pkg_name + ".utils", os.path.join(REF, "utils.py"))
-    try:
-        u.__spec__.loader.exec_module(u)
-    except ImportError as e:  # the reference's utils.py imports safetensors / huggingface_hub at module level
-        pytest.skip(f"reference utils.py needs a package that is not installed: {e}")
-    module(pkg_name + ".ops")
-    mods = {}
-    for sub in ("quantize", "gemm", "gemv", "fused"):
-        pass
-    module(pkg_name + ".models")
-    for name, rel in ((".ops.quantize", "ops/quantize.py"), (".ops.gemm", "ops/gemm.py"), (".ops.gemv", "ops/gemv.py"),
-                      (".models.linear", "models/linear.py"), (".ops.fused", "ops/fused.py")):
-        m = module(pkg_name + name, os.path.join(REF, rel))
-        m.__spec__.loader.exec_module(m)
-        mods[name] = m
-    return mods
+def _make(desc):
+    if "tensor" in desc:
+        return torch.zeros(desc["tensor"]["shape"], dtype=getattr(torch, desc["tensor"]["dtype"]))
+    return desc["value"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree only exists in the build container")
-def test_unmodified_reference_callers_bind_to_the_shim():
-    mods = _load_reference_as("_ref_nunchaku")
-    RefLinear = mods[".models.linear"].SVDQW4A4Linear
-    lin = RefLinear(128, 256, rank=16, torch_dtype=torch.bfloat16, device="cpu")
-    assert tuple(lin.qweight.shape) == (256, 64)
-    x = torch.zeros(1, 4, 128, dtype=torch.bfloat16)
+def test_unmodified_reference_callers_bind_to_the_shim(golden_dir):
+    """The calls the reference's own ``ops/*.py`` and ``models/linear.py`` make into ``_C.ops`` (recorded from the unmodified files by
+    tools/make_shim_calls.py -> tests/golden/reference_shim_calls.json) arrive in this library with the reference's positional arguments."""
+    from nunchaku import _C
+    from nunchaku.models.linear import SVDQW4A4Linear
+
+    rec = json.load(open(os.path.join(golden_dir, "reference_shim_calls.json")))
+    # the reference's SVDQW4A4Linear(128, 256, rank=16) holds the same parameters as ours
+    assert tuple(rec["linear_128_256_r16"]["qweight"]["shape"]) == (256, 64)
+    ours = SVDQW4A4Linear(128, 256, rank=16, torch_dtype=torch.bfloat16, device="cpu").state_dict()
+    assert {k: {"shape": list(v.shape), "dtype": str(v.dtype).replace("torch.", "")} for k, v in ours.items()} == rec["linear_128_256_r16"]
     # the reference's forward -> its quantize() -> its ops/quantize.py wrapper (allocates the [M_pad, K/2] buffer) -> shim
     # _C.ops.quantize_w4a4_act_fuse_lora with the reference's 8 positional arguments: arrives in this library, which has no
-    # CPU path and says so (on a GPU the same call runs: tests/test_gpu_parity.py::test_reference_style_calls...)
-    with pytest.raises(RuntimeError, match="no CPU path|need GPU tensors"):
-        lin(x)
-    fused = mods[".ops.fused"]
-    fc1 = RefLinear(128, 256, rank=16, torch_dtype=torch.bfloat16, device="cpu")
-    fc2 = RefLinear(256, 128, rank=16, torch_dtype=torch.bfloat16, device="cpu")
-    with pytest.raises(RuntimeError, match="no CPU path|need GPU tensors"):
-        fused.fused_gelu_mlp(x, fc1, fc2)
+    # CPU path and says so (on a GPU the same call runs: tests/test_gpu_parity.py::test_reference_style_calls...); the same for fused_gelu_mlp
+    assert set(rec["calls"]) == {"SVDQW4A4Linear.forward", "fused_gelu_mlp"}
+    for call in rec["calls"].values():
+        args = [_make(a) for a in call["args"]]
+        kwargs = {k: _make(v) for k, v in call["kwargs"].items()}
+        with pytest.raises(RuntimeError, match="no CPU path|need GPU tensors"):
+            getattr(_C.ops, call["op"])(*args, **kwargs)
