@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define SVDQ_ABI_VERSION 22
+#define SVDQ_ABI_VERSION 23
 
 /* model dtype of the 16-bit tensors */
 enum { SVDQ_BF16 = 0, SVDQ_FP16 = 1 };
@@ -458,6 +458,39 @@ int svdq_gemv_awq(const svdq_gemv_awq_args *args, void *stream);
  * out / N / out_chunks; x, M, K, ldx, group_size and dtype are taken from args[0]. */
 #define SVDQ_GEMV_BATCH_MAX 80
 int svdq_gemv_awq_batched(const svdq_gemv_awq_args *args, int32_t count, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * AWQ W4A16 GEMM, group 128 (ABI 23; reference: ops.gemm_awq, nunchaku/csrc/ops.h:148-160 -> src/kernels/awq/gemm_awq.cu;
+ * module nunchaku/models/text_encoders/linear.py, W4Linear).  The projections of the 4-bit T5 text encoder, any M >= 1.
+ *   w16[n, k] = round16( fma(q[n,k], scales[k/128, n], scaled_zeros[k/128, n]) )     one 16-bit rounding (__hfma2)
+ *   out[m, n] = round16( sum_k w16[n,k] * x[m,k] )                                    exact products, fp32 sums (MFMA)
+ *   (+ bias[n], optional: one more 16-bit rounding, W4Linear.forward's `out + bias`)
+ * qweight is the CHECKPOINT tensor as stored: [N/4, K] int16 (the same bytes as the GEMV's [N/4, K/2] int32), tinychat
+ * pack_w4 order -- no load-time repack.  scales / scaled_zeros are [G_pad, N] 16-bit with G_pad >= K/128 (the converter
+ * pads G_pad to ceil_num_groups; rows >= K/128 are not read).  K % 128 == 0, N % 64 == 0, group_size == 128 (else
+ * SVDQ_E_UNSUPPORTED).  fp16 outputs beyond the range go to +-inf (round to nearest, no clamp), as in the reference.
+ * K-split: a launch whose output tiles do not fill the chip splits K into slices; each slice stores fp32 partial tiles into
+ * `workspace` and a second kernel adds them in slice order (bit-identical from launch to launch).  workspace = NULL: no
+ * split (same contract, another fp32 summation order); a non-NULL workspace must hold svdq_gemm_awq_workspace_bytes(M, N, K)
+ * bytes (16-byte aligned; no zero fill needed), else SVDQ_E_INVALID.  The plan depends on (M, N, K) only, not on the device.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct svdq_gemm_awq_args {
+    const void *x;            /* [M, K] 16-bit, row stride ldx (>= K, % 8 == 0), 16-byte aligned */
+    const void *qweight;      /* [N/4, K] int16, 16-byte aligned */
+    const void *scales;       /* [G_pad, N] 16-bit */
+    const void *scaled_zeros; /* [G_pad, N] 16-bit (zeros already scaled and negated: w = q*scale + scaled_zero) */
+    const void *bias;         /* [N] 16-bit or NULL */
+    void *out;                /* [M, N] 16-bit, contiguous */
+    void *workspace;          /* fp32 partial tiles of the K-split, or NULL */
+    int64_t workspace_bytes;
+    int32_t M, N, K, ldx;
+    int32_t group_size;       /* must be 128 */
+    int32_t dtype;            /* SVDQ_BF16 | SVDQ_FP16 */
+} svdq_gemm_awq_args;
+
+int svdq_gemm_awq(const svdq_gemm_awq_args *args, void *stream);
+/* workspace bytes a launch of this shape uses (0: it does not split K) */
+int64_t svdq_gemm_awq_workspace_bytes(int32_t M, int32_t N, int32_t K);
 
 /* ------------------------------------------------------------------------------------------
  * Load-time re-layout of reference checkpoint tensors (NVIDIA fragment order -> CDNA4 order).

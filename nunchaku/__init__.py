@@ -5,7 +5,9 @@
 (reference: nunchaku/__init__.py:1-17, nunchaku/csrc/pybind.cpp:108-123).  ``nunchaku._C.ops`` takes the reference's
 positional signatures, reference-sized opaque buffers and checkpoint-layout parameters (nunchaku_amd/_C.py), so the
 reference's own ``ops/*.py`` / ``models/linear.py`` callers run against it unchanged (tests/test_nunchaku_shim.py).
-Model families outside the FLUX / Qwen-Image hot path (SANA, Z-Image, T5) are not part of this package.
+``from nunchaku import NunchakuT5EncoderModel`` is the 4-bit T5 text encoder of the FLUX pipelines (AWQ W4A16 group-128
+linears on ``ops.gemm_awq``); transformers is imported on first access of that name, so ``import nunchaku`` works without it.
+Model families outside these (SANA, Z-Image) are not part of this package.
 """
 from .models import (  # noqa: F401
     NunchakuFluxTransformer2dModel,
@@ -13,4 +15,12 @@ from .models import (  # noqa: F401
     NunchakuQwenImageTransformer2DModel,
 )
 
-__all__ = ["NunchakuFluxTransformer2dModel", "NunchakuFluxTransformer2DModelV2", "NunchakuQwenImageTransformer2DModel"]
+__all__ = ["NunchakuFluxTransformer2dModel", "NunchakuFluxTransformer2DModelV2", "NunchakuQwenImageTransformer2DModel"]  # (+ NunchakuT5EncoderModel, lazily)
+
+
+def __getattr__(name):
+    if name == "NunchakuT5EncoderModel":
+        from .models.text_encoders.t5_encoder import NunchakuT5EncoderModel
+
+        return NunchakuT5EncoderModel
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -142,10 +142,11 @@ def _workspace(device: torch.device, kind: str = "gemm", min_bytes: int = 0) -> 
         grown = True
     if ws is None:
         lib = _lib.load()
-        size = lib.svdq_attention_workspace_bytes() if kind == "attention" else lib.svdq_gemm_workspace_bytes()
+        # (kind "awq": the fp32 partial tiles of gemm_awq's K-split -- no counters, no status word, sized by the launch)
+        size = lib.svdq_attention_workspace_bytes() if kind == "attention" else 0 if kind == "awq" else lib.svdq_gemm_workspace_bytes()
         with torch.cuda.device(idx):
             buf = torch.zeros(max(int(size), int(min_bytes)), dtype=torch.uint8, device=device)
-        ws = _Workspace(buf, _status_word())
+        ws = _Workspace(buf, None if kind == "awq" else _status_word())
         _workspaces[key] = ws
         _evict(kind, key)
     else:
@@ -684,6 +685,49 @@ class _Ops:
         a.M, a.N, a.K, a.ldx = m, n, k, x2.stride(0) if m > 1 else k
         a.group_size, a.dtype, a.out_chunks = group_size, _DT[in_feats.dtype], int(out_chunks)
         _lib.check(lib.svdq_gemv_awq(C.byref(a), _stream()), "gemv_awq")
+        return out
+
+    @staticmethod
+    def gemm_awq(in_feats, kernel, scaling_factors, zeros, bias=None):
+        """reference: csrc/ops.h:148-160 -> awq_gemm_forward_cuda (src/kernels/awq/gemm_awq.cu), group size 128: allocates and returns
+        ``in_feats.shape[:-1] + (N,)`` with ``N = kernel.shape[0] * 4``, ``K = in_feats.shape[-1]``.  ``kernel`` is the checkpoint's
+        ``qweight`` as stored ([N/4, K] int16, or the same bytes as [N/4, K/2] int32); ``scaling_factors`` / ``zeros`` are
+        ``[>= K/128, N]`` (scaled zeros).  Any number of rows.  ``bias`` (extension) fuses W4Linear.forward's 16-bit ``out + bias``.
+        A launch that splits K takes its fp32 partial tiles from the stream's cached workspace (``_workspace(kind="awq")``)."""
+        lib = _lib.load()
+        if in_feats.dtype not in _DT or scaling_factors.dtype != in_feats.dtype or zeros.dtype != in_feats.dtype:
+            raise ValueError("gemm_awq: in_feats, scaling_factors and zeros must share one 16-bit dtype")
+        if in_feats.dim() < 1 or kernel.dim() != 2 or kernel.dtype not in (torch.int16, torch.int32):
+            raise ValueError("gemm_awq: kernel must be the [N/4, K] int16 (or [N/4, K/2] int32) qweight")
+        K, N = in_feats.shape[-1], kernel.shape[0] * 4
+        if kernel.shape[1] * kernel.element_size() != 2 * K:
+            raise ValueError(f"gemm_awq: kernel {tuple(kernel.shape)} {kernel.dtype} does not hold N x K = {N} x {K} 4-bit codes")
+        if scaling_factors.dim() != 2 or scaling_factors.shape[1] != N or scaling_factors.shape[0] < K // 128 or zeros.shape != scaling_factors.shape:
+            raise ValueError("gemm_awq: scaling_factors / zeros must be [>= K/128, N]")
+        if bias is not None and (bias.dtype != in_feats.dtype or bias.numel() != N):
+            raise ValueError("gemm_awq: bias must be [N] in the dtype of in_feats")
+        for t in (in_feats, kernel, scaling_factors, zeros):
+            if not t.is_cuda:
+                raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
+        M = in_feats.numel() // K if K else 0
+        out = torch.empty(*in_feats.shape[:-1], N, dtype=in_feats.dtype, device=in_feats.device)
+        if M == 0:
+            return out
+        x2 = in_feats.reshape(M, K)
+        if x2.stride(1) != 1 or (M > 1 and x2.stride(0) % 8) or x2.data_ptr() % 16:
+            x2 = x2.contiguous()
+        a = _lib.GemmAwqArgs()
+        a.x, a.qweight, a.scales, a.scaled_zeros = x2.data_ptr(), _ptr(kernel), _ptr(scaling_factors), _ptr(zeros)
+        a.bias, a.out = _ptr(bias), out.data_ptr()
+        a.M, a.N, a.K, a.ldx = M, N, K, x2.stride(0) if M > 1 else K
+        a.group_size, a.dtype = 128, _DT[in_feats.dtype]
+        if K % 128 == 0 and N % 64 == 0:  # (otherwise the library reports the shape)
+            need = int(lib.svdq_gemm_awq_workspace_bytes(M, N, K))
+            if need:
+                ws = _workspace(in_feats.device, "awq", min_bytes=need)
+                if ws.buf.numel() >= need:  # (a capture cannot grow the buffer: that launch runs without the K-split)
+                    a.workspace, a.workspace_bytes = ws.buf.data_ptr(), ws.buf.numel()
+        _lib.check(lib.svdq_gemm_awq(C.byref(a), _stream()), "gemm_awq")
         return out
 
     @staticmethod

@@ -12,7 +12,7 @@ _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "li
 
 SVDQ_BF16, SVDQ_FP16 = 0, 1
 FUSE_NONE, FUSE_SILU, FUSE_GELU_QUANT, FUSE_RMSNORM_ROPE = 0, 1, 2, 3
-ABI_VERSION = 22
+ABI_VERSION = 23
 LORA_ACT_F32, LORA_ACT_Q32, LORA_ACT_Q32_RUNS = 0, 1, 2
 
 
@@ -85,12 +85,23 @@ class GemvAwqArgs(C.Structure):
     ]
 
 
+class GemmAwqArgs(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("qweight", C.c_void_p), ("scales", C.c_void_p), ("scaled_zeros", C.c_void_p),
+        ("bias", C.c_void_p), ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("ldx", C.c_int32),
+        ("group_size", C.c_int32), ("dtype", C.c_int32),
+    ]
+
+
 EXPORTS = {
     "svdq_quantize_w4a4_act_fuse_lora": (C.c_int, [C.POINTER(QuantizeArgs), C.c_void_p]),
     "svdq_gemm_w4a4": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
     "svdq_attention": (C.c_int, [C.POINTER(AttentionArgs), C.c_void_p]),
     "svdq_gemv_awq": (C.c_int, [C.POINTER(GemvAwqArgs), C.c_void_p]),
     "svdq_gemv_awq_batched": (C.c_int, [C.POINTER(GemvAwqArgs), C.c_int32, C.c_void_p]),
+    "svdq_gemm_awq": (C.c_int, [C.POINTER(GemmAwqArgs), C.c_void_p]),
+    "svdq_gemm_awq_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "svdq_residual_gate_stats": (C.c_int, [C.POINTER(ResidualArgs), C.c_void_p]),
     "svdq_gemm_workspace_bytes": (C.c_int64, []),
     "svdq_gemm_workspace_bytes_for": (C.c_int64, [C.POINTER(GemmArgs)]),
