@@ -182,7 +182,10 @@ def release_workspaces() -> None:
 #   * a weight-side tensor that does not carry the `_svdq_amd` mark (set by SVDQW4A4Linear on its Parameters) is taken to be
 #     in the checkpoint layout and converted on first use; the converted copy is cached per storage and reused until the
 #     tensor is modified through torch (``_version``) or ``invalidate()`` is called (writes through ``.data`` do not bump
-#     the version: LoRA / offload code that updates weights that way must call it);
+#     the version: code that updates weights that way must call it).  The same holds for the fragment images of marked
+#     low-rank factors (``_packed_fragments``).  The library's own writers bump the version: ``replica.broadcast_module_``
+#     writes receivers with ``t.copy_``, and the offload slots (models/offload.py) hold their parameters as views of the
+#     slot's flat buffer, which share its version counter, so the ``flat.copy_`` of every block load bumps all of them;
 #   * packed Q / K / V buffers of the "nunchaku-fp16" attention surface remember which token rows are real.
 # An entry dies with its storage (weakref.finalize on the storage object: the last view going away frees the side data too,
 # stream-ordered through the caching allocator like the buffer itself).

@@ -198,11 +198,20 @@ class CPUOffloadManager:
                 t = getattr(m, tn)
                 if nib is not None:
                     N, K = nib
-                    img = torch.empty(N, K * 3 // 4, dtype=torch.int8, device=device)
-                    t.data = img
-                    expand.append((flat[o:o + size], img, N, K))
+                    dev_t = torch.empty(N, K * 3 // 4, dtype=torch.int8, device=device)
+                    expand.append((flat[o:o + size], dev_t, N, K))
                 else:
-                    t.data = flat[o:o + size].view(t.dtype).view(t.shape)
+                    dev_t = flat[o:o + size].view(t.dtype).view(t.shape)
+                # The slot's tensors ARE the views (not `t.data = view`, which keeps the copy's own version counter): a view shares the
+                # version counter of `flat`, so every load's `flat.copy_` bumps `_version` of all of them and nunchaku_amd._C re-packs the
+                # fragment images it caches per (storage, version) -- the low-rank factors of a new tenant are never served from the
+                # previous tenant's images.  The image an entry replaces was allocated on the compute stream and is read only by kernels
+                # queued there; the caching allocator hands its memory out again only to later work of that stream, so freeing it while
+                # such a kernel is still queued is safe (the load itself runs on the memory stream and never touches the images).
+                if tn in m._parameters:
+                    m._parameters[tn] = nn.Parameter(dev_t, requires_grad=t.requires_grad)
+                else:
+                    m._buffers[tn] = dev_t
             for m in module.modules():
                 if isinstance(m, SVDQW4A4Linear):
                     m._set_amd_names(set(m._layout_params()))  # everything in the kernel layout once a load has landed

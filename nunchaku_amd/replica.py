@@ -83,7 +83,9 @@ def broadcast_module_(module: torch.nn.Module, src: int = 0, bucket_bytes: int =
         dist.broadcast(buf, src=src)
         if not is_src:
             for t, o, sz in zip(group, offs, sizes):
-                t.data.copy_(buf[o:o + sz].view(t.dtype).view(t.shape))
+                # through the tensor itself, not `.data`: the write bumps `t._version`, so conversions and fragment images that
+                # nunchaku_amd._C cached from this receiver's earlier weights are rebuilt at their next use
+                t.copy_(buf[o:o + sz].view(t.dtype).view(t.shape))
         total += sum(sizes)
 
     group, acc = [], 0

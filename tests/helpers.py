@@ -85,3 +85,33 @@ def checked_codes(qx, asc, x: np.ndarray, smooth, dtype: str, max_flips: float =
     assert np.all(scales >= env["s_lo"]) and np.all(scales <= env["s_hi"]), "quantiser scales outside the approximation envelope"
     assert (scales != a_ieee).mean() <= max_flips, f"{(scales != a_ieee).sum()} scales differ from the IEEE oracle"
     return codes, scales
+
+
+def served_fragment_images(module: torch.nn.Module):
+    """The MFMA-fragment images of low-rank factors (``nunchaku_amd._C._packed_fragments``, ABI 21) that the cache would SERVE for the parameters of
+    ``module`` now -- entries whose version is the parameter's current ``_version`` -- each compared with a fresh pack of the parameter's current
+    bytes.  Returns ``(images checked, names of the parameters whose served image differs)``.  Bytes a pack does not write (padding) are not compared:
+    they are found by packing twice into buffers filled with different bytes.  Synchronises the device."""
+    from nunchaku_amd import _C, _lib
+
+    lib = _lib.load()
+    torch.cuda.synchronize()
+    checked, stale = 0, []
+    for name, p in module.named_parameters():
+        for (kind, off, shape), (ver, img) in (_C._converted.get(p) or {}).items():
+            if not kind.startswith("frag_") or off != p.storage_offset() or shape != tuple(p.shape) or ver != p._version:
+                continue
+            down = kind == "frag_down"
+            N, R = shape  # down: [K, R]-shaped rank-major image of the factor, N = K; up: [N, R]
+            fresh = []
+            for fill in (0x00, 0xFF):
+                out = torch.full((img.numel(),), fill, dtype=torch.uint8, device=p.device)
+                fn = lib.svdq_pack_lora_down if down else lib.svdq_pack_lora_up
+                _lib.check(fn(p.data_ptr(), out.data_ptr(), N, R, _C._DT[p.dtype], torch.cuda.current_stream().cuda_stream), kind)
+                fresh.append(out)
+            torch.cuda.synchronize()
+            written = fresh[0] == fresh[1]
+            checked += 1
+            if not torch.equal(img[written], fresh[0][written]):
+                stale.append(name)
+    return checked, stale

@@ -389,6 +389,159 @@ def test_cached_fragment_images_of_low_rank_factors_follow_the_parameter():
         _Ops.cache_packed_lowrank = True
 
 
+def _offload_slot_of_lowrank_layers(rank=128):
+    """A real offload slot (models/offload.py) holding rank-``rank`` layers: fc1 256 -> 1024 and fc2 1024 -> 256 of two streams (a, b).  Block 0 stays
+    resident, blocks 1 and 2 (other weights) live in pinned host images; ``load_block(i, slot=0)`` writes block i into slot 0's flat buffer with one
+    ``flat.copy_``, and the slot's parameters are kernel-layout views of that buffer (the layers' marks: ``_C.mark_amd``)."""
+    from torch import nn
+    from nunchaku_amd.models.offload import CPUOffloadManager
+
+    dtype, C, Hd = "bf16", 256, 1024
+    blocks = []
+    for b in range(3):
+        seed = 400 + 10 * b
+        blocks.append(nn.ModuleDict({
+            "fc1a": make_module(O.make_svdq_layer(C, Hd, rank, seed=seed, dtype=dtype, cheap=True), dtype),
+            "fc2a": make_module(O.make_svdq_layer(Hd, C, rank, seed=seed + 1, dtype=dtype, cheap=True), dtype, act_unsigned=True),
+            "fc1b": make_module(O.make_svdq_layer(C, Hd, rank, seed=seed + 2, dtype=dtype, cheap=True), dtype),
+            "fc2b": make_module(O.make_svdq_layer(Hd, C, rank, seed=seed + 3, dtype=dtype, cheap=True), dtype, act_unsigned=True)}))
+    mgr = CPUOffloadManager(blocks, device="cuda", num_blocks_on_gpu=1, num_slots=2)
+    mgr.load_block(1, slot=0)
+    return mgr, mgr._slots[0]
+
+
+def _lowrank_site(site, s):
+    """One launch of consumer ``site`` of the fragment cache on the slot's layers ``s``.  Returns (bit-exact outputs, low-rank accumulators, the
+    parameters whose fragment images it reads, plan check).  The activation side is quantised once per weight state (``prepare``), so the cached and
+    the uncached launch get the same inputs."""
+    from nunchaku_amd import layout
+    from nunchaku_amd._C import ops
+    from nunchaku_amd.ops.attention import attention_packed_quantized
+    from nunchaku_amd.ops.fused import _quantize_pair, _second
+    from nunchaku_amd.ops.gemm import svdq_gemm_w4a4_cuda
+
+    dtype, C, Hd, R = "bf16", 256, 1024, s.fc1a.rank
+    td = TORCH_DT[dtype]
+    if site == "attention":  # the fused quantiser of attention_packed_quantized: split low-rank down projection, two parameter sets (text rows first)
+        g = torch.Generator(device="cuda").manual_seed(5)
+        L = 512
+        qkv = (torch.randn(L, 3 * C, device="cuda", generator=g) * 0.5).to(td)
+        vt = (torch.randn(C, L, device="cuda", generator=g) * 0.5).to(td)
+
+        def prepare():
+            return None
+
+        def launch(_):
+            act, asc, lact = attention_packed_quantized(qkv, vt, 2, s.fc1a, lin_first=s.fc1b, split_rows=256)
+            assert ops.attention_last_plan()["split_lowrank"], ops.attention_last_plan()
+            return (act, asc), lact
+
+        return prepare, launch, (s.fc1b.proj_down, s.fc1a.proj_down), 0
+    xa = t16(O.make_activations(300 if site != "pair" else 256, C, seed=33, dtype=dtype), dtype)
+    xb = t16(O.make_activations(256, C, seed=34, dtype=dtype), dtype)
+    if site == "lora_up":  # plain epilogue, rank 48 .. 160 on 128 x 128 tiles: both low-rank operands as packed fragments (geometry 2)
+        def prepare():
+            return s.fc1a.quantize(xa)
+
+        def launch(inp):
+            qx, asc, la = inp
+            out = torch.empty(qx.shape[0], Hd, dtype=td, device="cuda")
+            s.fc1a.forward_quant(qx, asc, la, out)
+            assert ops.gemm_last_plan()["lora_up_packed"], ops.gemm_last_plan()
+            return (out,), None
+
+        return prepare, launch, (s.fc1a.proj_up,), 2
+    if site == "gelu_quant":  # GELU_QUANT, N % 256 == 0: the split down projection of the next layer (geometry 7)
+        def prepare():
+            return s.fc1a.quantize(xa)
+
+        def launch(inp):
+            qx, asc, la = inp
+            M_pad = qx.shape[0]
+            qh = torch.empty(layout.act_image_shape(M_pad, Hd), dtype=torch.uint8, device="cuda")
+            sh = torch.empty(Hd // 64, M_pad, dtype=td, device="cuda")
+            lh = torch.empty(M_pad, R, dtype=torch.float32, device="cuda")
+            svdq_gemm_w4a4_cuda(act=qx, wgt=s.fc1a.qweight, qout=qh, ascales=asc, wscales=s.fc1a.wscales, oscales=sh, lora_act_in=la,
+                                lora_up=s.fc1a.proj_up, lora_down=s.fc2a.proj_down, lora_act_out=lh, bias=s.fc1a.bias,
+                                smooth_factor=s.fc2a.smooth_factor)
+            assert ops.gemm_last_plan()["variant"] == "split_down", ops.gemm_last_plan()
+            return (qh, sh), lh
+
+        return prepare, launch, (s.fc2a.proj_down,), 7
+    assert site == "pair"  # the grouped two-weight GELU_QUANT launch of fused_gelu_mlp_pair (second weight set from row 256 on)
+
+    def prepare():
+        return _quantize_pair(xa[None], s.fc1a, xb[None], s.fc1b)  # [1, tokens, C] streams
+
+    def launch(inp):
+        act, asc, lact, Ma = inp
+        Mt = act.shape[0]
+        qh = torch.empty(Mt, Hd * 3 // 4, dtype=torch.uint8, device="cuda")
+        sh = torch.empty(Hd // 64, Mt, dtype=td, device="cuda")
+        lh = torch.empty(Mt, R, dtype=torch.float32, device="cuda")
+        svdq_gemm_w4a4_cuda(act=act, wgt=s.fc1a.qweight, qout=qh, ascales=asc, wscales=s.fc1a.wscales, oscales=sh, lora_act_in=lact,
+                            lora_up=s.fc1a.proj_up, lora_down=s.fc2a.proj_down, lora_act_out=lh, bias=s.fc1a.bias,
+                            smooth_factor=s.fc2a.smooth_factor, second=_second(s.fc1b, smooth_factor=s.fc2b.smooth_factor, lora_down=s.fc2b.proj_down),
+                            split_rows=Ma)
+        assert ops.gemm_last_plan()["variant"] == "split_down", ops.gemm_last_plan()
+        return (qh, sh), lh
+
+    return prepare, launch, (s.fc2a.proj_down, s.fc2b.proj_down), 7
+
+
+@pytest.mark.parametrize("write", ["slot_load", "data_assign", "data_copy_invalidate"])
+@pytest.mark.parametrize("site", ["lora_up", "gelu_quant", "pair", "attention"])
+def test_cached_fragment_images_follow_writes_that_bypass_the_parameter(site, write):
+    """Each consumer of the ABI 21 fragment cache (``lora_up_packed``, ``next_lora_down_packed``, its grouped form ``next_lora_down_packed2``, the
+    attention quantiser's ``qlora_down_packed(2)``) after the weights were rewritten behind the parameter's back: a block load into an offload slot
+    (``flat.copy_`` into the buffer the parameters view), a ``.data`` assignment of a new tensor, and a ``.data.copy_`` followed by ``_C.invalidate``.
+    The launch after the write must give what a launch that packs on every call (``cache_packed_lowrank = False``) gives on the new weights: codes,
+    scales and 16-bit outputs bit for bit, the fp32 low-rank accumulators to the order of their atomics."""
+    from nunchaku_amd import _C
+    from nunchaku_amd._C import _Ops
+
+    mgr, slot = _offload_slot_of_lowrank_layers()
+    s = slot.module
+    prepare, launch, readers, geometry = _lowrank_site(site, s)
+    _Ops.gemm_geometry = geometry
+    try:
+        first = launch(prepare())  # fills the cache from block 1's weights
+        for p in readers:
+            assert p.untyped_storage().data_ptr() == slot.flat.untyped_storage().data_ptr(), "slot parameters view the slot's flat buffer"
+            assert any(k[0].startswith("frag_") for k in _C._converted.get(p) or {}), "a launch at rank 128 caches the factor's fragment image"
+        entries = len(_C._converted.get(slot.flat))
+        if write == "slot_load":
+            mgr.load_block(2, slot=0)
+        else:
+            host = dict(mgr.blocks[2].named_parameters())  # block 2's factors, kernel layout, pinned host image
+            with torch.no_grad():
+                for n, p in s.named_parameters():
+                    if n.rpartition(".")[2] in ("proj_down", "proj_up"):
+                        new = host[n].to("cuda")
+                        if write == "data_assign":
+                            p.data = new
+                        else:
+                            p.data.copy_(new)
+                            _C.invalidate(p)
+        inp = prepare()
+        got_x, got_l = launch(inp)
+        if write == "slot_load":
+            assert len(_C._converted.get(slot.flat)) == entries, "a re-pack replaces the slot's cache entries, it does not add to them"
+        _Ops.cache_packed_lowrank = False
+        want_x, want_l = launch(inp)
+    finally:
+        _Ops.gemm_geometry = 0
+        _Ops.cache_packed_lowrank = True
+    for a, b in zip(got_x, want_x):
+        assert torch.equal(a, b), f"{site} after {write}: {(a != b).sum().item()} of {a.numel()} output elements differ from the launch on the new weights"
+    if want_l is not None:
+        err, top = float((got_l - want_l).abs().max()), float(want_l.abs().max())
+        assert err <= 1e-5 * top + 1e-6, f"{site} after {write}: the low-rank accumulators follow stale fragment images (max err {err:.3e}, max {top:.3e})"
+        assert float((first[1] - want_l).abs().max()) > 1e-2 * top, "the write must change the low-rank result (else the test shows nothing)"
+    else:
+        assert not torch.equal(first[0][0], want_x[0]), "the write must change the result (else the test shows nothing)"
+
+
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
 def test_fused_gelu_mlp(dtype):
     from nunchaku_amd import layout

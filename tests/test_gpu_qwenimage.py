@@ -146,11 +146,24 @@ def test_qwen_block_matches_the_reference_op_sequence(t_txt):
         assert psnr > 55.0, psnr
 
 
-def _small_model(layers=4):
+def _small_model(layers=4, rank=32):
     from nunchaku_amd.models.qwenimage import NunchakuQwenImageTransformer2DModel
 
     return NunchakuQwenImageTransformer2DModel(num_layers=layers, num_attention_heads=2, attention_head_dim=128, in_channels=64,
-                                               out_channels=16, joint_attention_dim=128, device="cuda").init_synthetic_(seed=5).eval()
+                                               out_channels=16, joint_attention_dim=128, rank=rank, device="cuda").init_synthetic_(seed=5).eval()
+
+
+def _fragment_images(blocks) -> dict:
+    """(block, parameter, cache key) -> the cached MFMA-fragment image (nunchaku_amd._C._packed_fragments) of every low-rank factor of ``blocks``"""
+    from nunchaku_amd import _C
+
+    out = {}
+    for i, b in enumerate(blocks):
+        for name, p in b.named_parameters():
+            for k, v in (_C._converted.get(p) or {}).items():
+                if k[0].startswith("frag_") and (k[1], k[2]) == (p.storage_offset(), tuple(p.shape)):
+                    out[(i, name, k)] = v[1]
+    return out
 
 
 def test_qwen_model_offload_auto_keeps_every_block_that_fits():
@@ -180,16 +193,29 @@ def test_qwen_model_offload_auto_keeps_every_block_that_fits():
         CPUOffloadManager(list(model.transformer_blocks), num_blocks_on_gpu="all")
 
 
-@pytest.mark.parametrize("late,num_slots", [(False, 2), (True, 2), (False, 3)], ids=["nibbles", "after-first-forward", "three-slots"])
-def test_qwen_model_offload_equals_resident(late, num_slots):
+_OFFLOAD_VARIANTS = [(False, 2, "nibbles"), (True, 2, "after-first-forward"), (False, 3, "three-slots")]
+
+
+# rank 32 (no fragment images: the control) keeps the variants' plain ids; ranks 64 .. 160 use the fragment cache
+@pytest.mark.parametrize("late,num_slots,rank", [pytest.param(late, slots, rank, id=name if rank == 32 else f"{name}-r{rank}")
+                                                 for rank in (32, 64, 128, 160) for late, slots, name in _OFFLOAD_VARIANTS])
+def test_qwen_model_offload_equals_resident(late, num_slots, rank):
     """set_offload(True): blocks live in pinned host memory (their tensors are views of one flat image each), a ring of device
     slots, copies on a side stream ahead of the compute.  In deterministic mode (fixed-point low-rank accumulation: no
     run-to-run noise) offloaded forwards must equal the resident model BIT FOR BIT -- over several forwards (the ring wraps and
     continues across forwards), whether offload is switched on before the first forward or after it (layers already repacked:
     their code tensors are converted back to nibbles for the link), with two or three slots.  After every block load the slot's
-    parameters are compared with the host image bit for bit; after set_offload(False) the model runs resident again."""
-    from nunchaku_amd import layout, mode
+    parameters are compared with the host image bit for bit; after set_offload(False) the model runs resident again.
+
+    Ranks 48 .. 160 keep MFMA-fragment images of the low-rank factors per (storage, version) (ABI 21, ``_C._packed_fragments``): every
+    block load into a slot must re-pack them (a stale image runs the low-rank branch with the previous tenant's weights), the slot's
+    cache entries are replaced rather than added, and a resident block's images are packed once.  The kernels read those images only
+    with fp32 low-rank accumulators, whose run-to-run noise hides a stale image in the model's output, so before every load the images
+    the cache would serve for the slot's outgoing tenant are compared with a fresh pack of the slot's weights.  Rank 32 uses no images:
+    the control."""
+    from nunchaku_amd import _C, layout, mode
     from nunchaku_amd.models.linear import SVDQW4A4Linear
+    from tests.helpers import served_fragment_images
 
     g = torch.Generator(device="cuda").manual_seed(9)
     lat = torch.randn(1, 256, 64, device="cuda", generator=g).bfloat16()
@@ -197,10 +223,10 @@ def test_qwen_model_offload_equals_resident(late, num_slots):
     t = torch.tensor([0.6], device="cuda")
     n_blocks, nb = 6, 2
     with torch.no_grad(), mode.deterministic_mode():
-        resident = _small_model(n_blocks)
+        resident = _small_model(n_blocks, rank)
         ref = resident(lat, enc, None, t, [(1, 16, 16)]).sample.clone()
         assert torch.equal(resident(lat, enc, None, t, [(1, 16, 16)]).sample, ref), "deterministic mode: resident forwards differ"
-        model = resident if late else _small_model(n_blocks)  # same seed: same weights
+        model = resident if late else _small_model(n_blocks, rank)  # same seed: same weights
         model.set_offload(True, num_blocks_on_gpu=nb, use_pin_memory=True, num_slots=num_slots)
         mgr = model.offload_manager
         assert len(mgr.buffer_blocks) == num_slots and mgr.n_offloaded == n_blocks - nb
@@ -215,9 +241,13 @@ def test_qwen_model_offload_equals_resident(late, num_slots):
 
         # every load: the slot's parameters equal the host block's (code tensors: after re-expansion) bit for bit
         checked = []
+        served = []  # (outgoing tenant, fragment images checked, parameters whose image is stale) before every load into a slot
         orig_load = mgr.load_block
 
         def checking_load(block_idx, non_blocking=True, slot=None):
+            sl = mgr._slots[slot if slot is not None else (mgr._seq + block_idx - nb) % mgr.num_slots]
+            if sl.tenant >= 0:  # its compute has been issued: what the cache serves for the slot must be the outgoing tenant's factors
+                served.append((sl.tenant, *served_fragment_images(sl.module)))
             orig_load(block_idx, non_blocking, slot)
             if block_idx < nb or block_idx >= n_blocks:
                 return
@@ -236,7 +266,11 @@ def test_qwen_model_offload_equals_resident(late, num_slots):
             checked.append(block_idx)
 
         mgr.load_block = checking_load
-        got = [model(lat, enc, None, t, [(1, 16, 16)]).sample.clone() for _ in range(3)]
+        got, slot_entries, resident_images = [], [], []
+        for _ in range(3):
+            got.append(model(lat, enc, None, t, [(1, 16, 16)]).sample.clone())
+            slot_entries.append([len(_C._converted.get(s.flat) or {}) for s in mgr._slots])
+            resident_images.append(_fragment_images(mgr.blocks[:nb]))
         torch.cuda.synchronize()
         mgr.load_block = orig_load
         assert mgr.forward_counter == 3 and mgr.current_block_idx == 0
@@ -244,8 +278,21 @@ def test_qwen_model_offload_equals_resident(late, num_slots):
         for k, a in enumerate(got):
             assert torch.equal(a, ref), f"offloaded forward {k} (late={late}, slots={num_slots}) differs from the resident model: rel " \
                                         f"{((a.float() - ref.float()).norm() / ref.float().norm()).item():.3e}"
+        # the fragment cache: a slot's entries are replaced by every new tenant, never added (bounded memory); resident blocks pack once
+        assert slot_entries[0] == slot_entries[1] == slot_entries[2], f"cache entries per slot storage grew across forwards: {slot_entries}"
+        stale = [(tenant, names) for tenant, _, names in served if names]
+        assert not stale, f"rank {rank}: the cache served fragment images of another block's low-rank factors (tenant, parameters): {stale[:2]}"
+        if rank == 32:
+            assert not any(slot_entries[0]) and not resident_images[0], "rank 32 keeps no fragment images"
+            assert not any(n for _, n, _ in served)
+        else:
+            assert all(slot_entries[0]) and resident_images[0], (slot_entries[0], len(resident_images[0]))
+            assert len(served) >= 2 * (n_blocks - nb) and all(n for _, n, _ in served), [n for _, n, _ in served]
+        for imgs in resident_images[1:]:
+            assert imgs.keys() == resident_images[0].keys() and all(imgs[k] is v for k, v in resident_images[0].items()), \
+                "a resident block's fragment images must be packed once and reused"
         # a host block is still a loadable module: its state dict is the checkpoint-layout state dict of the resident twin
-        twin = _small_model(n_blocks)
+        twin = _small_model(n_blocks, rank)
         sd_host = mgr.blocks[nb].state_dict()
         sd_twin = twin.transformer_blocks[nb].state_dict()
         assert set(sd_host) == set(sd_twin)
