@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define SVDQ_ABI_VERSION 23
+#define SVDQ_ABI_VERSION 24
 
 /* model dtype of the 16-bit tensors */
 enum { SVDQ_BF16 = 0, SVDQ_FP16 = 1 };
@@ -424,6 +424,44 @@ typedef struct svdq_residual_args {
 } svdq_residual_args;
 
 int svdq_residual_gate_stats(const svdq_residual_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Residual difference (ABI 24; the decision pass of First-Block Cache.  reference: nunchaku/caching/utils_v2.py:133,176
+ * `hidden - original`, fbcache.py:275-277 `(t1 - t2).abs().mean() / t1.abs().mean()`, 16-bit torch ops):
+ *   r[m, c] = base ? round16(cur[m, c] - base[m, c]) : cur[m, c];        out_res[m, c] = r[m, c]   (if out_res)
+ *   sum_diff = sum |round16(prev[m, c] - r[m, c])|;   sum_prev = sum |prev[m, c]|                   (if prev)
+ * over rows [0, M) of [M, C] 16-bit tensors with the common row stride ld.  base == NULL compares an existing residual
+ * (out_res must be NULL then); prev == NULL is the subtraction alone.  out_res may alias cur or base.
+ * The sums are fp32 and bit-identical from launch to launch (no floating-point atomics): per-row sums go to `partials`, a second
+ * kernel behind the first on the same stream adds them in a fixed order and fills `result`.  A term passes through at most
+ * 8 * ceil(C / 512) + 6 + ceil(rows / 256) + 8 additions (rows = M + M2).  C as for svdq_residual_gate_stats.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct svdq_residual_diff_result {
+    float sum_diff, sum_prev;   /* fp32 sums over both problems */
+    float mean_diff, mean_prev; /* round16(sum * (1 / (rows * C))): torch's 16-bit mean, widened to fp32 */
+    float ratio;                /* round16(mean_diff / mean_prev): the 16-bit quotient the reference compares with its threshold */
+    int32_t rows;               /* M + M2 */
+    int32_t reserved[2];
+} svdq_residual_diff_result;
+
+typedef struct svdq_residual_diff_args {
+    const void *cur;   /* [M, C] 16-bit, row stride ld */
+    const void *base;  /* [M, C] or NULL (r = cur) */
+    const void *prev;  /* [M, C] or NULL (no sums) */
+    void *out_res;     /* [M, C] or NULL */
+    /* Grouped launch (optional, cur2 != NULL): a second problem of the same width and row stride (M2 rows) whose terms go
+     * into the SAME two sums -- the real text rows and the real image rows of a joint sequence [text | pad | image | pad].
+     * base2 / prev2 / out_res2 must mirror base / prev / out_res in being given or NULL. */
+    const void *cur2, *base2, *prev2;
+    void *out_res2;
+    float *partials;                   /* [M + M2, 2] fp32 scratch; required with prev */
+    svdq_residual_diff_result *result; /* DEVICE record; required with prev */
+    int32_t M, M2, C, ld;
+    int32_t dtype;
+    int32_t reserved;
+} svdq_residual_diff_args;
+
+int svdq_residual_diff(const svdq_residual_diff_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * AWQ W4A16 GEMV (reference: ops.gemv_awq, nunchaku/csrc/ops.h:123-145 -> src/kernels/awq/gemv_awq.cu:100-286;

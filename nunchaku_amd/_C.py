@@ -660,6 +660,46 @@ class _Ops:
         _lib.check(lib.svdq_residual_gate_stats(C.byref(args), _stream()), "residual_gate_stats")
 
     @staticmethod
+    def residual_diff(cur, base=None, prev=None, out_res=None, partials=None, result=None, second=None):
+        """Extension (ABI 24, First-Block Cache): ``r = cur - base`` (``base`` None: ``r = cur``) written to ``out_res`` and, with
+        ``prev``, the fp32 sums of ``|prev - r|`` and ``|prev|`` (16-bit torch-op rounding) reduced in a fixed order into the device
+        record ``result`` (8 x 4 bytes: sum_diff, sum_prev, mean_diff, mean_prev, ratio, rows, -, -).  2-D row-major views with a common
+        row stride; ``second`` = ``(cur, base, prev, out_res)`` of a second problem whose terms go into the same sums;
+        ``partials``: float32 scratch of 2 x (all rows)."""
+        lib = _lib.load()
+        if cur.dim() != 2 or cur.stride(1) != 1 or cur.dtype not in _DT:
+            raise ValueError("residual_diff: cur must be a 2-D 16-bit view with unit column stride")
+        M, Cc = cur.shape
+        rows = M + (second[0].shape[0] if second is not None else 0)
+
+        def same(t, ref, name):
+            if t is not None and (tuple(t.shape) != tuple(ref.shape) or t.stride() != ref.stride() or t.dtype != ref.dtype):
+                raise ValueError(f"residual_diff: {name} must match cur in shape, strides and dtype")
+
+        for name, t in (("base", base), ("prev", prev), ("out_res", out_res)):
+            same(t, cur, name)
+        if partials is not None and (partials.dtype != torch.float32 or partials.numel() < 2 * rows or not partials.is_contiguous()):
+            raise ValueError("residual_diff: partials must be contiguous float32 with 2 elements per row")
+        if result is not None and (result.numel() * result.element_size() < C.sizeof(_lib.ResidualDiffResult) or not result.is_contiguous()):
+            raise ValueError("residual_diff: result must be a contiguous buffer of at least 32 bytes")
+        tensors = [cur, base, prev, out_res, partials, result] + (list(second) if second is not None else [])
+        for t in tensors:
+            if t is not None and not t.is_cuda:
+                raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
+        dp = lambda t: None if t is None else t.data_ptr()
+        args = _lib.ResidualDiffArgs()
+        args.cur, args.base, args.prev, args.out_res, args.partials, args.result = dp(cur), dp(base), dp(prev), dp(out_res), dp(partials), dp(result)
+        args.M, args.C, args.ld, args.dtype = M, Cc, cur.stride(0), _DT[cur.dtype]
+        if second is not None:
+            c2, b2, p2, o2 = second
+            if c2.dim() != 2 or c2.shape[1] != Cc or c2.stride() != cur.stride() or c2.dtype != cur.dtype:
+                raise ValueError("residual_diff: the second problem must have the width, row stride and dtype of the first")
+            for name, t in (("base", b2), ("prev", p2), ("out_res", o2)):
+                same(t, c2, "second problem: " + name)
+            args.cur2, args.base2, args.prev2, args.out_res2, args.M2 = dp(c2), dp(b2), dp(p2), dp(o2), c2.shape[0]
+        _lib.check(lib.svdq_residual_diff(C.byref(args), _stream()), "residual_diff")
+
+    @staticmethod
     def gemv_awq(in_feats, kernel, scaling_factors, zeros, m, n, k, group_size, bias=None, out_chunks=1):
         """reference: csrc/ops.h:123-145 -> gemv_awq (src/kernels/awq/gemv_awq.cu:253-286): allocates and returns
         the output, shape ``in_feats.shape[:-1] + (n,)``.  ``kernel`` is the checkpoint's ``qweight`` as stored

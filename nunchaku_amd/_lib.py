@@ -12,7 +12,7 @@ _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "li
 
 SVDQ_BF16, SVDQ_FP16 = 0, 1
 FUSE_NONE, FUSE_SILU, FUSE_GELU_QUANT, FUSE_RMSNORM_ROPE = 0, 1, 2, 3
-ABI_VERSION = 23
+ABI_VERSION = 24
 LORA_ACT_F32, LORA_ACT_Q32, LORA_ACT_Q32_RUNS = 0, 1, 2
 
 
@@ -36,6 +36,22 @@ class ResidualArgs(C.Structure):
         ("eps", C.c_float), ("clamp_fp16", C.c_int32), ("zero_ptr", C.c_void_p), ("zero_bytes", C.c_int64),
         ("res2", C.c_void_p), ("a2", C.c_void_p), ("b2", C.c_void_p), ("gate2", C.c_void_p), ("out2", C.c_void_p),
         ("stats2", C.c_void_p), ("M2", C.c_int32), ("reserved2", C.c_int32),
+    ]
+
+
+class ResidualDiffResult(C.Structure):
+    _fields_ = [
+        ("sum_diff", C.c_float), ("sum_prev", C.c_float), ("mean_diff", C.c_float), ("mean_prev", C.c_float),
+        ("ratio", C.c_float), ("rows", C.c_int32), ("reserved", C.c_int32 * 2),
+    ]
+
+
+class ResidualDiffArgs(C.Structure):
+    _fields_ = [
+        ("cur", C.c_void_p), ("base", C.c_void_p), ("prev", C.c_void_p), ("out_res", C.c_void_p),
+        ("cur2", C.c_void_p), ("base2", C.c_void_p), ("prev2", C.c_void_p), ("out_res2", C.c_void_p),
+        ("partials", C.c_void_p), ("result", C.c_void_p),
+        ("M", C.c_int32), ("M2", C.c_int32), ("C", C.c_int32), ("ld", C.c_int32), ("dtype", C.c_int32), ("reserved", C.c_int32),
     ]
 
 
@@ -103,6 +119,7 @@ EXPORTS = {
     "svdq_gemm_awq": (C.c_int, [C.POINTER(GemmAwqArgs), C.c_void_p]),
     "svdq_gemm_awq_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "svdq_residual_gate_stats": (C.c_int, [C.POINTER(ResidualArgs), C.c_void_p]),
+    "svdq_residual_diff": (C.c_int, [C.POINTER(ResidualDiffArgs), C.c_void_p]),
     "svdq_gemm_workspace_bytes": (C.c_int64, []),
     "svdq_gemm_workspace_bytes_for": (C.c_int64, [C.POINTER(GemmArgs)]),
     "svdq_gemm_workspace_status": (C.c_int, [C.c_void_p, C.c_void_p]),

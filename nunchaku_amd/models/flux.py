@@ -23,7 +23,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..ops.attention import attention_packed, attention_packed_quantized, kv_valid_ranges, q_prescale
-from ..ops.elementwise import residual_gate_stats, residual_gate_stats_pair
+from ..ops.elementwise import residual_add_pair, residual_diff, residual_gate_stats, residual_gate_stats_pair
 from ..ops.gemv import awq_gemv_w4a16_batched
 from ..ops.fused import (fused_gelu_mlp, fused_gelu_mlp_pair, fused_qkv_norm_rottary, fused_qkv_norm_rottary_pair,
                          linear_pair, linear_pair_quantized, quantize_two)
@@ -253,8 +253,10 @@ class FluxJointBlockAMD(nn.Module):
         # already carries the +1 of the scale
         return F.layer_norm(x, (x.shape[-1],), eps=1e-6) * scale[:, None] + shift[:, None]
 
-    def forward(self, hidden, encoder_hidden, temb_act, rotary, stats=None, mods=None, kv_valid=None):
+    def forward(self, hidden, encoder_hidden, temb_act, rotary, stats=None, mods=None, kv_valid=None, keep_input=False):
         """``mods`` = (mod, mod_context) outputs computed ahead of the block (one batched GEMV launch per step).
+        ``keep_input``: the fused path leaves ``hidden`` / ``encoder_hidden`` as they are (its first residual pass writes new tensors
+        instead of updating the streams in place; same launches) -- First-Block Cache needs a block's input after the block.
         ``stats`` = (image-stream, text-stream) LayerNorm statistics of the inputs: the fused path -- LayerNorm and
         modulation inside the quantisers, gated residual + next statistics in one element-wise pass (B == 1).
         Returns (encoder_hidden, hidden, stats)."""
@@ -288,17 +290,17 @@ class FluxJointBlockAMD(nn.Module):
         if self.attn.grouped and encoder_hidden.shape[1] % 256 == 0:
             # grouped launches: the text stream's pool carries the scratch of BOTH streams (its rows come first)
             encoder_hidden, e_stats, hidden, h_stats, e_pool = residual_gate_stats_pair(
-                encoder_hidden, ca, c_gate_msa, hidden, a, gate_msa, zero_floats=(mp_e + mp_h) * r_mlp)
+                encoder_hidden, ca, c_gate_msa, hidden, a, gate_msa, zero_floats=(mp_e + mp_h) * r_mlp, inplace=not keep_input)
             ffc, ff = fused_gelu_mlp_pair(encoder_hidden, self.ff_context.fc1, self.ff_context.fc2, hidden, self.ff.fc1, self.ff.fc2,
                                           ln_a=(e_stats, c_scale_mlp, c_shift_mlp, e_pool), ln_b=(h_stats, scale_mlp, shift_mlp))
             encoder_hidden, e_stats, hidden, h_stats, e_pool = residual_gate_stats_pair(
                 encoder_hidden, ffc, c_gate_mlp, hidden, ff, gate_mlp, zero_floats=(mp_e + mp_h) * (self.attn.to_qkv.rank + self.attn.out_proj.rank),
                 clamp_fp16_a=True)  # the reference clips the text stream at the end of an fp16 joint block
             return encoder_hidden, hidden, ((h_stats, None), (e_stats, e_pool))
-        hidden, h_stats, h_pool = residual_gate_stats(hidden, a, gate_msa, zero_floats=mp_h * r_mlp)
+        hidden, h_stats, h_pool = residual_gate_stats(hidden, a, gate_msa, zero_floats=mp_h * r_mlp, inplace=not keep_input)
         hidden, h_stats, h_pool = residual_gate_stats(hidden, self.ff(hidden, ln=(h_stats, scale_mlp, shift_mlp, h_pool)), gate_mlp,
                                                       zero_floats=mp_h * self.attn.to_qkv.rank)  # next block's QKV quantiser
-        encoder_hidden, e_stats, e_pool = residual_gate_stats(encoder_hidden, ca, c_gate_msa, zero_floats=mp_e * r_mlp_c)
+        encoder_hidden, e_stats, e_pool = residual_gate_stats(encoder_hidden, ca, c_gate_msa, zero_floats=mp_e * r_mlp_c, inplace=not keep_input)
         encoder_hidden, e_stats, e_pool = residual_gate_stats(
             encoder_hidden, self.ff_context(encoder_hidden, ln=(e_stats, c_scale_mlp, c_shift_mlp, e_pool)), c_gate_mlp,
             zero_floats=mp_e * self.attn.add_qkv_proj.rank, clamp_fp16=True)
@@ -321,7 +323,8 @@ class FluxSingleBlockAMD(nn.Module):
     def mod(self) -> AWQW4A16Linear:
         return self.norm.linear
 
-    def forward(self, hidden, temb_act, rotary, stats=None, mods=None, kv_valid=None):
+    def forward(self, hidden, temb_act, rotary, stats=None, mods=None, kv_valid=None, keep_input=False):
+        """``keep_input``: the fused path writes its result to a new tensor instead of updating ``hidden`` in place (same launch)."""
         if stats is None:
             shift, scale, gate = self.mod(temb_act).view(temb_act.shape[0], 3, -1).permute(1, 0, 2)
             n = F.layer_norm(hidden, (hidden.shape[-1],), eps=1e-6) * scale[:, None] + shift[:, None]
@@ -340,7 +343,7 @@ class FluxSingleBlockAMD(nn.Module):
         att = self.attn(hidden, rotary=rotary, ln=ln, quantized=q_qkv, kv_valid=kv_valid)
         # hidden + gate * (att + mlp), the next block's statistics and its three low-rank accumulators, one pass
         hidden, st, pool = residual_gate_stats(hidden, att, gate, b=mlp, zero_floats=_pad256(hidden.shape[1]) * (
-            self.mlp_fc1.rank + self.mlp_fc2.rank + self.attn.to_qkv.rank + self.attn.out_proj.rank), clamp_fp16=True)
+            self.mlp_fc1.rank + self.mlp_fc2.rank + self.attn.to_qkv.rank + self.attn.out_proj.rank), clamp_fp16=True, inplace=not keep_input)
         return hidden, (st, pool)
 
 
@@ -495,8 +498,9 @@ class FluxEngineMixin:
         (transformer_flux_v2.py:430-561; batch 1 -- the fused QKV epilogue takes one rotary table).
         ``controlnet_block_samples`` / ``controlnet_single_block_samples``: lists of ``[1, T_img, dim]`` residuals added to the image
         stream behind the joint / single blocks with diffusers' indexing (``FluxTransformer2DModel.forward``: sample
-        ``i // ceil(blocks / samples)``, or ``i % samples`` with ``controlnet_blocks_repeat``)."""
-        dt = self.dtype_
+        ``i // ceil(blocks / samples)``, or ``i % samples`` with ``controlnet_blocks_repeat``).
+        The step is its stages run back to back (``_prologue``, ``_run_joint``, ``_join``, ``_run_single``, ``_tail``);
+        :meth:`engine_forward_cached` is the same stages with the First-Block-Cache decision in between."""
         if hidden_states.shape[0] > 1:
             # The fused QKV epilogue takes ONE rotary table and the operand buffers of a launch belong to one sample
             # (reference: rotary_emb.shape[0] * shape[1] == M assert, launch_impl.cuh:353; SURVEY.md section 8e): a batch
@@ -509,6 +513,19 @@ class FluxEngineMixin:
                                            per(timestep, i), img_ids, txt_ids, per(guidance, i), per_list(controlnet_block_samples, i),
                                            per_list(controlnet_single_block_samples, i), controlnet_blocks_repeat)
                               for i in range(hidden_states.shape[0])], dim=0)
+        st = self._prologue(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance,
+                            controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat)
+        # every modulation projection depends on the timestep embedding only: one batched GEMV launch for the whole step
+        self._launch_mods(st, range(len(self.blocks)), range(len(self.single_blocks)))
+        self._run_joint(st, 0, len(self.blocks))
+        self._join(st)
+        self._run_single(st, 0, len(self.single_blocks))
+        return self._tail(st)
+
+    def _prologue(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance=None,
+                  controlnet_block_samples=None, controlnet_single_block_samples=None, controlnet_blocks_repeat=False) -> "_Step":
+        """Embedders, rotary tables, padding of the two streams and their first LayerNorm statistics."""
+        dt = self.dtype_
         hidden = self.x_embedder(hidden_states)
         # diffusers casts timestep / guidance to the model dtype BEFORE the x1000 (transformer_flux.py: timestep.to(dtype) * 1000)
         temb = self.time_embed(timestep_embedding(timestep.to(dt) * 1000).to(dt))
@@ -554,42 +571,191 @@ class FluxEngineMixin:
         else:
             p_txt = t_txt
 
-        fused = self.fused_norm and hidden.shape[0] == 1
-        stats = ((residual_gate_stats(hidden)[1], None), (residual_gate_stats(enc)[1], None)) if fused else None
-        # every modulation projection depends on the timestep embedding only: one batched GEMV launch for the whole step
-        mods = awq_gemv_w4a16_batched(temb_act, [m for b in self.blocks for m in (b.mod, b.mod_context)] +
-                                      [b.mod for b in self.single_blocks]) if fused and self.batched_mods else None
+        st = _Step()
+        st.hidden, st.enc, st.temb_act, st.rot, st.kv_valid = hidden, enc, temb_act, (rot_img, rot_txt, rot_all), kv_valid
+        st.t_txt, st.t_img, st.p_txt, st.joined, st.mods = t_txt, t_img, p_txt, False, {}
+        st.cn_joint, st.cn_single, st.cn_repeat = controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat
+        st.fused = self.fused_norm and hidden.shape[0] == 1
+        st.stats = ((residual_gate_stats(hidden)[1], None), (residual_gate_stats(enc)[1], None)) if st.fused else None
+        return st
+
+    def _launch_mods(self, st: "_Step", joint, single) -> None:
+        """The modulation projections of the joint blocks ``joint`` and the single blocks ``single`` (index ranges) in one batched GEMV
+        launch; a block whose projections were not launched here runs its own."""
+        if not (st.fused and self.batched_mods):
+            return
+        lins = [m for i in joint for m in (self.blocks[i].mod, self.blocks[i].mod_context)] + [self.single_blocks[i].mod for i in single]
+        if not lins:
+            return
+        outs = awq_gemv_w4a16_batched(st.temb_act, lins)
+        for k, i in enumerate(joint):
+            st.mods["j", i] = (outs[2 * k], outs[2 * k + 1])
+        for k, i in enumerate(single):
+            st.mods["s", i] = outs[2 * len(joint) + k]
+
+    @staticmethod
+    def _control(st: "_Step", samples, i, n_blocks):
+        """diffusers' choice of the ControlNet residual behind block i, as a [1, rows of the (padded) stream, dim] tensor"""
+        n = len(samples)
+        smp = samples[i % n] if st.cn_repeat else samples[i // -(-n_blocks // n)]
+        rows = st.hidden.shape[1]
+        return F.pad(smp.to(st.hidden.dtype), (0, 0, 0, rows - smp.shape[1])) if smp.shape[1] != rows else smp.to(st.hidden.dtype)
+
+    def _run_joint(self, st: "_Step", lo: int, hi: int, keep_input: bool = False) -> None:
+        """Joint blocks ``lo .. hi - 1``.  ``keep_input``: block ``lo`` leaves its two input tensors as they are (the fused path updates the
+        streams in place otherwise)."""
         nj = len(self.blocks)
-
-        def control(samples, i, n_blocks):
-            """diffusers' choice of the ControlNet residual behind block i, as a [1, rows of the (padded) image stream, dim] tensor"""
-            n = len(samples)
-            smp = samples[i % n] if controlnet_blocks_repeat else samples[i // -(-n_blocks // n)]
-            return F.pad(smp.to(hidden.dtype), (0, 0, 0, hidden.shape[1] - smp.shape[1])) if smp.shape[1] != hidden.shape[1] else smp.to(hidden.dtype)
-
-        for i, blk in enumerate(self.blocks):
-            enc, hidden, stats = blk(hidden, enc, temb_act, (rot_img, rot_txt, rot_all), stats,
-                                     mods=(mods[2 * i], mods[2 * i + 1]) if mods is not None else None, kv_valid=kv_valid)
-            if controlnet_block_samples is not None:
+        for i in range(lo, hi):
+            st.enc, st.hidden, st.stats = self.blocks[i](st.hidden, st.enc, st.temb_act, st.rot, st.stats, mods=st.mods.get(("j", i)),
+                                                         kv_valid=st.kv_valid, keep_input=keep_input and i == lo)
+            if st.cn_joint is not None:
                 # hidden_states + sample (one 16-bit add); the fused path needs the LayerNorm statistics of the sum: the same pass
-                hidden, h_stats = residual_gate_stats(hidden, control(controlnet_block_samples, i, nj), want_stats=fused)
-                if fused:
-                    stats = ((h_stats, stats[0][1]), stats[1])
-        t_pad = enc.shape[1]
-        hidden = torch.cat([enc, hidden], dim=1)
-        stats = (torch.cat([stats[1][0], stats[0][0]], dim=0), None) if fused else None  # [txt; img] row order
-        for i, blk in enumerate(self.single_blocks):
-            hidden, stats = blk(hidden, temb_act, rot_all, stats, mods=mods[2 * nj + i] if mods is not None else None, kv_valid=kv_valid)
-            if controlnet_single_block_samples is not None:
-                img_rows = hidden[:, t_pad:]
-                smp = control(controlnet_single_block_samples, i, len(self.single_blocks))
-                _, i_stats = residual_gate_stats(img_rows, F.pad(smp, (0, 0, 0, img_rows.shape[1] - smp.shape[1])), want_stats=fused)
-                if fused:
-                    stats[0][t_pad:] = i_stats
-        hidden = hidden[:, p_txt:p_txt + t_img]
-        scale, shift = self.norm_out_mod(temb_act).chunk(2, dim=-1)  # AdaLayerNormContinuous
+                st.hidden, h_stats = residual_gate_stats(st.hidden, self._control(st, st.cn_joint, i, nj), want_stats=st.fused)
+                if st.fused:
+                    st.stats = ((h_stats, st.stats[0][1]), st.stats[1])
+
+    def _join(self, st: "_Step") -> None:
+        """[text | image] for the single blocks; the statistics in the same row order."""
+        st.hidden = torch.cat([st.enc, st.hidden], dim=1)
+        st.stats = (torch.cat([st.stats[1][0], st.stats[0][0]], dim=0), None) if st.fused else None  # [txt; img] row order
+        st.joined = True
+
+    def _run_single(self, st: "_Step", lo: int, hi: int, keep_input: bool = False) -> None:
+        """Single blocks ``lo .. hi - 1`` on the joined stream; ``keep_input`` as in :meth:`_run_joint`."""
+        ns, t_pad = len(self.single_blocks), st.p_txt
+        for i in range(lo, hi):
+            st.hidden, st.stats = self.single_blocks[i](st.hidden, st.temb_act, st.rot[2], st.stats, mods=st.mods.get(("s", i)),
+                                                        kv_valid=st.kv_valid, keep_input=keep_input and i == lo)
+            if st.cn_single is not None:
+                img_rows = st.hidden[:, t_pad:]
+                smp = self._control(st, st.cn_single, i, ns)
+                _, i_stats = residual_gate_stats(img_rows, F.pad(smp, (0, 0, 0, img_rows.shape[1] - smp.shape[1])), want_stats=st.fused)
+                if st.fused:
+                    st.stats[0][t_pad:] = i_stats
+
+    def _tail(self, st: "_Step") -> torch.Tensor:
+        """The real image rows through AdaLayerNormContinuous and the output projection."""
+        off = st.p_txt if st.joined else 0
+        hidden = st.hidden[:, off:off + st.t_img]
+        scale, shift = self.norm_out_mod(st.temb_act).chunk(2, dim=-1)  # AdaLayerNormContinuous
         hidden = F.layer_norm(hidden, (self.dim,), eps=1e-6) * (1 + scale[:, None]) + shift[:, None]
         return self.proj_out(hidden)
+
+    def _first_residual(self, name: str, curs, bases) -> torch.Tensor:
+        """What the first block did to the real rows ``curs`` (one or two row ranges; ``bases``: the same rows before the block) as one
+        ``[1, rows, dim]`` tensor -- and, in the same launch, its distance to the stored first residual ``name`` (handed to
+        ``fbcache.are_two_tensors_similar`` with the tensor)."""
+        from ..caching import fbcache
+
+        prev = fbcache.get_buffer(name)
+        out = torch.empty(1, sum(c.shape[0] for c in curs), self.dim, dtype=curs[0].dtype, device=curs[0].device)
+        edges = [0]
+        for c in curs:
+            edges.append(edges[-1] + c.shape[0])
+        cut = lambda t: [t[0, a:b] for a, b in zip(edges[:-1], edges[1:])]
+        usable = prev is not None and prev.shape == out.shape and prev.dtype == out.dtype and prev.device == out.device and prev.is_contiguous()
+        _, record = residual_diff(list(curs), list(bases), cut(prev) if usable else None, cut(out))
+        return fbcache.attach_comparison(out, prev, record) if usable else out
+
+    def engine_forward_cached(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance=None,
+                              controlnet_block_samples=None, controlnet_single_block_samples=None, *, use_double_fb_cache: bool = False,
+                              residual_diff_threshold_multi: float = 0.12, residual_diff_threshold_single: float = -1.0,
+                              verbose: bool = False):
+        """One denoising step with First-Block Cache (reference: caching/utils_v2.py ``cached_forward_v2``): the stages of
+        :meth:`engine_forward` with the decision of ``caching.fbcache.check_and_apply_cache`` in between.
+
+        Behind joint block 0 the change it made to the real image rows is compared with the one of the last computed step
+        (``svdq_residual_diff``: subtraction and comparison in one pass).  Hit: the other blocks are skipped and the stored residuals of
+        the image and the text stream are added (one grouped ``svdq_residual_gate_stats`` pass); only block 0's modulation projections were
+        launched.  Miss: the other blocks run and their summed effect is stored.  ``use_double_fb_cache``: the miss / hit above covers the
+        joint blocks only and a second decision is taken behind single block 0 on the real rows of ``[text | image]``.
+
+        Needs an active ``fbcache.cache_context``.  The decision is read on the host, which synchronises the stream.  Refused with an
+        error: a stream under capture (``graph.CapturedStep``), batch > 1 (the uncached forward loops over the samples; one cache context
+        holds one sample's residuals) and ControlNet residuals (the reference's cached forward drops them silently)."""
+        from ..caching import fbcache
+
+        if hidden_states.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("First-Block Cache reads its decision on the host, which synchronises the stream: a cached forward cannot be "
+                               "captured into a graph (run the uncached forward under capture: residual_diff_threshold_multi < 0)")
+        if hidden_states.shape[0] != 1:
+            raise ValueError(f"First-Block Cache supports batch 1 only (got {hidden_states.shape[0]}): run the samples one by one, each in "
+                             "its own cache context")
+        if controlnet_block_samples is not None or controlnet_single_block_samples is not None:
+            raise ValueError("First-Block Cache does not support ControlNet residuals: the skipped blocks' residuals would be dropped")
+        assert fbcache.get_current_cache_context() is not None, "cache_context must be set before"
+        nj, ns = len(self.blocks), len(self.single_blocks)
+        if nj == 0:
+            raise ValueError("First-Block Cache needs at least one joint block")
+        double = bool(use_double_fb_cache) and ns > 0
+
+        st = self._prologue(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance)
+        t_txt, t_img, p_txt = st.t_txt, st.t_img, st.p_txt
+        self._launch_mods(st, range(0, 1), range(0, 1) if double else range(0))  # of the blocks that run whatever the decision
+        h0 = st.hidden
+        self._run_joint(st, 0, 1, keep_input=True)
+        first = self._first_residual("first_multi_hidden_states_residual", [st.hidden[0, :t_img]], [h0[0, :t_img]])
+        del h0
+
+        def apply_residual(hidden_states, encoder_hidden_states, mode):
+            """a hit: the stored residuals are added in place; in double mode the same pass delivers single block 0's LayerNorm statistics"""
+            if mode == "multi":
+                h_res, e_res = fbcache.get_buffer("multi_hidden_states_residual"), fbcache.get_buffer("multi_encoder_hidden_states_residual")
+                assert h_res is not None, "multi_hidden_states_residual must be set before"
+                assert e_res is not None, "multi_encoder_hidden_states_residual must be set before"
+                h_stats, e_stats = residual_add_pair(hidden_states, h_res, encoder_hidden_states, e_res, want_stats=double and st.fused)
+                if double and st.fused:
+                    st.stats = ((h_stats, None), (e_stats, None))
+                return hidden_states, encoder_hidden_states
+            res = fbcache.get_buffer("single_hidden_states_residual")
+            assert res is not None, "single_hidden_states_residual must be set before"
+            return residual_gate_stats(hidden_states, res, want_stats=False)[0]
+
+        def remaining_multi(hidden_states, encoder_hidden_states):
+            """a miss: the other joint blocks (and, with one decision per step, all single blocks); block 0's outputs survive for the residuals"""
+            self._launch_mods(st, range(1, nj), range(0) if double else range(ns))
+            self._run_joint(st, 1, nj, keep_input=True)
+            if double:
+                cur_e, cur_h = st.enc, st.hidden
+            else:
+                self._join(st)  # a new tensor: the single blocks update it in place
+                self._run_single(st, 0, ns)
+                cur_e, cur_h = st.hidden[:, :p_txt], st.hidden[:, p_txt:]
+            (e_res, h_res), _ = residual_diff([cur_e[0], cur_h[0]], [encoder_hidden_states[0], hidden_states[0]])
+            return cur_h, cur_e, h_res.unsqueeze(0), e_res.unsqueeze(0)
+
+        st.hidden, st.enc, _ = fbcache.check_and_apply_cache(
+            first_residual=first, hidden_states=st.hidden, encoder_hidden_states=st.enc, threshold=residual_diff_threshold_multi,
+            parallelized=False, mode="multi", verbose=verbose, call_remaining_fn=remaining_multi, remaining_kwargs={},
+            apply_residual_fn=apply_residual)
+        st.joined = False  # (after a miss with one decision per step the two streams are views of the joined tensor)
+        if double:
+            self._join(st)
+            s0 = st.hidden
+            self._run_single(st, 0, 1, keep_input=True)
+            real = lambda t: [t[0, :t_txt], t[0, p_txt:p_txt + t_img]]  # the padding rows take no part in the decision
+            first = self._first_residual("first_single_hidden_states_residual", real(st.hidden), real(s0))
+            del s0
+
+            def remaining_single(hidden_states, encoder_hidden_states):
+                self._launch_mods(st, range(0), range(1, ns))
+                self._run_single(st, 1, ns, keep_input=True)
+                res, _ = residual_diff(st.hidden[0], hidden_states[0])
+                return st.hidden, res.unsqueeze(0)
+
+            st.hidden, _, _ = fbcache.check_and_apply_cache(
+                first_residual=first, hidden_states=st.hidden, encoder_hidden_states=None, threshold=residual_diff_threshold_single,
+                parallelized=False, mode="single", verbose=verbose, call_remaining_fn=remaining_single, remaining_kwargs={},
+                apply_residual_fn=apply_residual)
+        return self._tail(st)
+
+
+class _Step:
+    """What one denoising step carries between the stages of :class:`FluxEngineMixin`: the two streams (``hidden`` is the joined
+    ``[text | image]`` stream once ``joined``), the LayerNorm statistics that travel with them on the fused path, and the step's constants."""
+
+    __slots__ = ("hidden", "enc", "stats", "temb_act", "rot", "kv_valid", "t_txt", "t_img", "p_txt", "fused", "mods", "joined",
+                 "cn_joint", "cn_single", "cn_repeat")
 
 
 class FluxTransformerAMD(nn.Module, FluxEngineMixin):

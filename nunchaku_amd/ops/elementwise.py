@@ -52,18 +52,105 @@ def residual_gate_stats(res: torch.Tensor, a: torch.Tensor | None = None, gate: 
 
 
 def residual_gate_stats_pair(res_a, a_a, gate_a, res_b, a_b, gate_b, zero_floats: int = 0, eps: float = 1e-6, clamp_fp16_a: bool = False,
-                             clamp_fp16_b: bool = False):
+                             clamp_fp16_b: bool = False, inplace: bool = True):
     """Two independent gated residuals (the two streams of a joint block: same width, different row counts) and their
-    statistics in ONE launch, both in place.  Returns ``(y_a, stats_a, y_b, stats_b[, ZeroPool])``."""
+    statistics in ONE launch, both in place (``inplace`` False: into new tensors).  Returns ``(y_a, stats_a, y_b, stats_b[, ZeroPool])``."""
     C = res_a.shape[-1]
     ra, rb = res_a.reshape(-1, C), res_b.reshape(-1, C)
+    oa, ob = (ra, rb) if inplace else (torch.empty_like(ra), torch.empty_like(rb))
     sa = torch.empty(ra.shape[0], 2, dtype=torch.float32, device=res_a.device)
     sb = torch.empty(rb.shape[0], 2, dtype=torch.float32, device=res_a.device)
     zf = zero_floats * lora_act_words()
     zero = torch.empty((zf + 3) // 4 * 4, dtype=torch.float32, device=res_a.device) if zf > 0 else None
-    ops.residual_gate_stats(ra, a_a.reshape(-1, C), None, gate_a.reshape(-1), ra, sa, eps, zero,
-                            second=(rb, a_b.reshape(-1, C), None, gate_b.reshape(-1), rb, sb),
+    ops.residual_gate_stats(ra, a_a.reshape(-1, C), None, gate_a.reshape(-1), oa, sa, eps, zero,
+                            second=(rb, a_b.reshape(-1, C), None, gate_b.reshape(-1), ob, sb),
                             clamp_fp16=int(bool(clamp_fp16_a)) | (2 if clamp_fp16_b else 0))
+    if not inplace:
+        res_a, res_b = oa.view(res_a.shape), ob.view(res_b.shape)
     if zero_floats > 0:
         return res_a, sa, res_b, sb, ZeroPool(zero if zero is not None else torch.empty(0, dtype=torch.float32, device=res_a.device))
     return res_a, sa, res_b, sb
+
+
+def residual_add_pair(res_a, a_a, res_b, a_b, want_stats: bool = False, eps: float = 1e-6):
+    """``res_a += a_a`` and ``res_b += a_b`` (one 16-bit add each, in place) in ONE launch, with the row statistics of both sums when
+    ``want_stats``: a First-Block-Cache hit adds the stored residuals of the two streams this way.  Returns ``(stats_a, stats_b)``."""
+    C = res_a.shape[-1]
+    ra, rb = res_a.reshape(-1, C), res_b.reshape(-1, C)
+    sa = torch.empty(ra.shape[0], 2, dtype=torch.float32, device=res_a.device) if want_stats else None
+    sb = torch.empty(rb.shape[0], 2, dtype=torch.float32, device=res_a.device) if want_stats else None
+    ops.residual_gate_stats(ra, a_a.reshape(-1, C), None, None, ra, sa, eps, None, second=(rb, a_b.reshape(-1, C), None, None, rb, sb))
+    return sa, sb
+
+
+class ResidualDiff:
+    """The device record of a :func:`residual_diff` launch (``svdq_residual_diff_result``).  ``read()`` copies it to the host --
+    that synchronises the stream, so it raises while the stream is being captured -- and keeps the values."""
+
+    FIELDS = ("sum_diff", "sum_prev", "mean_diff", "mean_prev", "ratio")
+
+    def __init__(self, record: torch.Tensor, dtype: torch.dtype):
+        self.record, self.dtype, self._host = record, dtype, None
+
+    def read(self) -> dict:
+        if self._host is None:
+            if self.record.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("residual_diff: the result record is read on the host, which synchronises the stream: "
+                                   "not possible while the stream is being captured into a graph")
+            self._host = dict(zip(self.FIELDS, self.record[:5].tolist()))
+        return self._host
+
+    @property
+    def ratio(self) -> torch.Tensor:
+        """the 16-bit quotient of the two 16-bit means, a 0-dim CPU tensor in the dtype of the compared tensors"""
+        return torch.tensor(self.read()["ratio"], dtype=self.dtype)
+
+    def is_similar(self, threshold: float) -> torch.Tensor:
+        return self.ratio < threshold  # torch's comparison of a 16-bit tensor with a Python number
+
+
+def residual_diff(cur, base=None, prev=None, out=None, want_res: bool | None = None):
+    """``r = cur - base`` (``base`` None: ``r = cur``) and, with ``prev``, the relative L1 distance ``mean|prev - r| / mean|prev|`` with
+    the rounding points of the reference's 16-bit torch ops (caching/fbcache.py:275-277), in one pass over the tensors.
+    Every argument is a ``[..., C]`` tensor or a sequence of up to two of them: two problems (the real text and image rows of a padded
+    joint sequence) feed the same two sums.  Returns ``(r or None, ResidualDiff or None)``; ``r`` is ``out`` when given, else new
+    (a list for two problems); ``want_res`` defaults to "when there is a base"."""
+    def seq(x):
+        return list(x) if isinstance(x, (list, tuple)) else [x]
+
+    curs = seq(cur)
+    n = len(curs)
+    if not 1 <= n <= 2:
+        raise ValueError("residual_diff: one or two problems")
+    bases, prevs, outs = (seq(x) if x is not None else [None] * n for x in (base, prev, out))
+    if not (len(bases) == len(prevs) == len(outs) == n):
+        raise ValueError("residual_diff: base / prev / out must have as many entries as cur")
+    C = curs[0].shape[-1]
+    if want_res is None:
+        want_res = base is not None
+    if want_res and base is None:
+        raise ValueError("residual_diff: without a base the residual is cur itself")
+    if want_res and out is None:
+        outs = [torch.empty(c.shape, dtype=c.dtype, device=c.device) for c in curs]
+    def v(t):
+        if t is not None and not t.is_contiguous():
+            raise ValueError("residual_diff: tensors must be contiguous (row slices of a contiguous tensor are)")
+        return None if t is None else t.view(-1, C)
+
+    probs = [(v(c), v(b), v(p), v(o) if want_res else None) for c, b, p, o in zip(curs, bases, prevs, outs)]
+    for c, b, p, o in probs:
+        for t, s in ((b, c), (p, c), (o, c)):
+            if t is not None and t.shape != s.shape:
+                raise ValueError(f"residual_diff: shapes differ: {tuple(t.shape)} vs {tuple(s.shape)}")
+    rows = sum(p[0].shape[0] for p in probs)
+    rec = None
+    partials = result = None
+    if prev is not None:
+        partials = torch.empty(rows, 2, dtype=torch.float32, device=curs[0].device)
+        result = torch.empty(8, dtype=torch.float32, device=curs[0].device)
+        rec = ResidualDiff(result, curs[0].dtype)
+    ops.residual_diff(*probs[0], partials=partials, result=result, second=probs[1] if n == 2 else None)
+    res = None
+    if want_res:
+        res = outs if isinstance(cur, (list, tuple)) else outs[0]
+    return res, rec
