@@ -247,6 +247,7 @@ __device__ __forceinline__ void finish_rows(const AttnParams &p, const v16f (&o)
             float scale_rounded = scale;
             asm volatile("" : "+v"(scale_rounded));
             sc16[g] = f2h<T>(scale_rounded);
+            // (no nan_to_zero() here, unlike quantize.hip: the converter emits 0x3F, not code 0, for a NaN -- a non-finite attention output is not handled)
             v16f ev, od;
 #pragma unroll
             for (int i = 0; i < 16; i++) {

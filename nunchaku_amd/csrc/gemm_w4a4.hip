@@ -187,6 +187,17 @@ __device__ __forceinline__ float gelu_tanh_f(float x) {
 // reference: gemm_utils.cuh:290-303 (silu = x * rcp.approx(1 + ex2.approx(-x * log2 e))), applied by EpilogueSilu (gemm_base.cuh:783-792).  The same two hardware
 // approximations here (v_exp_f32, v_rcp_f32: 1 ulp each), held to oracle.silu_envelope; rounds 1-5 computed an exact expf and an IEEE divide:
 // 2.5-2.7 k static VALU per wave-tile against ~0.9 k for the default epilogue.
+// EpilogueDefault's fp16 clamp as the reference does it (gemm_base.cuh:692-693): ON the fp16 values, __hmin with 65504 FIRST, then __hmax with -65504; both
+// return the non-NaN operand, so +-inf (an fp32 sum beyond the fp16 range converts to inf) -> +-65504 and NaN -> +65504.  The other order (max first, or one
+// v_med3_f32, which returns min3 for a NaN) stores -65504 for a NaN.  Packed: v_pk_min_f16 + v_pk_max_f16 per PAIR -- the instruction count of the one
+// v_med3_f32 per element this replaces.  Returns the pair as the store's dword (low half = v0).
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned cvt_clamp_pk_fp16(float v0, float v1) {
+    f16x2_t h = {(_Float16)v0, (_Float16)v1};
+    h = __builtin_elementwise_min(h, (f16x2_t){(_Float16)65504.f, (_Float16)65504.f});
+    h = __builtin_elementwise_max(h, (f16x2_t){(_Float16)-65504.f, (_Float16)-65504.f});
+    return __builtin_bit_cast(unsigned, h);
+}
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f)); }
 
 typedef __attribute__((address_space(3))) void lds_void;
@@ -1269,7 +1280,7 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm_w4a4_kernel(const GemmParams 
         }
 
         SVDQ_PROBE_STAMP(4);
-        // EpilogueDefault (gemm_base.cuh:667-698): store rows < M; fp16 clamps to +-65504.
+        // EpilogueDefault (gemm_base.cuh:667-698): store rows < M; fp16 clamps to +-65504 (cvt_clamp_pk_fp16: NaN -> +65504, as the reference).
         // A lane holds 4 consecutive columns per (tile, c); the partner lane (lane ^ 32) holds the next 4.
         // One v_permlane32_swap per dword turns two 8-byte pieces per lane into one 16-byte piece, so a
         // wave store writes 32 contiguous bytes per row with dwordx4 stores (8 instead of 32 per wave).
@@ -1294,8 +1305,9 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm_w4a4_kernel(const GemmParams 
 #pragma unroll
                         for (int r = 0; r < 16; r += 2) {
                             float v0 = acc[ni][mi][r], v1 = acc[ni][mi][r + 1];
-                            if constexpr (DT == SVDQ_FP16) { v0 = fminf(fmaxf(v0, -65504.f), 65504.f); v1 = fminf(fmaxf(v1, -65504.f), 65504.f); }
-                            const unsigned own = (unsigned)hbits(f2h<T>(v0)) | ((unsigned)hbits(f2h<T>(v1)) << 16);
+                            unsigned own;
+                            if constexpr (DT == SVDQ_FP16) own = cvt_clamp_pk_fp16(v0, v1);
+                            else own = (unsigned)hbits(f2h<T>(v0)) | ((unsigned)hbits(f2h<T>(v1)) << 16);
                             const unsigned oth = (unsigned)__builtin_amdgcn_update_dpp(0, (int)own, 0xB1, 0xf, 0xf, true); // lane ^ 1
                             const unsigned val = odd ? ((oth >> 16) | (own & 0xffff0000u)) : ((own & 0xffffu) | (oth << 16));
                             // channel n = nv0 + 32 ni + 8 (r >> 2) + 4 h + (r & 3) + odd: the h / odd part sits in lane_off
@@ -1324,11 +1336,12 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm_w4a4_kernel(const GemmParams 
                         float v0 = acc[ni][mi][(2 * j) * 4 + 2 * d], v1 = acc[ni][mi][(2 * j) * 4 + 2 * d + 1];
                         float w0 = acc[ni][mi][(2 * j + 1) * 4 + 2 * d], w1 = acc[ni][mi][(2 * j + 1) * 4 + 2 * d + 1];
                         if constexpr (DT == SVDQ_FP16) {
-                            v0 = fminf(fmaxf(v0, -65504.f), 65504.f); v1 = fminf(fmaxf(v1, -65504.f), 65504.f);
-                            w0 = fminf(fmaxf(w0, -65504.f), 65504.f); w1 = fminf(fmaxf(w1, -65504.f), 65504.f);
+                            x[d] = cvt_clamp_pk_fp16(v0, v1);
+                            y[d] = cvt_clamp_pk_fp16(w0, w1);
+                        } else {
+                            x[d] = (unsigned)hbits(f2h<T>(v0)) | ((unsigned)hbits(f2h<T>(v1)) << 16);
+                            y[d] = (unsigned)hbits(f2h<T>(w0)) | ((unsigned)hbits(f2h<T>(w1)) << 16);
                         }
-                        x[d] = (unsigned)hbits(f2h<T>(v0)) | ((unsigned)hbits(f2h<T>(v1)) << 16);
-                        y[d] = (unsigned)hbits(f2h<T>(w0)) | ((unsigned)hbits(f2h<T>(w1)) << 16);
                         // x.hi-lanes <-> y.lo-lanes: lo lanes end up with (own x, partner x), hi lanes (partner y, own y)
                         auto sw = __builtin_amdgcn_permlane32_swap(x[d], y[d], false, false);
                         x[d] = sw[0];

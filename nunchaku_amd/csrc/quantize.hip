@@ -218,12 +218,16 @@ __global__ __launch_bounds__(256, OCC) void quantize_kernel(const typename Half<
             // q = rne(x_hat / scale) as FP6 e2m3 = q/8, packed 32 x 6 bits: ONE v_cvt_scalef32_2xpk16_fp6_f32 (scale 8 =
             // divide by 2^3; element 2i from the first source, 2i+1 from the second; RNE; |x_hat/scale| <= 7 by
             // construction so the -8..7 clamp never fires; probed on gfx950 with tools/ubench5.hip) instead of
-            // rint / clamp / sign-magnitude encode / shift / or per element
+            // rint / clamp / sign-magnitude encode / shift / or per element.
+            // NaN: FP6 has no NaN encoding and the converter emits 0x3F for one (sign + largest magnitude, -7.5: measured on an MI355X by
+            // tests/test_gpu_numeric_edges.py before nan_to_zero() -- one v_med3_f32 -- was added; attention.hip's quantiser has no such guard), where the reference's cvt.rni gives code 0 (gemm_w4a4.cuh:483-497).  A NaN
+            // arrives here as a NaN input element (fmaxf above skips it, as __hmax does) or as inf * 0 in a group holding +-inf (scale inf, rscale 0):
+            // both become code 0.
             v16f ev, od;
 #pragma unroll
             for (int i = 0; i < 16; i++) {
-                ev[i] = xh[2 * i] * rscale;
-                od[i] = xh[2 * i + 1] * rscale;
+                ev[i] = nan_to_zero(xh[2 * i] * rscale);
+                od[i] = nan_to_zero(xh[2 * i + 1] * rscale);
             }
             const v6i pk = __builtin_amdgcn_cvt_scalef32_2xpk16_fp6_f32(ev, od, 8.0f);
 #pragma unroll
@@ -529,6 +533,11 @@ __global__ __launch_bounds__(256, MULTI ? 2 : 4) void quantize_kernel_v2(QuantPa
             // q = rne(x_hat / scale) as FP6 e2m3 = q/8, 32 x 6 bits in ONE v_cvt_scalef32_2xpk16_fp6_f32 (see the general kernel)
             ev = ev * rscale;
             od = od * rscale;
+#pragma unroll
+            for (int i = 0; i < 16; i++) { // NaN (a NaN element, or inf * 0 in a group holding inf) -> code 0, see the general kernel
+                ev[i] = nan_to_zero(ev[i]);
+                od[i] = nan_to_zero(od[i]);
+            }
             const v6i pk = __builtin_amdgcn_cvt_scalef32_2xpk16_fp6_f32(ev, od, 8.0f);
             if (grp == 0) {
                 *reinterpret_cast<uint4 *>(dst) = make_uint4((unsigned)pk[0], (unsigned)pk[1], (unsigned)pk[2], (unsigned)pk[3]);

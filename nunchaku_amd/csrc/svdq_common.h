@@ -95,6 +95,10 @@ template <typename T> __device__ __forceinline__ f32x2_t round16_pair(float a, f
 // 2 ulp, i.e. exactly as faithful to the reference as the IEEE quotient (oracle: quantize_envelope; the 16-bit result differs from the IEEE one on
 // ~2^-15 (bf16) / ~2^-12 (fp16) of the elements).  `rs` = __builtin_amdgcn_rcpf(smooth): every kernel of the library forms it the same way, so the
 // stand-alone quantiser, its fast path and the attention / GEMM epilogues that quantise emit identical bits for identical inputs.
+// NaN -> 0, everything else unchanged: what cvt.rni does to a NaN quotient in the reference's quantiser (gemm_w4a4.cuh:483-497, gemm_utils.cuh:209-229)
+// ONE v_med3_f32(v, 0, v): the median of {v, 0, v} is v; with a NaN operand the instruction returns min3, and v_min skips NaN: min3(NaN, 0, NaN) = 0.
+// (fmed3f(v, -7, 7) would give -7 for a NaN, not 0; a compare + select costs two instructions per element.)
+__device__ __forceinline__ float nan_to_zero(float v) { return __builtin_amdgcn_fmed3f(v, 0.f, v); }
 template <typename T> __device__ __forceinline__ float smooth_div16(float x, float rs) { return round16<T>(x * rs); }
 
 // ---- order-independent accumulation format of the low-rank activations ("deterministic mode") -------------------

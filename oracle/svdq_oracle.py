@@ -108,6 +108,22 @@ def ceil_div(a: int, b: int) -> int:
     return (a + b - 1) // b
 
 
+FP16_MAX = 65504.0
+
+
+def clamp16_default(y16: np.ndarray, dtype: str) -> np.ndarray:
+    """The store of GEMM::EpilogueDefault (gemm_base.cuh:689-695), fp16 only:
+        pack[i] = __hmin(pack[i], (half)65504);  pack[i] = __hmax(pack[i], (half)-65504);
+    in THIS order.  __hmin / __hmax return the non-NaN operand when exactly one operand is NaN (CUDA math API, "Half
+    Comparison Functions"), so  NaN -> min(NaN, 65504) = 65504 -> max(65504, -65504) = +65504;  +inf -> +65504;
+    -inf -> -65504; finite values are unchanged.  bf16 (``half_t`` = __nv_bfloat16) takes no clamp at all (:689,
+    ``if constexpr (std::is_same_v<half_t, half>)``): inf and NaN are stored as they are.
+    np.fmin / np.fmax have the same "non-NaN operand" rule."""
+    if dtype != "fp16":
+        return y16
+    return np.fmax(np.fmin(np.asarray(y16, dtype=F32), F32(FP16_MAX)), F32(-FP16_MAX))
+
+
 # --------------------------------------------------------------------------
 # Reference ("on-disk") tensor layouts.  packer.py:187-301,362-437 and the
 # device-side consumers gemm_base.cuh:265-355, lora.cuh:43-59.
@@ -306,12 +322,21 @@ def quantize_rows(xh: np.ndarray, dtype: str, unsigned: bool):
     rcp.approx.ftz is replaced by the IEEE reciprocal 1.0f/scale.  A zero group gives
     scale 0 -> rcp = inf -> 0*inf = NaN -> cvt.rni(NaN) = 0, i.e. code 0.
 
+    Non-finite input (nothing in the reference guards against it; this is what its instructions do):
+      * the maximum is a chain of __hmax starting from 0 (:455-471), and __hmax returns the non-NaN operand:
+        amax IGNORES NaN elements.  (np.fmax, not np.max: the latter propagates NaN.)
+      * a group holding +-inf: amax = inf, scale = inf, stored ascale = inf (:476-480); rcp(inf) = +0 (:486), so
+        finite elements give 0 and the inf element inf * 0 = NaN -> cvt.rni(NaN) = 0 (:496-497, gemm_utils.cuh:209-229):
+        EVERY code of the group is 0.
+      * a NaN element among finite ones: NaN * rcp = NaN -> code 0; amax, scale and the group's other codes are what
+        they would be without it.  An all-NaN group has amax 0: ascale 0, every code 0.
+
     Returns (codes int8 [M, K], ascales float32-valued-16-bit [K/64, M]).
     """
     M, K = xh.shape
     G = K // GROUP
     xg = xh.reshape(M, G, GROUP).astype(F32)
-    amax = np.abs(xg).max(axis=2)  # exact in the 16-bit type
+    amax = np.fmax.reduce(np.abs(xg), axis=2, initial=F32(0))  # exact in the 16-bit type; NaN ignored (__hmax, :455-471)
     recip_q = F32(1.0) / F32(15.0 if unsigned else 7.0)
     scale = (amax.astype(F32) * recip_q).astype(F32)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
@@ -366,12 +391,16 @@ def quantize_rows_envelope(xlo: np.ndarray, xhi: np.ndarray, dtype: str, unsigne
     abs_lo = np.where(straddle, F32(0), np.minimum(np.abs(lo), np.abs(hi)))
     abs_hi = np.maximum(np.abs(lo), np.abs(hi))
     recip_q = F32(1.0) / F32(15.0 if unsigned else 7.0)
-    sc_lo = (abs_lo.max(axis=2).astype(F32) * recip_q).astype(F32)
-    sc_hi = (abs_hi.max(axis=2).astype(F32) * recip_q).astype(F32)
+    # NaN elements are ignored by the maximum (quantize_rows: __hmax); their own codes come out as 0 below (NaN candidates)
+    sc_lo = (np.fmax.reduce(abs_lo, axis=2, initial=F32(0)).astype(F32) * recip_q).astype(F32)
+    sc_hi = (np.fmax.reduce(abs_hi, axis=2, initial=F32(0)).astype(F32) * recip_q).astype(F32)
     qmin, qmax = (0, 15) if unsigned else (-8, 7)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         r_hi = _widen32((F32(1.0) / sc_lo).astype(F32), PTX_APPROX["rcp.approx.ftz.f32"]["max_ulp"])[1]  # largest reciprocal: of the smallest scale
         r_lo = _widen32((F32(1.0) / sc_hi).astype(F32), PTX_APPROX["rcp.approx.ftz.f32"]["max_ulp"])[0]
+        # the reciprocal of an infinite scale is +0 exactly (PTX rcp.approx: rcp(+inf) = +0; v_rcp_f32 alike), not "0 +- 1 ulp"
+        r_hi = np.where(np.isinf(sc_lo), F32(0), r_hi)
+        r_lo = np.where(np.isinf(sc_hi), F32(0), r_lo)
         cands = [(a * r[:, :, None]).astype(F32) for a in (lo, hi) for r in (r_lo, r_hi)]
         v_lo = np.minimum.reduce(cands)
         v_hi = np.maximum.reduce(cands)
@@ -544,6 +573,18 @@ def quantize_w4a4_act_fuse_lora(
 # --------------------------------------------------------------------------
 # GEMM + epilogues
 # --------------------------------------------------------------------------
+def _non_finite_is_data(fn):
+    """inf / NaN operands are ordinary data for the decorated function: overflow and invalid-operation warnings are off inside it"""
+    import functools
+
+    @functools.wraps(fn)
+    def wrapped(*args, **kwargs):
+        with np.errstate(over="ignore", invalid="ignore"):
+            return fn(*args, **kwargs)
+
+    return wrapped
+
+
 def int_group_dot(qa: np.ndarray, qw: np.ndarray) -> np.ndarray:
     """psum[g, m, n] = sum_{k in group g} qa[m, k] * qw[n, k]  (int32)
     gemm_w4a4.cuh:408-426 (mma m16n8k64 s4|u4 x s4 -> s32), :721-735."""
@@ -561,17 +602,19 @@ def gelu_tanh(x: np.ndarray) -> np.ndarray:
     """gemm_utils.cuh:305-312 (gelu_half2): x*(0.5 + 0.5*tanh(0.79788456*(x + 0.044715*x^3)))
     in fp32; tanh.approx replaced by exact tanh."""
     x = x.astype(F32)
-    x3 = (x * x * x).astype(F32)
-    inner = (F32(0.79788456) * (x + F32(0.044715) * x3)).astype(F32)
-    t = (F32(0.5) + F32(0.5) * np.tanh(inner).astype(F32)).astype(F32)
-    return (x * t).astype(F32)
+    with np.errstate(over="ignore", invalid="ignore"):  # non-finite rows are data: NaN / inf flow through
+        x3 = (x * x * x).astype(F32)
+        inner = (F32(0.79788456) * (x + F32(0.044715) * x3)).astype(F32)
+        t = (F32(0.5) + F32(0.5) * np.tanh(inner).astype(F32)).astype(F32)
+        return (x * t).astype(F32)
 
 
 def silu(x: np.ndarray) -> np.ndarray:
     """gemm_base.cuh:783-792, gemm_utils.cuh:280-293,314-319: x*sigmoid(x) in fp32
     (ex2.approx/rcp.approx replaced by exact math)."""
     x = x.astype(np.float64)
-    return (x / (1.0 + np.exp(-x))).astype(F32)
+    with np.errstate(over="ignore", invalid="ignore"):  # exp(+big) = inf -> x / inf = -0; silu(-inf) = -inf / inf = NaN (the reference: -inf * sigmoid = -inf * 0)
+        return (x / (1.0 + np.exp(-x))).astype(F32)
 
 
 def rmsnorm_rope(y16: np.ndarray, norm_q, norm_k, rot: np.ndarray, dtype: str) -> np.ndarray:
@@ -605,6 +648,7 @@ def rmsnorm_rope(y16: np.ndarray, norm_q, norm_k, rot: np.ndarray, dtype: str) -
     return round16(y.reshape(M, N), dtype)
 
 
+@_non_finite_is_data
 def gemm_w4a4(
     qa: np.ndarray,
     ascales: np.ndarray,
@@ -623,6 +667,7 @@ def gemm_w4a4(
     norm_k=None,
     rot=None,
     accum: str = "fp32",  # "fp32": exact accumulation ; "ref16": the reference's 16-bit chain
+    packed_qkv: bool = False,  # rmsnorm_rope: the reference's out_q / out_k / out_v form (EpiloguePackQKV): no fp16 clamp
     envelope: bool = False,  # gelu_quant: also return the approximation envelope of codes and scales ("envelope": quantize_rows_envelope's dict)
 ):
     """kernels::gemm_w4a4 (gemm_w4a4_launch_impl.cuh:7-424) with the epilogue chain
@@ -639,6 +684,18 @@ def gemm_w4a4(
                   fsum) sequentially over groups in the 16-bit type (USE_FP32_ACCUM=false,
                   gemm_w4a4.cuh:1080), bias add in 16-bit (gemm_base.cuh:717-767), low-rank
                   in fp32 then back to 16-bit (lora.cuh:145-158,221).
+
+    The end of the chain (gemm_w4a4_launch_impl.cuh:282-423) and the fp16 clamp (:func:`clamp16_default`):
+      fuse="none"         EpilogueNop  -> EpilogueDefault (:407-420)                      clamped
+      fuse="silu"         EpilogueSilu -> EpilogueDefault (:416-417)                      clamped, AFTER the SiLU
+      fuse="rmsnorm_rope" EpilogueRMSNormRope -> EpilogueDefault (:395-404, ``out``)      clamped: Q, K after norm + rotation, and V
+                          EpilogueRMSNormRope -> EpiloguePackQKV (:377-394, out_q/k/v)    NOT clamped (epilogues.cuh:427-549 converts and
+                          stores, nothing else): ``packed_qkv=True`` restates that form's VALUES (its tile layout is not modelled).
+                          nunchaku_amd's ``out_vt`` is the V third of the ``out`` form transposed, and is clamped like it.
+      fuse="gelu_quant"   EpilogueGelu -> EpilogueQuantize: no 16-bit output.
+    Non-finite operands are ordinary data: an infinite ascale times a zero partial sum is NaN, as in IEEE arithmetic (and in
+    the reference's __hfma2 chain); such rows come out as float64 computes them, passed through the clamp above
+    (fp16: NaN -> +65504).  Nothing here raises or warns on them.
 
     Returns a dict with "out" (16-bit, [M, N]) or, for fuse="gelu_quant",
     "qout" (uint4 codes int8 [M, N]), "oscales" [N/64, M], "lora_act_out" f32 [M, R'].
@@ -680,14 +737,13 @@ def gemm_w4a4(
         raise ValueError(accum)
 
     if fuse == "none":
-        out = y16
-        if dtype == "fp16":  # EpilogueDefault clamp, gemm_base.cuh:689-695
-            out = np.clip(out, -65504.0, 65504.0)
-        return {"out": out}
+        return {"out": clamp16_default(y16, dtype)}  # EpilogueDefault, gemm_base.cuh:689-695
     if fuse == "silu":
-        return {"out": round16(silu(y16), dtype)}
+        # EpilogueSilu (gemm_base.cuh:783-792) on the 16-bit tile, then EpilogueDefault's clamp (launch_impl.cuh:416-417)
+        return {"out": clamp16_default(round16(silu(y16), dtype), dtype)}
     if fuse == "rmsnorm_rope":
-        return {"out": rmsnorm_rope(y16, norm_q, norm_k, rot, dtype)}
+        out = rmsnorm_rope(y16, norm_q, norm_k, rot, dtype)
+        return {"out": out if packed_qkv else clamp16_default(out, dtype)}  # launch_impl.cuh:377-405
     if fuse == "gelu_quant":
         # EpilogueGelu (epilogues.cuh:22-44) -> 16-bit
         g16 = round16(gelu_tanh(y16), dtype)

@@ -383,4 +383,7 @@ def test_wave_tile_epilogue_walk():
                         written[r] = idx
             idx += 1
         if dt == "fp16":
-            assert sum(1 for ln in lines if ln.startswith("v_med3_f32")) == 128
+            # the fp16 clamp on the converted pairs, in the reference's order (min with 65504 first: a NaN becomes +65504): one v_pk_min_f16 + one v_pk_max_f16
+            # per pair -- as many instructions as the one v_med3_f32 per element (128) they replace
+            ops = [ln.split()[0] for ln in lines if ln.startswith(("v_pk_min_f16", "v_pk_max_f16"))]
+            assert ops == ["v_pk_min_f16", "v_pk_max_f16"] * 64 and not any(ln.startswith("v_med3_f32") for ln in lines)

@@ -477,7 +477,7 @@ class Gen3:
 # the accumulators in AGPRs (1300 v_accvgpr moves and 644 B of scratch per tile in the first build).  So the epilogue is generated too: ~330 instructions per
 # wave-tile, every register named.  Same operations in the same order as gemm_w4a4_kernel's C++ (bit-identical outputs): acc += bias (an MFMA: bias[n] in k-slot 0
 # of the weight-side operand against 1.0), acc += lora_up x lora_act_in per 16 ranks in ascending order (activations rounded to 16 bits, times lora_scales[u] when
-# that is not 1), convert (fp16: clamp to +-65504 first), one v_permlane32_swap per dword so that a lane holds 8 consecutive columns, 16-byte stores.
+# that is not 1), convert (fp16: then clamp the pair to +-65504, NaN -> +65504), one v_permlane32_swap per dword so that a lane holds 8 consecutive columns, 16-byte stores.
 #   in:  v[0:127] acc; a[120:183] lora_act_in, a[184:199] lora_up, a200 bias (the loop call's "ep" loads)
 #        v209 = (lr * ldo + 8 h) * 2 (store offset of the lane's row), v210 = lr, v211 = h
 #        s94 flags (bit 0 low-rank, bit 1 bias), s95 / s96 lora_scales[0] / [1] (fp32 bits), s97 = M - (first row of the wave), s98 = 64 * ldo (bytes per 32 rows),
@@ -610,7 +610,7 @@ class GenEpi3:
                 e(f"s_mul_i32 {sr(E_S_TMP)}, {sr(E_S_RTB)}, {mi}")
                 e(f"v_add_u32 {vr(E_OFF[mi])}, {sr(E_S_TMP)}, {vr(E_OFF[0])}")
         if self.dt == "fp16":
-            e(f"s_mov_b32 {sr(E_S_TMP)}, 0x477fe000")     # 65504.0
+            e(f"s_mov_b32 {sr(E_S_TMP)}, 0x7bff7bff")     # (65504.0, 65504.0) as an fp16 pair
         for mi in range(4):
             k = 0
             for ni in range(2):
@@ -620,9 +620,13 @@ class GenEpi3:
                         for d in range(2):
                             a0 = ACC + 16 * t + (2 * j + half) * 4 + 2 * d
                             if self.dt == "fp16":
-                                e(f"v_med3_f32 {vr(E_T)}, {vr(a0)}, -{sr(E_S_TMP)}, {sr(E_S_TMP)}")
-                                e(f"v_med3_f32 {vr(E_T + 1)}, {vr(a0 + 1)}, -{sr(E_S_TMP)}, {sr(E_S_TMP)}")
-                                e(self.cvt(E_OUT + 4 * k + 2 * half + d, E_T, E_T + 1))
+                                # convert, then clamp the fp16 PAIR as the reference does (gemm_base.cuh:692-693) and cvt_clamp_pk_fp16() of the C++ epilogue:
+                                # min with 65504 FIRST, then max with -65504 -- v_pk_min / v_pk_max return the non-NaN operand, so a NaN becomes +65504
+                                # (one v_med3_f32 per element returned min3 = -65504 for it).  Same instruction count as the two v_med3_f32.
+                                o = E_OUT + 4 * k + 2 * half + d
+                                e(self.cvt(o, a0, a0 + 1))
+                                e(f"v_pk_min_f16 {vr(o)}, {vr(o)}, {sr(E_S_TMP)}")
+                                e(f"v_pk_max_f16 {vr(o)}, {vr(o)}, {sr(E_S_TMP)} neg_lo:[0,1] neg_hi:[0,1]")
                             else:
                                 e(self.cvt(E_OUT + 4 * k + 2 * half + d, a0, a0 + 1))
                     k += 1
