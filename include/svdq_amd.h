@@ -497,6 +497,32 @@ int svdq_gemv_awq(const svdq_gemv_awq_args *args, void *stream);
 #define SVDQ_GEMV_BATCH_MAX 80
 int svdq_gemv_awq_batched(const svdq_gemv_awq_args *args, int32_t count, void *stream);
 
+/* Low-rank (LoRA) branch of the M = 1 GEMV (reference: GEMV_AWQ lora_down / lora_up / lora_scale, src/Linear.cpp): `count`
+ * (<= SVDQ_GEMV_BATCH_MAX) layers in one call, issued behind svdq_gemv_awq_batched on the same stream over the entries that
+ * carry a LoRA.  Per entry, with fp32 accumulation and three 16-bit roundings:
+ *   t[j]    = round16( sum_k down[j,k] * x[k] )
+ *   d[n]    = round16( strength * sum_j up[n,j] * t[j] )
+ *   out[n'] = round16( out[n'] + d[n] ),  n' = (n % c) * (N / c) + n / c for out_chunks = c > 1 (the layout the GEMV wrote), else n
+ * (the sums and the product with strength are formed in fp64 and rounded once to 16 bits: each rounding point is the correctly rounded value.)
+ * r must be a multiple of 16, 16 <= r <= 128 (zero-pad the factors), K a multiple of 8; x, K and dtype are shared by all
+ * entries; x, down and up 16-byte aligned.  Two kernels (down, then up), no host synchronisation, safe under stream capture.
+ * Every t[j] and every out[n'] has one owner with a fixed summation order -- no atomics: bit-reproducible.  An update that
+ * rounds to zero (strength = 0) leaves out bit for bit as it was.  `t` must not be shared between entries of one call. */
+typedef struct svdq_gemv_lora_args {
+    const void *x;      /* [K] 16-bit: the GEMV's input row */
+    const void *down;   /* [r, K] 16-bit, row-major */
+    const void *up;     /* [N, r] 16-bit, row-major (logical output order: NOT de-interleaved) */
+    void *out;          /* [N] 16-bit, read-modify-write */
+    void *t;            /* [r] 16-bit scratch: the down projection, written by the first kernel and read by the second */
+    float strength;
+    int32_t r, N, K;
+    int32_t dtype;      /* SVDQ_BF16 | SVDQ_FP16 */
+    int32_t out_chunks; /* as svdq_gemv_awq_args.out_chunks */
+    int32_t reserved[2];
+} svdq_gemv_lora_args;
+
+int svdq_gemv_awq_lora_batched(const svdq_gemv_lora_args *entries, int32_t count, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * AWQ W4A16 GEMM, group 128 (ABI 23; reference: ops.gemm_awq, nunchaku/csrc/ops.h:148-160 -> src/kernels/awq/gemm_awq.cu;
  * module nunchaku/models/text_encoders/linear.py, W4Linear).  The projections of the 4-bit T5 text encoder, any M >= 1.

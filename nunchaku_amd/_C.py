@@ -800,7 +800,41 @@ class _Ops:
         for s0 in range(0, len(layers), 80):
             n = min(80, len(layers) - s0)
             _lib.check(lib.svdq_gemv_awq_batched(C.cast(C.byref(arr[s0]), C.POINTER(_lib.GemvAwqArgs)), n, _stream()), "gemv_awq_batched")
+        # the low-rank branch of the layers that carry a LoRA (AWQW4A16Linear.set_lora): directly behind, on the same stream; no launch without one
+        lora = [(l._lora, o, int(getattr(l, "out_chunks", 1))) for l, o in zip(layers, outs) if getattr(l, "_lora", None) is not None]
+        if lora:
+            ops.gemv_awq_lora_batched(x, lora)
         return outs
+
+    @staticmethod
+    def gemv_awq_lora_batched(in_feats, entries):
+        """Extension: ``out += strength * up @ round16(down @ x)`` for every ``(lora, out, out_chunks)`` of ``entries`` on the same single
+        row ``in_feats``, in place, two launches per 80 entries (svdq_gemv_awq_lora_batched: rounding points in include/svdq_amd.h).
+        ``lora`` has ``down [r, K]``, ``up [N, r]``, ``t [r]`` (scratch) and ``strength``; r a multiple of 16, at most 128;
+        ``out`` holds N elements in the layout the GEMV wrote with ``out_chunks``."""
+        lib = _lib.load()
+        if in_feats.dtype not in _DT or in_feats.numel() != in_feats.shape[-1] or not in_feats.is_cuda:
+            raise ValueError("gemv_awq_lora_batched: in_feats must be one row of a 16-bit GPU tensor")
+        x = in_feats.reshape(-1)
+        if not x.is_contiguous():
+            x = x.contiguous()
+        if x.data_ptr() % 16:  # (a row of a wider tensor that starts off a 16-byte boundary: the kernel's loads are 16 bytes wide)
+            x = x.clone()
+        k = x.numel()
+        arr = (_lib.GemvLoraArgs * len(entries))()
+        for a, (lo, out, chunks) in zip(arr, entries):
+            r = lo.down.shape[0]
+            n = lo.up.shape[0]
+            if lo.down.dim() != 2 or lo.up.dim() != 2 or lo.down.shape[1] != k or lo.up.shape[1] != r or lo.t.numel() != r or out.numel() != n:
+                raise ValueError("gemv_awq_lora_batched: need down [r, K], up [N, r], t [r] and out [N]")
+            for t in (lo.down, lo.up, lo.t, out):
+                if t.dtype != x.dtype or t.device != x.device:
+                    raise ValueError("gemv_awq_lora_batched: every tensor must have in_feats' dtype and device")
+            a.x, a.down, a.up, a.out, a.t = x.data_ptr(), _ptr(lo.down), _ptr(lo.up), _ptr(out), _ptr(lo.t)
+            a.strength, a.r, a.N, a.K, a.dtype, a.out_chunks = float(lo.strength), r, n, k, _DT[x.dtype], int(chunks)
+        for s0 in range(0, len(entries), 80):
+            n = min(80, len(entries) - s0)
+            _lib.check(lib.svdq_gemv_awq_lora_batched(C.cast(C.byref(arr[s0]), C.POINTER(_lib.GemvLoraArgs)), n, _stream()), "gemv_awq_lora_batched")
 
     @staticmethod
     def attention_fp16(q, k, v, o, scale):

@@ -101,6 +101,14 @@ class GemvAwqArgs(C.Structure):
     ]
 
 
+class GemvLoraArgs(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("down", C.c_void_p), ("up", C.c_void_p), ("out", C.c_void_p), ("t", C.c_void_p),
+        ("strength", C.c_float), ("r", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+        ("dtype", C.c_int32), ("out_chunks", C.c_int32), ("reserved", C.c_int32 * 2),
+    ]
+
+
 class GemmAwqArgs(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("qweight", C.c_void_p), ("scales", C.c_void_p), ("scaled_zeros", C.c_void_p),
@@ -116,6 +124,7 @@ EXPORTS = {
     "svdq_attention": (C.c_int, [C.POINTER(AttentionArgs), C.c_void_p]),
     "svdq_gemv_awq": (C.c_int, [C.POINTER(GemvAwqArgs), C.c_void_p]),
     "svdq_gemv_awq_batched": (C.c_int, [C.POINTER(GemvAwqArgs), C.c_int32, C.c_void_p]),
+    "svdq_gemv_awq_lora_batched": (C.c_int, [C.POINTER(GemvLoraArgs), C.c_int32, C.c_void_p]),
     "svdq_gemm_awq": (C.c_int, [C.POINTER(GemmAwqArgs), C.c_void_p]),
     "svdq_gemm_awq_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "svdq_residual_gate_stats": (C.c_int, [C.POINTER(ResidualArgs), C.c_void_p]),

@@ -383,6 +383,7 @@ class FluxEngineMixin:
         self.norm_out = _AdaLNContinuous(dim, torch_dtype, device)
         self.proj_out = nn.Linear(dim, in_channels, dtype=torch_dtype, device=device)
         self.dtype_ = torch_dtype
+        self._dense_lora: dict = {}  # LoRA deltas merged into 16-bit parameters: name -> (parameter, copy of its original data, fp32 delta at strength 1)
 
     # short names used throughout this package (and by its tests / tools)
     @property
@@ -427,23 +428,70 @@ class FluxEngineMixin:
 
     # runtime LoRA (reference: NunchakuFluxTransformer2dModel.update_lora_params / set_lora_strength,
     # transformer_flux.py:783-855): per-layer factors in logical layout widen the low-rank branch of that layer
-    def update_lora_params(self, lora: dict, strength: float = 1.0):
-        """``lora``: module name (e.g. ``"blocks.0.attn.to_qkv"``) -> ``(down [r, in], up [out, r])``."""
+    @torch.no_grad()
+    def update_lora_params(self, lora, strength: float = 1.0):
+        """``lora``: a diffusers / PEFT LoRA -- the path of a ``.safetensors`` file (``str`` / ``os.PathLike``) or its state dict
+        (``<module>.lora_A.weight`` / ``.lora_B.weight`` [/ ``.alpha``] keys, ``transformer.`` prefix optional: converted by
+        ``nunchaku_amd.lora.flux.to_engine_lora``) -- or, as before, ``{engine module name: (down [r, in], up [out, r])}``
+        (e.g. ``"transformer_blocks.0.attn.to_qkv"``; a 1-D tensor under ``"<module name>.bias"`` is a bias delta).  Replaces a LoRA attached earlier.
+        ``SVDQW4A4Linear`` and ``AWQW4A16Linear`` targets get a low-rank branch (``set_lora``); ``nn.Linear`` targets (embedders, ``norm_out.linear``,
+        ``proj_out``) are merged, ``W += strength * up @ down``, with the original kept for :meth:`reset_lora` / :meth:`set_lora_strength`.
+        Attaching, rescaling or removing a LoRA changes tensor shapes, kernel arguments (the strengths) or launches: a captured step
+        (``graph.CapturedStep``) has to be captured again afterwards, as with ``SVDQW4A4Linear.set_lora``.
+        A nunchaku-format LoRA (``lora_down`` / ``lora_up`` / ``qweight`` keys) raises ``NotImplementedError``; keys that fit nothing ``KeyError``."""
+        import os
+
+        from ..lora import flux as lora_flux
+
+        if isinstance(lora, (str, os.PathLike)):
+            lora = lora_flux.load_state_dict(lora)
+        if lora_flux.is_nunchaku_format(lora) or lora_flux.is_peft_format(lora):
+            lora = lora_flux.to_engine_lora(lora, self)
         mods = dict(self.named_modules())
+        bad = [n for n, v in lora.items() if not (isinstance(mods.get(n), (SVDQW4A4Linear, AWQW4A16Linear, nn.Linear)) and isinstance(v, (tuple, list)))
+               and not (n.endswith(".bias") and getattr(mods.get(n[:-5]), "bias", None) is not None and torch.is_tensor(v))]
+        if bad:
+            raise KeyError(f"update_lora_params: {bad} name no SVDQW4A4Linear, AWQW4A16Linear or nn.Linear (or '<module>.bias') of this model, "
+                           "and are no diffusers / PEFT LoRA keys (<module>.lora_A.weight / <module>.lora_B.weight)")
         self.reset_lora()
-        for name, (down, up) in lora.items():
-            if not isinstance(mods.get(name), SVDQW4A4Linear):
-                raise KeyError(f"update_lora_params: {name} is not an SVDQW4A4Linear of this model")
-            mods[name].set_lora(down, up, strength)
+        for name, v in lora.items():
+            if name not in mods:  # "<module>.bias": original kept, delta merged below
+                layer = mods[name[:-5]]
+                if isinstance(layer, SVDQW4A4Linear):
+                    layer._ensure_layout()  # the kernel layout of a bias is the natural order
+                self._dense_lora[name] = (layer.bias, layer.bias.data.clone(), v.reshape(-1).to(layer.bias.device, torch.float32))
+            elif isinstance(mods[name], nn.Linear):
+                w = mods[name].weight
+                down, up = v
+                if tuple(up.shape) != (w.shape[0], down.shape[0]) or down.shape[1] != w.shape[1]:
+                    raise ValueError(f"update_lora_params: {name}: expected down [r, {w.shape[1]}] and up [{w.shape[0]}, r]")
+                self._dense_lora[name] = (w, w.data.clone(), up.to(w.device, torch.float32) @ down.to(w.device, torch.float32))
+            else:
+                mods[name].set_lora(v[0], v[1], strength)
+        self._merge_dense_lora(strength)
 
+    def _merge_dense_lora(self, strength: float):
+        """16-bit parameter = round16(original + strength * delta), the sum in fp32"""
+        for param, orig, delta in self._dense_lora.values():
+            param.data.copy_((orig.float() + float(strength) * delta).to(orig.dtype))  # in place: whoever holds the storage sees the new weights
+
+    def lora_layers(self):
+        return [m for m in self.modules() if isinstance(m, (SVDQW4A4Linear, AWQW4A16Linear))]
+
+    @torch.no_grad()
     def set_lora_strength(self, strength: float):
-        for m in self.svdq_layers():
-            if m._base_lowrank is not None:
+        for m in self.lora_layers():
+            if (m._base_lowrank if isinstance(m, SVDQW4A4Linear) else m._lora) is not None:
                 m.set_lora_strength(strength)
+        self._merge_dense_lora(strength)
 
+    @torch.no_grad()
     def reset_lora(self):
-        for m in self.svdq_layers():
+        for m in self.lora_layers():
             m.reset_lora()
+        for param, orig, _ in self._dense_lora.values():
+            param.data.copy_(orig)
+        self._dense_lora.clear()
 
     @torch.no_grad()
     def init_synthetic_(self, seed: int = 0, repack: bool = True, codes: str = "uniform"):

@@ -17,6 +17,7 @@ repacked layer (which drops tensor attributes) stays correct.
 from __future__ import annotations
 
 import math
+from types import SimpleNamespace
 
 import torch
 from torch import nn
@@ -338,14 +339,66 @@ class AWQW4A16Linear(nn.Module):
         # extension: c > 1 makes forward() return the output de-interleaved into c contiguous [out/c] vectors
         # (what ``emb.view(B, -1, c).permute(2, 0, 1)`` of the AdaLayerNormZero modules reads), saving the copy
         self.out_chunks = 1
+        # runtime LoRA (set_lora): the factors in the layout svdq_gemv_awq_lora_batched reads (down [rp, in], up [out, rp], rp = ranks padded to
+        # 16; t [rp] is the kernel's scratch) + the strength.  Plain attributes, not parameters: no part of a checkpoint.
+        self._lora: SimpleNamespace | None = None
+        self._offloaded = False  # set by CPUOffloadManager while the owning block lives in host memory (set_lora then raises)
+
+    LORA_RANK_MAX = 128  # of the GEMV's low-rank branch (svdq_gemv_awq_lora_batched)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         from ..ops.gemv import awq_gemv_w4a16_cuda
 
         m = x.numel() // x.shape[-1]
-        return awq_gemv_w4a16_cuda(in_feats=x, kernel=self.qweight, scaling_factors=self.wscales, zeros=self.wzeros,
-                                   m=m, n=self.out_features, k=self.in_features, group_size=self.group_size, bias=self.bias,
-                                   out_chunks=self.out_chunks)
+        out = awq_gemv_w4a16_cuda(in_feats=x, kernel=self.qweight, scaling_factors=self.wscales, zeros=self.wzeros,
+                                  m=m, n=self.out_features, k=self.in_features, group_size=self.group_size, bias=self.bias,
+                                  out_chunks=self.out_chunks)
+        self.add_lora_(x, out)
+        return out
+
+    def add_lora_(self, x: torch.Tensor, out: torch.Tensor, out_chunks: int | None = None) -> torch.Tensor:
+        """``out += strength * up @ (down @ x)`` in place on a GEMV output of this layer (``out_chunks``: the layout it was written in; default: the
+        layer's own), row by row (the kernel takes one input row; the scratch is reused in stream order).  Nothing is launched without a LoRA."""
+        if self._lora is None:
+            return out
+        from ..ops.gemv import awq_gemv_lora_batched
+
+        c = self.out_chunks if out_chunks is None else out_chunks
+        x2, o2 = x.reshape(-1, self.in_features), out.view(-1, self.out_features)
+        for i in range(x2.shape[0]):
+            awq_gemv_lora_batched(x2[i], [(self._lora, o2[i], c)])
+        return out
+
+    @torch.no_grad()
+    def set_lora(self, down: torch.Tensor, up: torch.Tensor, strength: float = 1.0) -> "AWQW4A16Linear":
+        """Attach a user LoRA ``W += strength * up @ down`` (``down`` [r, in], ``up`` [out, r], logical layout: ``up`` rows in the checkpoint's
+        (interleaved) output order -- ``out_chunks`` is applied by the kernel).  The 4-bit weights are untouched: the GEMV's output gets
+        ``strength * up @ (down @ x)`` added by two small launches behind it (reference: GEMV_AWQ lora_down / lora_up / lora_scale)."""
+        if self._offloaded:
+            raise RuntimeError("set_lora: this layer belongs to a block that lives in host memory (CPUOffloadManager): attaching a LoRA to an offloaded "
+                               "block is unsupported whether it happens before or after set_offload(True): merge it into the checkpoint, or keep "
+                               "the block resident (num_blocks_on_gpu)")
+        if down.dim() != 2 or up.dim() != 2 or down.shape[1] != self.in_features or tuple(up.shape) != (self.out_features, down.shape[0]):
+            raise ValueError("set_lora: expected down [r, in_features] and up [out_features, r]")
+        r = down.shape[0]
+        rp = (r + 15) // 16 * 16
+        if r < 1 or rp > self.LORA_RANK_MAX:
+            raise ValueError(f"set_lora: rank {r} (padded to {rp}) exceeds the {self.LORA_RANK_MAX} ranks of the AWQ GEMV's low-rank branch")
+        dt, dev = self.wscales.dtype, self.wscales.device
+        d = torch.zeros(rp, self.in_features, dtype=dt, device=dev)
+        d[:r] = down.to(dt)
+        u = torch.zeros(self.out_features, rp, dtype=dt, device=dev)
+        u[:, :r] = up.to(dt)
+        self._lora = SimpleNamespace(down=d, up=u, t=torch.zeros(rp, dtype=dt, device=dev), strength=float(strength), rank=r)
+        return self
+
+    def set_lora_strength(self, strength: float):
+        if self._lora is None:
+            raise RuntimeError("set_lora_strength: no LoRA attached")
+        self._lora.strength = float(strength)
+
+    def reset_lora(self):
+        self._lora = None
 
     @classmethod
     def from_linear(cls, linear: nn.Linear, group_size: int = 64, torch_dtype: torch.dtype = torch.bfloat16,

@@ -31,7 +31,7 @@ import torch
 from torch import nn
 
 from .. import _lib, layout
-from .linear import SVDQW4A4Linear
+from .linear import AWQW4A16Linear, SVDQW4A4Linear
 
 _ALIGN = 256
 
@@ -136,6 +136,14 @@ class CPUOffloadManager:
     def _to_offload_form(self, block: nn.Module):
         """On the GPU: every SVDQuant tensor of ``block`` in the kernel layout, except ``qweight`` in nibble form."""
         for m in block.modules():
+            if isinstance(m, AWQW4A16Linear):  # same refusal as below: the LoRA factors are no part of the host image
+                if m._lora is not None:
+                    import warnings
+                    warnings.warn("CPUOffloadManager: the runtime LoRA attached to an offloaded AWQW4A16Linear is removed (set_lora / "
+                                  "update_lora_params do not reach offloaded blocks)", RuntimeWarning, stacklevel=3)
+                m.reset_lora()
+                m._offloaded = True
+                continue
             if not isinstance(m, SVDQW4A4Linear):
                 continue
             if m._base_lowrank is not None:
@@ -259,7 +267,7 @@ class CPUOffloadManager:
             for _, _, t in _named_tensors(blk):
                 t.data = t.data.to(device, copy=True)
             for m in blk.modules():
-                if isinstance(m, SVDQW4A4Linear):
+                if isinstance(m, (SVDQW4A4Linear, AWQW4A16Linear)):
                     m._offloaded = False
         self._images.clear()
         self._slots = []

@@ -245,7 +245,8 @@ class NunchakuQwenImageTransformerBlock(nn.Module):
         outs = []
         for lin in (self.img_mod[1], self.txt_mod[1]):
             m = awq_gemv_w4a16_cuda(temb_act, lin.qweight, lin.wscales, lin.wzeros, 1, lin.out_features, lin.in_features, lin.group_size,
-                                    lin.bias, out_chunks=6).view(6, -1)
+                                    lin.bias, out_chunks=6)
+            m = lin.add_lora_(temb_act, m, out_chunks=6).view(6, -1)  # (a LoRA on the modulation projection: nothing is launched without one)
             if self.scale_shift != 0:
                 m[1::3] += self.scale_shift  # a 16-bit add, as the reference's `scale + scale_shift` (:203-205)
             outs.append(m)
@@ -519,7 +520,7 @@ class NunchakuQwenImageTransformer2DModel(_DiffusersQwen if HAVE_DIFFUSERS_QWEN 
             if not self.offload and self.batched_mods:
                 # all 2 x num_layers modulation projections depend on temb only: ONE batched GEMV launch, +1 on the scale rows in two ops
                 lins = [SimpleNamespace(qweight=l.qweight, wscales=l.wscales, wzeros=l.wzeros, bias=l.bias, out_features=l.out_features,
-                                        in_features=l.in_features, group_size=l.group_size, out_chunks=6)
+                                        in_features=l.in_features, group_size=l.group_size, out_chunks=6, _lora=l._lora)
                         for b in self.transformer_blocks for l in (b.img_mod[1], b.txt_mod[1])]
                 outs = awq_gemv_w4a16_batched(temb_act, lins)
                 base = outs[0]._base if outs[0]._base is not None else outs[0]  # the launch's one output buffer: the layers' vectors back to back

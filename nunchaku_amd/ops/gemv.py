@@ -18,5 +18,12 @@ def awq_gemv_w4a16_cuda(in_feats: torch.Tensor, kernel: torch.Tensor, scaling_fa
 
 def awq_gemv_w4a16_batched(in_feats: torch.Tensor, layers) -> list[torch.Tensor]:
     """All of ``layers`` (AWQW4A16Linear) applied to the same single row ``in_feats`` in one launch (extension): the
-    modulation projections of every block of a denoising step depend only on the timestep embedding."""
+    modulation projections of every block of a denoising step depend only on the timestep embedding.  Layers that carry a LoRA
+    (``set_lora``) get their low-rank branch from one more batched call right behind it."""
     return ops.gemv_awq_batched(in_feats, list(layers))
+
+
+def awq_gemv_lora_batched(in_feats: torch.Tensor, entries) -> None:
+    """The low-rank branch behind the GEMV (extension): ``out += strength * up @ round16(down @ in_feats)`` in place for every
+    ``(lora, out, out_chunks)`` of ``entries`` (``lora``: what ``AWQW4A16Linear.set_lora`` keeps) on one input row, two launches."""
+    ops.gemv_awq_lora_batched(in_feats, list(entries))
