@@ -464,6 +464,36 @@ typedef struct svdq_residual_diff_args {
 int svdq_residual_diff(const svdq_residual_diff_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Modulated-input difference (the decision pass of TeaCache; added WITHOUT a version bump: one new symbol, nothing existing changes, so
+ * SVDQ_ABI_VERSION stays 24.  reference: nunchaku/caching/teacache.py:187,199-200 -- block 0's AdaLayerNormZero output and
+ * `(m - prev).abs().mean() / prev.abs().mean()`, 16-bit torch ops):
+ *   m[r, c] = round16( round16( round16((x[r, c] - mean[r]) * rstd[r]) * mod_scale[c] ) + mod_shift[c] )
+ *   out_mod[r, c] = m[r, c]                                                                       (if out_mod)
+ *   sum_diff = sum |round16(prev[r, c] - m[r, c])|;   sum_prev = sum |prev[r, c]|                  (if prev)
+ * over rows [0, M) of [M, C] 16-bit tensors with the common row stride ld; rows at or beyond M are neither read nor written.
+ * m has the rounding points of the quantiser's fused front end (svdq_quantize_args.ln_stats / mod_scale / mod_shift): (x - mean) in
+ * fp32, and the checkpoint's scale already contains the +1.  stats is what svdq_residual_gate_stats writes.  prev and out_mod may be the
+ * same buffer (the caller keeps one across steps).  prev == NULL modulates and stores only (the first step of a run); out_mod == NULL
+ * with prev compares only.  The sums follow svdq_residual_diff's contract -- per-row fp32 sums to `partials`, the same finishing kernel
+ * behind the first on the same stream, the same record, no floating-point atomics, bit-identical from launch to launch -- and a term
+ * passes through at most 8 * ceil(C / 512) + 6 + ceil(M / 256) + 8 additions.  C as for svdq_residual_gate_stats.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct svdq_modulated_diff_args {
+    const void *x;         /* [M, C] 16-bit, row stride ld */
+    const float *stats;    /* [M, 2] fp32 (mean, rstd) of the rows of x; required */
+    const void *mod_scale; /* [C] 16-bit */
+    const void *mod_shift; /* [C] 16-bit */
+    const void *prev;      /* [M, C] or NULL (no sums) */
+    void *out_mod;         /* [M, C] or NULL; may alias prev */
+    float *partials;                   /* [M, 2] fp32 scratch; required with prev */
+    svdq_residual_diff_result *result; /* DEVICE record; required with prev */
+    int32_t M, C, ld;
+    int32_t dtype;
+} svdq_modulated_diff_args;
+
+int svdq_modulated_diff(const svdq_modulated_diff_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * AWQ W4A16 GEMV (reference: ops.gemv_awq, nunchaku/csrc/ops.h:123-145 -> src/kernels/awq/gemv_awq.cu:100-286;
  * module nunchaku/models/linear.py:277-414).  The AdaLayerNormZero modulation projections of every block.
  *   out[m, n] = round16( sum_k round16( round16(q[n,k]*scales[k/64,n] + zeros[k/64,n]) * x[m,k] ) ) (+ bias[n])

@@ -1,1 +1,1 @@
-"""reference: nunchaku/caching/ (First-Block Cache)."""
+"""reference: nunchaku/caching/ (First-Block Cache, TeaCache)."""

@@ -700,6 +700,38 @@ class _Ops:
         _lib.check(lib.svdq_residual_diff(C.byref(args), _stream()), "residual_diff")
 
     @staticmethod
+    def modulated_diff(x, stats, mod_scale, mod_shift, prev=None, out_mod=None, partials=None, result=None):
+        """Extension (TeaCache): ``m = round16(round16(round16((x - mean) * rstd) * mod_scale) + mod_shift)`` -- the quantiser's fused
+        AdaLayerNormZero front end -- written to ``out_mod`` and, with ``prev``, the fp32 sums of ``|prev - m|`` and ``|prev|`` reduced in a
+        fixed order into the device record ``result`` (the layout of :meth:`residual_diff`'s).  2-D row-major views with a common row
+        stride; ``out_mod`` may be ``prev``; ``stats``: float32 ``[M, 2]``; ``partials``: float32 scratch of 2 x M."""
+        lib = _lib.load()
+        if x.dim() != 2 or x.stride(1) != 1 or x.dtype not in _DT:
+            raise ValueError("modulated_diff: x must be a 2-D 16-bit view with unit column stride")
+        M, Cc = x.shape
+        for name, t in (("prev", prev), ("out_mod", out_mod)):
+            if t is not None and (tuple(t.shape) != (M, Cc) or t.stride() != x.stride() or t.dtype != x.dtype):
+                raise ValueError(f"modulated_diff: {name} must match x in shape, strides and dtype")
+        for name, t in (("mod_scale", mod_scale), ("mod_shift", mod_shift)):
+            if t is None or t.numel() != Cc or t.dtype != x.dtype or not t.is_contiguous():
+                raise ValueError(f"modulated_diff: {name} must be a contiguous [C] tensor in the dtype of x")
+        if stats is None or stats.dtype != torch.float32 or stats.numel() != 2 * M or not stats.is_contiguous():
+            raise ValueError("modulated_diff: stats must be contiguous float32 [M, 2]")
+        if partials is not None and (partials.dtype != torch.float32 or partials.numel() < 2 * M or not partials.is_contiguous()):
+            raise ValueError("modulated_diff: partials must be contiguous float32 with 2 elements per row")
+        if result is not None and (result.numel() * result.element_size() < C.sizeof(_lib.ResidualDiffResult) or not result.is_contiguous()):
+            raise ValueError("modulated_diff: result must be a contiguous buffer of at least 32 bytes")
+        for t in (x, stats, mod_scale, mod_shift, prev, out_mod, partials, result):
+            if t is not None and not t.is_cuda:
+                raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
+        dp = lambda t: None if t is None else t.data_ptr()
+        args = _lib.ModulatedDiffArgs()
+        args.x, args.stats, args.mod_scale, args.mod_shift = dp(x), dp(stats), dp(mod_scale), dp(mod_shift)
+        args.prev, args.out_mod, args.partials, args.result = dp(prev), dp(out_mod), dp(partials), dp(result)
+        args.M, args.C, args.ld, args.dtype = M, Cc, x.stride(0), _DT[x.dtype]
+        _lib.check(lib.svdq_modulated_diff(C.byref(args), _stream()), "modulated_diff")
+
+    @staticmethod
     def gemv_awq(in_feats, kernel, scaling_factors, zeros, m, n, k, group_size, bias=None, out_chunks=1):
         """reference: csrc/ops.h:123-145 -> gemv_awq (src/kernels/awq/gemv_awq.cu:253-286): allocates and returns
         the output, shape ``in_feats.shape[:-1] + (n,)``.  ``kernel`` is the checkpoint's ``qweight`` as stored

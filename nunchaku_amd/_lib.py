@@ -55,6 +55,14 @@ class ResidualDiffArgs(C.Structure):
     ]
 
 
+class ModulatedDiffArgs(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("stats", C.c_void_p), ("mod_scale", C.c_void_p), ("mod_shift", C.c_void_p),
+        ("prev", C.c_void_p), ("out_mod", C.c_void_p), ("partials", C.c_void_p), ("result", C.c_void_p),
+        ("M", C.c_int32), ("C", C.c_int32), ("ld", C.c_int32), ("dtype", C.c_int32),
+    ]
+
+
 class GemmArgs(C.Structure):
     _fields_ = [
         ("act", C.c_void_p), ("wgt", C.c_void_p), ("ascales", C.c_void_p), ("wscales", C.c_void_p),
@@ -129,6 +137,7 @@ EXPORTS = {
     "svdq_gemm_awq_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "svdq_residual_gate_stats": (C.c_int, [C.POINTER(ResidualArgs), C.c_void_p]),
     "svdq_residual_diff": (C.c_int, [C.POINTER(ResidualDiffArgs), C.c_void_p]),
+    "svdq_modulated_diff": (C.c_int, [C.POINTER(ModulatedDiffArgs), C.c_void_p]),
     "svdq_gemm_workspace_bytes": (C.c_int64, []),
     "svdq_gemm_workspace_bytes_for": (C.c_int64, [C.POINTER(GemmArgs)]),
     "svdq_gemm_workspace_status": (C.c_int, [C.c_void_p, C.c_void_p]),

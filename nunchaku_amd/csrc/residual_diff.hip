@@ -50,8 +50,7 @@ __global__ __launch_bounds__(256) void residual_diff_kernel(const uint16_t *cur,
         if (out) *reinterpret_cast<u16x8 *>(out + off + c) = rv;
     }
     if (!prev) return;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { sd += __shfl_xor(sd, o); sp += __shfl_xor(sp, o); }
+    fold_wave_pair(sd, sp);
     if (lane == 0) {
         partials[2 * (size_t)grow] = sd;
         partials[2 * (size_t)grow + 1] = sp;
@@ -69,8 +68,7 @@ __global__ __launch_bounds__(256) void residual_diff_reduce_kernel(const float *
         sd += partials[2 * (size_t)r];
         sp += partials[2 * (size_t)r + 1];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { sd += __shfl_xor(sd, o); sp += __shfl_xor(sp, o); }
+    fold_wave_pair(sd, sp);
     if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = sd; sh[1][threadIdx.x >> 6] = sp; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -103,10 +101,14 @@ template <int DT> static int launch_residual_diff(const svdq_residual_diff_args 
     default: return -1;
     }
 #undef SVDQ_DIFF_CASE
-    if (p->prev)
-        hipLaunchKernelGGL((residual_diff_reduce_kernel<DT>), dim3(1), dim3(256), 0, st, (const float *)p->partials, rows,
-                           1.0f / ((float)rows * (float)p->C), p->result);
+    if (p->prev) launch_diff_reduce(DT, p->partials, rows, p->C, p->result, st);
     return 0;
+}
+
+void launch_diff_reduce(int dtype, const float *partials, int rows, int C, svdq_residual_diff_result *result, hipStream_t st) {
+    const float inv_n = 1.0f / ((float)rows * (float)C);
+    if (dtype == SVDQ_BF16) hipLaunchKernelGGL((residual_diff_reduce_kernel<SVDQ_BF16>), dim3(1), dim3(256), 0, st, partials, rows, inv_n, result);
+    else hipLaunchKernelGGL((residual_diff_reduce_kernel<SVDQ_FP16>), dim3(1), dim3(256), 0, st, partials, rows, inv_n, result);
 }
 
 } // namespace svdq

@@ -23,7 +23,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..ops.attention import attention_packed, attention_packed_quantized, kv_valid_ranges, q_prescale
-from ..ops.elementwise import residual_add_pair, residual_diff, residual_gate_stats, residual_gate_stats_pair
+from ..ops.elementwise import modulated_diff, modulated_diff_scratch, residual_add_pair, residual_diff, residual_gate_stats, residual_gate_stats_pair
 from ..ops.gemv import awq_gemv_w4a16_batched
 from ..ops.fused import (fused_gelu_mlp, fused_gelu_mlp_pair, fused_qkv_norm_rottary, fused_qkv_norm_rottary_pair,
                          linear_pair, linear_pair_quantized, quantize_two)
@@ -795,6 +795,79 @@ class FluxEngineMixin:
                 first_residual=first, hidden_states=st.hidden, encoder_hidden_states=None, threshold=residual_diff_threshold_single,
                 parallelized=False, mode="single", verbose=verbose, call_remaining_fn=remaining_single, remaining_kwargs={},
                 apply_residual_fn=apply_residual)
+        return self._tail(st)
+
+    def teacache_forward(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance=None,
+                         controlnet_block_samples=None, controlnet_single_block_samples=None, *, decide):
+        """One denoising step with TeaCache (reference: caching/teacache.py ``teacache_forward``): the decision is taken BEFORE any block runs,
+        from the AdaLayerNormZero-modulated input of joint block 0 on the real image rows.
+
+        Behind the embedders one ``svdq_modulated_diff`` pass forms that modulated input -- from the image stream's LayerNorm statistics (the
+        ones block 0 consumes anyway on the fused path) and block 0's ``shift_msa`` / ``scale_msa`` -- stores it over the previous step's
+        (``self.previous_modulated_input``, one buffer kept across steps) and compares the two on the way.  ``decide(ratio_fn)`` is the state
+        machine of ``caching.teacache`` -> ``(should_calc, refresh)``; it calls ``ratio_fn`` (the host read of the record: synchronises the
+        stream) only on steps whose outcome is not forced.  ``refresh`` False is a step inside the ``skip_steps`` window: every block runs,
+        ``previous_residual`` stays.  Skip: ``hidden += previous_residual`` on the real image rows and the tail -- no block, no modulation
+        projection but block 0's.  Computed step: the uncached step's launches, then ``previous_residual = hidden_after_blocks -
+        hidden_after_embed`` (image rows; one ``svdq_residual_diff`` subtraction into the kept buffer).
+
+        Refused with an error: a stream under capture, batch > 1, ControlNet residuals, a model with First-Block Cache switched on, an
+        offloaded model."""
+        if hidden_states.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("TeaCache reads its decision on the host, which synchronises the stream: a cached forward cannot be "
+                               "captured into a graph (run the uncached forward under capture: TeaCache(..., enabled=False))")
+        if hidden_states.shape[0] != 1:
+            raise ValueError(f"TeaCache supports batch 1 only (got {hidden_states.shape[0]}): run the samples one by one, each in "
+                             "its own TeaCache context")
+        if controlnet_block_samples is not None or controlnet_single_block_samples is not None:
+            raise ValueError("TeaCache does not support ControlNet residuals: a skipped step would drop them")
+        if getattr(self, "_is_cached", False) and getattr(self, "residual_diff_threshold_multi", -1.0) >= 0.0:
+            raise RuntimeError("TeaCache and First-Block Cache cannot be active on the same model: both decide which blocks of a step run "
+                               "(switch First-Block Cache off: residual_diff_threshold_multi < 0)")
+        if getattr(self, "offload", False):  # (no FLUX model of this library sets it today -- only Qwen-Image offloads; the guard is for the day one does)
+            raise NotImplementedError("TeaCache does not support an offloaded model")
+        nj, ns = len(self.blocks), len(self.single_blocks)
+        if nj == 0:
+            raise ValueError("TeaCache needs at least one joint block (the decision reads its modulation)")
+
+        st = self._prologue(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance)
+        t_img = st.t_img
+        self._launch_mods(st, range(0, 1), range(0))  # of the block whose modulation the decision reads
+        mods0 = st.mods.get(("j", 0))
+        shift_msa, scale_msa = (mods0[0] if mods0 is not None else self.blocks[0].mod(st.temb_act)).view(6, -1)[:2]
+        x = st.hidden[0, :t_img]  # padding rows take no part
+        stats = st.stats[0][0][:t_img] if st.fused else residual_gate_stats(x)[1]
+        buf = getattr(self, "previous_modulated_input", None)
+        usable = buf is not None and buf.shape == x.shape and buf.dtype == x.dtype and buf.device == x.device
+        if not usable:  # first step of a context (or a new token count): the buffers that are then kept across steps
+            buf = torch.empty_like(x)
+            self._teacache_scratch = modulated_diff_scratch(t_img, x.device)
+        _, record = modulated_diff(x, stats, scale_msa, shift_msa, prev=buf if usable else None, out=buf, scratch=self._teacache_scratch)
+        self.previous_modulated_input = buf
+
+        def ratio():
+            if record is None:
+                raise RuntimeError("TeaCache: no modulated input of the previous step with this step's shape to compare with "
+                                   "(the token count changed inside a run of num_steps steps)")
+            return record.read()["ratio"]
+
+        should_calc, refresh = decide(ratio)
+        res = getattr(self, "previous_residual", None)
+        if refresh and not should_calc:
+            if res is None or res.shape != x.shape or res.dtype != x.dtype or res.device != x.device:
+                raise RuntimeError("TeaCache: a step is to be skipped but no residual of a computed step with this step's shape is stored")
+            residual_gate_stats(x, res, want_stats=False)  # hidden += previous_residual, one 16-bit add in place
+            return self._tail(st)
+        h0 = st.hidden
+        self._launch_mods(st, range(1, nj), range(ns))
+        self._run_joint(st, 0, nj, keep_input=refresh)  # (the fused path updates the stream in place otherwise)
+        self._join(st)
+        self._run_single(st, 0, ns)
+        if refresh:
+            if res is None or res.shape != x.shape or res.dtype != x.dtype or res.device != x.device:
+                res = torch.empty_like(x)
+            residual_diff(st.hidden[0, st.p_txt:st.p_txt + t_img], h0[0, :t_img], out=res)
+            self.previous_residual = res
         return self._tail(st)
 
 

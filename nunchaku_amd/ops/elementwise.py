@@ -154,3 +154,34 @@ def residual_diff(cur, base=None, prev=None, out=None, want_res: bool | None = N
     if want_res:
         res = outs if isinstance(cur, (list, tuple)) else outs[0]
     return res, rec
+
+
+def modulated_diff(x, stats, scale, shift, prev=None, out=None, scratch=None):
+    """``m = LayerNorm(x) * scale + shift`` with the rounding points of the quantiser's fused AdaLayerNormZero front end (``stats``: the
+    ``[rows, 2]`` float32 (mean, rstd) of :func:`residual_gate_stats`; ``scale`` / ``shift``: ``[C]``, the scale with its +1) and, with
+    ``prev``, the relative L1 distance ``mean|prev - m| / mean|prev|`` of TeaCache's decision (reference: caching/teacache.py:199-200) in
+    the same pass.  ``x`` / ``prev`` / ``out`` are ``[..., C]`` contiguous tensors of one shape; ``out`` may be ``prev`` (one buffer kept
+    across steps).  ``scratch``: ``(partials, record)`` of an earlier :func:`modulated_diff_scratch` call to reuse instead of allocating (the
+    record of the earlier launch must have been read, or be of no interest, by then).  Returns ``(m, ResidualDiff or None)``; ``m`` is ``out``
+    when given, else new."""
+    C = x.shape[-1]
+    if out is None:
+        out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    for name, t in (("x", x), ("prev", prev), ("out", out)):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"modulated_diff: {name} must be contiguous (row slices of a contiguous tensor are)")
+        if t is not None and t.shape != x.shape:
+            raise ValueError(f"modulated_diff: shapes differ: {name} {tuple(t.shape)} vs x {tuple(x.shape)}")
+    x2 = x.view(-1, C)
+    rec = partials = result = None
+    if prev is not None:
+        partials, result = scratch if scratch is not None else modulated_diff_scratch(x2.shape[0], x.device)
+        rec = ResidualDiff(result, x.dtype)
+    ops.modulated_diff(x2, stats, scale.reshape(-1), shift.reshape(-1), None if prev is None else prev.view(-1, C), out.view(-1, C),
+                       partials=partials, result=result)
+    return out, rec
+
+
+def modulated_diff_scratch(rows: int, device):
+    """``(partials [rows, 2], record [8])`` float32: what a :func:`modulated_diff` launch with ``prev`` writes besides ``out``"""
+    return torch.empty(rows, 2, dtype=torch.float32, device=device), torch.empty(8, dtype=torch.float32, device=device)
