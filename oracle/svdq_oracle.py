@@ -1036,12 +1036,14 @@ def ln_mod_ref(x: np.ndarray, stats: np.ndarray, scale: np.ndarray, shift: np.nd
 # reference's different-but-equivalent algorithm.
 # --------------------------------------------------------------------------
 def attention_tiled(q: np.ndarray, k: np.ndarray, v: np.ndarray, scale: float, dtype: str, kb: int = 64, wave_rows: int = 32,
-                    defer_log2: float = 8.0) -> np.ndarray:
+                    defer_log2: float = 8.0, key_mask: np.ndarray | None = None) -> np.ndarray:
     """One head.  q [Lq, d], k / v [L, d]: 16-bit values carried as float32.  Per tile of ``kb`` keys:
     S = Q K^T in fp32; row maximum of the tile; the running (O, l) are rescaled only when some row of the 32-row wave
     block outgrew its running maximum by more than ``defer_log2`` (in log2 units, after scale * log2(e)) -- then EVERY
     row of the block takes max(m, m_tile); P = exp2(S c - m c) in fp32, ROUNDED to the 16-bit type; O += P16 V (fp32
-    accumulate) and l += sum(P16) -- the row sum is over the rounded probabilities; out = round16(O / l)."""
+    accumulate) and l += sum(P16) -- the row sum is over the rounded probabilities; out = round16(O / l).
+    ``key_mask`` (bool [L]): the real keys of a padded buffer (svdq_attention_args.kv_len0 ..): the others score -inf whatever their
+    K rows hold, tiles without a real key are skipped."""
     Lq, d = q.shape
     L = k.shape[0]
     assert L % kb == 0 and Lq % wave_rows == 0
@@ -1054,7 +1056,14 @@ def attention_tiled(q: np.ndarray, k: np.ndarray, v: np.ndarray, scale: float, d
         m = np.full(wave_rows, -np.inf, dtype=F32)
         l = np.zeros(wave_rows, dtype=F32)
         for t0 in range(0, L, kb):
-            s = (qb @ k[t0:t0 + kb].T).astype(F32)
+            if key_mask is not None:
+                if not key_mask[t0:t0 + kb].any():
+                    continue
+                kt, vt = (np.where(key_mask[t0:t0 + kb, None], t[t0:t0 + kb], F32(0)) for t in (k, v))
+                s = np.where(key_mask[None, t0:t0 + kb], (qb @ kt.T).astype(F32), F32(-np.inf))
+            else:
+                kt, vt = k[t0:t0 + kb], v[t0:t0 + kb]
+                s = (qb @ kt.T).astype(F32)
             mloc = s.max(axis=1)
             with np.errstate(invalid="ignore"):
                 grow = (mloc - m) * c
@@ -1068,7 +1077,7 @@ def attention_tiled(q: np.ndarray, k: np.ndarray, v: np.ndarray, scale: float, d
                 m = m_new
             p = np.exp2((s * c - (m * c)[:, None]).astype(F32)).astype(F32)
             p16 = round16(p, dtype)
-            o += (p16 @ v[t0:t0 + kb]).astype(F32)
+            o += (p16 @ vt).astype(F32)
             l += p16.sum(axis=1, dtype=F32)
         out[w0:w0 + wave_rows] = o / l[:, None]
     return round16(out, dtype)
