@@ -11,7 +11,8 @@ MLP x4; every 3072-wide projection is an ``SVDQW4A4Linear`` driven through
 AdaLayerNorm modulation) are restated here with plain torch ops.  The AdaLN modulation projections are
 AWQ W4A16 GEMVs (``AWQW4A16Linear``) and attention runs on this library's kernel, as in the reference
 (SURVEY.md section 8f items 1 and 3).  Used by bench.py with synthetic weights and by the GPU tests; a
-reference checkpoint's SVDQ tensors load into the ``SVDQW4A4Linear`` members unchanged.
+reference checkpoint's SVDQ tensors load into the ``SVDQW4A4Linear`` members unchanged.  The fused path of the joint block
+(the same computation as the Qwen-Image block's) is models/blocks.py; its reference-op path (``stats is None``) is here.
 """
 
 from __future__ import annotations
@@ -23,13 +24,14 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..ops.attention import attention_packed, attention_packed_quantized, kv_valid_ranges, q_prescale
-from ..ops.elementwise import modulated_diff, modulated_diff_scratch, residual_add_pair, residual_diff, residual_gate_stats, residual_gate_stats_pair
+from ..ops.elementwise import ln_pool, modulated_diff, modulated_diff_scratch, residual_add_pair, residual_diff, residual_gate_stats
 from ..ops.gemv import awq_gemv_w4a16_batched
-from ..ops.fused import (fused_gelu_mlp, fused_gelu_mlp_pair, fused_qkv_norm_rottary, fused_qkv_norm_rottary_pair,
-                         linear_pair, linear_pair_quantized, quantize_two)
+from ..ops.fused import fused_gelu_mlp, fused_qkv_norm_rottary, fused_qkv_norm_rottary_pair, linear_pair, quantize_two
 from ..utils import pad_tensor
+from . import blocks
+from .blocks import FeedForward as _FeedForward, _GELUProj, pad256 as _pad256  # noqa: F401  (the names this module has always had)
 from .embeddings import flux_pos_embed, pack_rotemb
-from .linear import AWQW4A16Linear, SVDQW4A4Linear, synthetic_codes_
+from .linear import AWQW4A16Linear, SVDQW4A4Linear
 
 
 _FREQS: dict = {}
@@ -48,15 +50,6 @@ def timestep_embedding(t: torch.Tensor, dim: int = 256, max_period: float = 1000
             _FREQS[key] = freqs
     args = t.float()[:, None] * freqs[None]
     return torch.cat([args.cos(), args.sin()], dim=-1)
-
-
-def _pad256(n: int) -> int:
-    return (n + 255) // 256 * 256
-
-
-def _pair_compatible(la, lb) -> bool:
-    return (la.in_features == lb.in_features and la.out_features == lb.out_features and la.rank == lb.rank
-            and (la.bias is None) == (lb.bias is None) and getattr(la, "lora_scales", None) == getattr(lb, "lora_scales", None))
 
 
 class _MLPEmbedder(nn.Module):
@@ -78,14 +71,6 @@ class _TimeTextEmbed(nn.Module):
         self.timestep_embedder = _MLPEmbedder(256, dim, dtype, device)
         self.guidance_embedder = _MLPEmbedder(256, dim, dtype, device) if guidance else None
         self.text_embedder = _MLPEmbedder(pooled_dim, dim, dtype, device)
-
-
-class _AdaLNContinuous(nn.Module):
-    """diffusers' AdaLayerNormContinuous of the output head: ``linear`` (dim -> 2 dim); the LayerNorm has no parameters."""
-
-    def __init__(self, dim, dtype, device):
-        super().__init__()
-        self.linear = nn.Linear(dim, 2 * dim, dtype=dtype, device=device)
 
 
 class FluxAttentionAMD(nn.Module):
@@ -131,41 +116,39 @@ class FluxAttentionAMD(nn.Module):
         """``ln`` / ``ln_ctx`` = (stats, scale, shift): the inputs are the UN-normalised streams and the
         AdaLayerNormZero front end runs inside the QKV projections' quantiser.  ``kv_valid``: the real key rows when the
         streams are padded to 256 rows (the engine pads every token count onto this path; ``ops.attention.kv_valid_ranges``)."""
-        B = hidden.shape[0]
-        hd = self.heads * self.head_dim
+        B, hd = hidden.shape[0], self.heads * self.head_dim
         t_txt = encoder_hidden.shape[1] if self.joint else 0
         tokens = t_txt + hidden.shape[1]
         svdq = self._use_svdq(B, tokens)
+        if self.joint and svdq and self.grouped and len(rotary) > 2:  # every launch serves both streams (svdq: B == 1)
+            out = blocks.joint_attention(self, hidden, encoder_hidden, rotary[2], ln, ln_ctx, kv_valid, quantized=self.fused_out_quant)
+            if out is not None:
+                return out
         qs = q_prescale(self.head_dim) if svdq else 0.0  # the QKV GEMM emits Q times scale * log2(e): the attention kernel's fast geometry
         qkv = torch.empty(B, tokens, 3 * hd, dtype=hidden.dtype, device=hidden.device)
         vt = torch.empty(hd, tokens, dtype=hidden.dtype, device=hidden.device) if svdq else None
-        grouped = False
         if self.joint:
             # both projections write straight into one [txt; img] buffer (B == 1): no torch.cat round trip
-            rot_img, rot_txt = rotary[0], rotary[1]
-            if self.grouped and B == 1 and len(rotary) > 2:  # one launch for both streams (rows: text, then image)
+            grouped = False
+            if self.grouped and B == 1 and len(rotary) > 2 and not svdq:  # torch's attention on the grouped projections (svdq: declined above)
                 grouped = fused_qkv_norm_rottary_pair(encoder_hidden, self.add_qkv_proj, self.norm_added_q, self.norm_added_k,
                                                       hidden, self.to_qkv, self.norm_q, self.norm_k, rotary[2], qkv[0],
                                                       out_vt=vt, ln_a=ln_ctx, ln_b=ln, q_scale=qs)
-            if not grouped:
-                fused_qkv_norm_rottary(hidden, self.to_qkv, self.norm_q, self.norm_k, rot_img, output=qkv[0, t_txt:],
+            if not grouped:  # the two projections cannot share a launch: one each
+                fused_qkv_norm_rottary(hidden, self.to_qkv, self.norm_q, self.norm_k, rotary[0], output=qkv[0, t_txt:],
                                        out_vt=vt[:, t_txt:] if svdq else None, ln=ln, q_scale=qs)
-                fused_qkv_norm_rottary(encoder_hidden, self.add_qkv_proj, self.norm_added_q, self.norm_added_k, rot_txt,
+                fused_qkv_norm_rottary(encoder_hidden, self.add_qkv_proj, self.norm_added_q, self.norm_added_k, rotary[1],
                                        output=qkv[0, :t_txt], out_vt=vt[:, :t_txt] if svdq else None, ln=ln_ctx, q_scale=qs)
+            if svdq and self.grouped:
+                return blocks.joint_attention_out(self, qkv[0], vt, t_txt, ln_pool(ln_ctx), kv_valid, quantized=self.fused_out_quant)
         else:
             fused_qkv_norm_rottary(hidden, self.to_qkv, self.norm_q, self.norm_k, rotary, output=qkv.view(B * tokens, -1),
                                    out_vt=vt, ln=ln, quantized=quantized, q_scale=qs)
+            if svdq and self.fused_out_quant:
+                qres = attention_packed_quantized(qkv[0], vt, self.heads, self.out_proj, pool=ln_pool(ln), q_prescaled=True, kv_valid=kv_valid)
+                if qres is not None:  # the 16-bit attention output never exists: straight into the output projection
+                    return self.out_proj.forward_quant(*qres).view(B, tokens, -1)
         pool = None
-        if svdq and self.fused_out_quant and B == 1 and (not self.joint or (self.grouped and _pair_compatible(self.to_add_out, self.out_proj))):
-            src = ln_ctx if self.joint else ln  # the pool of the stream whose rows come first carries the scratch
-            qpool = src[3] if src is not None and len(src) > 3 else None
-            qres = attention_packed_quantized(qkv[0], vt, self.heads, self.out_proj, lin_first=self.to_add_out if self.joint else None,
-                                              split_rows=t_txt, pool=qpool, q_prescaled=True, kv_valid=kv_valid)
-            if qres is not None:  # the 16-bit attention output never exists: straight into the output projection(s)
-                if self.joint:
-                    ca, a = linear_pair_quantized(*qres, self.to_add_out, self.out_proj, t_txt)
-                    return a, ca
-                return self.out_proj.forward_quant(*qres).view(B, tokens, -1)
         if svdq:  # the same launch clears the low-rank accumulators of the output projections' quantisers
             zf = _pad256(hidden.shape[1]) * self.out_proj.rank + (_pad256(t_txt) * self.to_add_out.rank if self.joint else 0)
             o, pool = attention_packed(qkv[0], vt, self.heads, zero_floats=zf, q_prescaled=True, kv_valid=kv_valid)
@@ -182,36 +165,6 @@ class FluxAttentionAMD(nn.Module):
                 return a, ca
             return self.out_proj(o[:, t_txt:], pool=pool), self.to_add_out(o[:, :t_txt], pool=pool)
         return self.out_proj(o, pool=pool)
-
-
-class _GELUProj(nn.Module):
-    """``net.0`` of a diffusers FeedForward(activation_fn="gelu-approximate"): holds ``proj``; the activation itself runs in
-    the projection's GEMM epilogue."""
-
-    def __init__(self, dim, hidden, kw):
-        super().__init__()
-        self.proj = SVDQW4A4Linear(dim, hidden, **kw)
-
-
-class _FeedForward(nn.Module):
-    """fc1 -> GELU(tanh) -> fc2 with the requantisation fused into fc1's epilogue (reference: NunchakuFeedForward,
-    models/attention.py:76-123).  Module names are diffusers' ``net = [GELU(proj), Dropout, Linear]``: checkpoint keys
-    ``ff.net.0.proj.*`` / ``ff.net.2.*``."""
-
-    def __init__(self, dim, kw):
-        super().__init__()
-        self.net = nn.ModuleList([_GELUProj(dim, 4 * dim, kw), nn.Identity(), SVDQW4A4Linear(4 * dim, dim, **{**kw, "act_unsigned": True})])
-
-    @property
-    def fc1(self) -> SVDQW4A4Linear:
-        return self.net[0].proj
-
-    @property
-    def fc2(self) -> SVDQW4A4Linear:
-        return self.net[2]
-
-    def forward(self, x, ln=None):
-        return fused_gelu_mlp(x, self.fc1, self.fc2, ln=ln)
 
 
 class _AdaLNZero(nn.Module):
@@ -278,33 +231,11 @@ class FluxJointBlockAMD(nn.Module):
             if encoder_hidden.dtype == torch.float16:  # transformer_flux_v2.py: the fp16 joint block clips its text stream
                 encoder_hidden = encoder_hidden.clip(-65504, 65504)
             return encoder_hidden, hidden, None
-        (h_stats, h_pool), (e_stats, e_pool) = stats  # pools: fp32 zeros for the low-rank accumulators of the next calls
         m_out, c_out = mods if mods is not None else (self.mod(temb_act), self.mod_context(temb_act))
-        shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp = m_out.view(6, -1)
-        c_shift_msa, c_scale_msa, c_gate_msa, c_shift_mlp, c_scale_mlp, c_gate_mlp = c_out.view(6, -1)
-        a, ca = self.attn(hidden, encoder_hidden, rotary, ln=(h_stats, scale_msa, shift_msa, h_pool),
-                          ln_ctx=(e_stats, c_scale_msa, c_shift_msa, e_pool), kv_valid=kv_valid)
-        mp_h, mp_e = _pad256(hidden.shape[1]), _pad256(encoder_hidden.shape[1])
-        r_mlp = self.ff.fc1.rank + self.ff.fc2.rank          # fc1's quantiser + the GELU epilogue's accumulator for fc2
-        r_mlp_c = self.ff_context.fc1.rank + self.ff_context.fc2.rank
-        if self.attn.grouped and encoder_hidden.shape[1] % 256 == 0:
-            # grouped launches: the text stream's pool carries the scratch of BOTH streams (its rows come first)
-            encoder_hidden, e_stats, hidden, h_stats, e_pool = residual_gate_stats_pair(
-                encoder_hidden, ca, c_gate_msa, hidden, a, gate_msa, zero_floats=(mp_e + mp_h) * r_mlp, inplace=not keep_input)
-            ffc, ff = fused_gelu_mlp_pair(encoder_hidden, self.ff_context.fc1, self.ff_context.fc2, hidden, self.ff.fc1, self.ff.fc2,
-                                          ln_a=(e_stats, c_scale_mlp, c_shift_mlp, e_pool), ln_b=(h_stats, scale_mlp, shift_mlp))
-            encoder_hidden, e_stats, hidden, h_stats, e_pool = residual_gate_stats_pair(
-                encoder_hidden, ffc, c_gate_mlp, hidden, ff, gate_mlp, zero_floats=(mp_e + mp_h) * (self.attn.to_qkv.rank + self.attn.out_proj.rank),
-                clamp_fp16_a=True)  # the reference clips the text stream at the end of an fp16 joint block
-            return encoder_hidden, hidden, ((h_stats, None), (e_stats, e_pool))
-        hidden, h_stats, h_pool = residual_gate_stats(hidden, a, gate_msa, zero_floats=mp_h * r_mlp, inplace=not keep_input)
-        hidden, h_stats, h_pool = residual_gate_stats(hidden, self.ff(hidden, ln=(h_stats, scale_mlp, shift_mlp, h_pool)), gate_mlp,
-                                                      zero_floats=mp_h * self.attn.to_qkv.rank)  # next block's QKV quantiser
-        encoder_hidden, e_stats, e_pool = residual_gate_stats(encoder_hidden, ca, c_gate_msa, zero_floats=mp_e * r_mlp_c, inplace=not keep_input)
-        encoder_hidden, e_stats, e_pool = residual_gate_stats(
-            encoder_hidden, self.ff_context(encoder_hidden, ln=(e_stats, c_scale_mlp, c_shift_mlp, e_pool)), c_gate_mlp,
-            zero_floats=mp_e * self.attn.add_qkv_proj.rank, clamp_fp16=True)
-        return encoder_hidden, hidden, ((h_stats, h_pool), (e_stats, e_pool))
+        # the reference clips the text stream only at the end of an fp16 joint block (transformer_flux_v2.py)
+        return blocks.dual_stream_block(
+            lambda h, e, ln, ln_ctx: self.attn(h, e, rotary, ln=ln, ln_ctx=ln_ctx, kv_valid=kv_valid), self.attn, self.ff, self.ff_context,
+            hidden, encoder_hidden, stats, m_out, c_out, clamp_img=False, keep_input=keep_input, grouped=self.attn.grouped)
 
 
 class FluxSingleBlockAMD(nn.Module):
@@ -380,7 +311,7 @@ class FluxEngineMixin:
         self.time_text_embed = _TimeTextEmbed(dim, pooled_projection_dim, guidance_embeds, torch_dtype, device)
         self.transformer_blocks = nn.ModuleList([FluxJointBlockAMD(dim, heads, kw) for _ in range(num_layers)])
         self.single_transformer_blocks = nn.ModuleList([FluxSingleBlockAMD(dim, heads, kw) for _ in range(num_single_layers)])
-        self.norm_out = _AdaLNContinuous(dim, torch_dtype, device)
+        self.norm_out = blocks.AdaLNContinuous(dim, torch_dtype, device)
         self.proj_out = nn.Linear(dim, in_channels, dtype=torch_dtype, device=device)
         self.dtype_ = torch_dtype
         self._dense_lora: dict = {}  # LoRA deltas merged into 16-bit parameters: name -> (parameter, copy of its original data, fp32 delta at strength 1)
@@ -495,49 +426,8 @@ class FluxEngineMixin:
 
     @torch.no_grad()
     def init_synthetic_(self, seed: int = 0, repack: bool = True, codes: str = "uniform"):
-        """Random-init weights of FLUX shape (no checkpoints in this environment): int4 codes uniform or with the
-        distribution of a quantised Gaussian residual (``codes``: models/linear.py ``synthetic_codes_``),
-        scales/low-rank factors small so activations stay O(1).  Parameters are written in the
-        checkpoint layout (random nibbles are random int4 codes) and repacked like a real checkpoint."""
-        dev = self.proj_out.weight.device
-        g = torch.Generator(device=dev).manual_seed(seed)
-
-        def rnd(shape, scale):
-            return torch.randn(shape, generator=g, device=dev) * scale
-
-        def uni(shape):
-            return torch.rand(shape, generator=g, device=dev)
-
-        for m in self.modules():
-            if isinstance(m, SVDQW4A4Linear):
-                K = m.in_features
-                synthetic_codes_(m.qweight, m.wscales, K, g, codes)  # scaled so that |W row| ~ 1/sqrt(K)
-                if m.bias is not None:
-                    m.bias.copy_(rnd(m.bias.shape, 0.02))
-                m.smooth_factor.copy_(uni((K,)) + 0.5)
-                m.smooth_factor_orig.copy_(m.smooth_factor)
-                m.proj_down.copy_(rnd(m.proj_down.shape, 0.5 / math.sqrt(K)))
-                m.proj_up.copy_(rnd(m.proj_up.shape, 0.5 / math.sqrt(m.rank)))
-                m._amd_layout = False
-                if repack:  # False: stay in the checkpoint layout (repacked lazily on first use, like a loaded checkpoint)
-                    m.repack_()
-            elif isinstance(m, AWQW4A16Linear):
-                # uniform 4-bit codes (std 4.6) centred by the zero point: weights ~ 1/sqrt(K)
-                sc = 1.0 / (4.6 * math.sqrt(m.in_features))
-                m.qweight.copy_(torch.randint(-2 ** 31, 2 ** 31, m.qweight.shape, generator=g, device=dev, dtype=torch.int64))
-                m.wscales.copy_((uni(m.wscales.shape) * 0.5 + 0.75) * sc)
-                m.wzeros.copy_(m.wscales.float() * -7.5)
-                # nunchaku checkpoints carry the +1 of every modulation scale in the bias (scale_shift = 0,
-                # normalization.py:24-25): chunks (shift, SCALE, gate[, shift, SCALE, gate]) are interleaved per channel
-                m.bias.zero_()
-                chunks = m.out_features // m.in_features
-                m.bias.view(-1, chunks)[:, 1::3] = 1.0  # checkpoint (interleaved) order; out_chunks only permutes the OUTPUT
-            elif isinstance(m, nn.Linear):
-                m.weight.copy_(rnd(m.weight.shape, 1.0 / math.sqrt(m.in_features)))
-                m.bias.zero_()
-            elif isinstance(m, nn.RMSNorm):
-                m.weight.fill_(1.0)
-        return self
+        """Random-init weights of FLUX shape (models/blocks.py ``init_synthetic_``), repacked like a loaded checkpoint."""
+        return blocks.init_synthetic_(self, seed, codes, repack=repack, awq_scale_one=True)
 
     def engine_forward(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids,
                        guidance=None, controlnet_block_samples=None, controlnet_single_block_samples=None, controlnet_blocks_repeat=False):
@@ -641,14 +531,6 @@ class FluxEngineMixin:
         for k, i in enumerate(single):
             st.mods["s", i] = outs[2 * len(joint) + k]
 
-    @staticmethod
-    def _control(st: "_Step", samples, i, n_blocks):
-        """diffusers' choice of the ControlNet residual behind block i, as a [1, rows of the (padded) stream, dim] tensor"""
-        n = len(samples)
-        smp = samples[i % n] if st.cn_repeat else samples[i // -(-n_blocks // n)]
-        rows = st.hidden.shape[1]
-        return F.pad(smp.to(st.hidden.dtype), (0, 0, 0, rows - smp.shape[1])) if smp.shape[1] != rows else smp.to(st.hidden.dtype)
-
     def _run_joint(self, st: "_Step", lo: int, hi: int, keep_input: bool = False) -> None:
         """Joint blocks ``lo .. hi - 1``.  ``keep_input``: block ``lo`` leaves its two input tensors as they are (the fused path updates the
         streams in place otherwise)."""
@@ -657,8 +539,7 @@ class FluxEngineMixin:
             st.enc, st.hidden, st.stats = self.blocks[i](st.hidden, st.enc, st.temb_act, st.rot, st.stats, mods=st.mods.get(("j", i)),
                                                          kv_valid=st.kv_valid, keep_input=keep_input and i == lo)
             if st.cn_joint is not None:
-                # hidden_states + sample (one 16-bit add); the fused path needs the LayerNorm statistics of the sum: the same pass
-                st.hidden, h_stats = residual_gate_stats(st.hidden, self._control(st, st.cn_joint, i, nj), want_stats=st.fused)
+                st.hidden, h_stats = blocks.add_control(st.hidden, st.cn_joint, i, nj, st.cn_repeat, want_stats=st.fused)
                 if st.fused:
                     st.stats = ((h_stats, st.stats[0][1]), st.stats[1])
 
@@ -675,19 +556,14 @@ class FluxEngineMixin:
             st.hidden, st.stats = self.single_blocks[i](st.hidden, st.temb_act, st.rot[2], st.stats, mods=st.mods.get(("s", i)),
                                                         kv_valid=st.kv_valid, keep_input=keep_input and i == lo)
             if st.cn_single is not None:
-                img_rows = st.hidden[:, t_pad:]
-                smp = self._control(st, st.cn_single, i, ns)
-                _, i_stats = residual_gate_stats(img_rows, F.pad(smp, (0, 0, 0, img_rows.shape[1] - smp.shape[1])), want_stats=st.fused)
+                _, i_stats = blocks.add_control(st.hidden[:, t_pad:], st.cn_single, i, ns, st.cn_repeat, want_stats=st.fused)
                 if st.fused:
                     st.stats[0][t_pad:] = i_stats
 
     def _tail(self, st: "_Step") -> torch.Tensor:
         """The real image rows through AdaLayerNormContinuous and the output projection."""
         off = st.p_txt if st.joined else 0
-        hidden = st.hidden[:, off:off + st.t_img]
-        scale, shift = self.norm_out_mod(st.temb_act).chunk(2, dim=-1)  # AdaLayerNormContinuous
-        hidden = F.layer_norm(hidden, (self.dim,), eps=1e-6) * (1 + scale[:, None]) + shift[:, None]
-        return self.proj_out(hidden)
+        return self.proj_out(self.norm_out(st.hidden[:, off:off + st.t_img], st.temb_act))
 
     def _first_residual(self, name: str, curs, bases) -> torch.Tensor:
         """What the first block did to the real rows ``curs`` (one or two row ranges; ``bases``: the same rows before the block) as one

@@ -14,7 +14,8 @@ SDPA as separate torch / diffusers ops; Qwen's rotary (``apply_rotary_emb_qwen(u
 times a unit complex number) is exactly the adjacent-pair rotation of the FLUX QKV epilogue, so here the projection runs
 with the fused RMSNorm + RoPE epilogue (V written transposed) and attention is this library's kernel on the QKV buffer in
 place -- both streams in ONE launch each when the text length is a multiple of 256 (grouped launches).  ``fused_qkv = False``
-on the attention module selects the reference's op-for-op sequence (plain projection, torch RMSNorm / rotary, SDPA).
+on the attention module selects the reference's op-for-op sequence (plain projection, torch RMSNorm / rotary, SDPA).  The block's
+fused path (``forward_fused``: the same computation as the FLUX joint block's) is models/blocks.py.
 """
 
 from __future__ import annotations
@@ -27,42 +28,17 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ..ops.attention import attention_packed, attention_packed_quantized, kv_valid_ranges, q_prescale
-from ..ops.elementwise import residual_gate_stats, residual_gate_stats_pair
-from ..ops.fused import (fused_gelu_mlp, fused_gelu_mlp_pair, fused_qkv_norm_rottary, fused_qkv_norm_rottary_pair, linear_pair,
-                         linear_pair_quantized)
+from ..ops.attention import attention_packed, kv_valid_ranges, q_prescale
+from ..ops.elementwise import residual_gate_stats
+from ..ops.fused import fused_qkv_norm_rottary, fused_qkv_norm_rottary_pair, linear_pair
 from ..ops.gemv import awq_gemv_w4a16_batched, awq_gemv_w4a16_cuda
 from ..utils import pad_tensor
+from . import blocks
+from .blocks import FeedForward as NunchakuFeedForward, _GELUProj  # noqa: F401  (reference: models/attention.py:76-123)
 from .embeddings import pack_rotemb
-from .linear import AWQW4A16Linear, SVDQW4A4Linear, synthetic_codes_
+from .linear import AWQW4A16Linear, SVDQW4A4Linear
 from .offload import CPUOffloadManager
 from .transformer_flux import NunchakuModelLoaderMixin
-
-
-def _pad256(n: int) -> int:
-    return (n + 255) // 256 * 256
-
-
-class _GELUProj(nn.Module):
-    """``net.0`` of a diffusers FeedForward with ``activation_fn="gelu-approximate"``: holds ``proj`` (the activation itself
-    is fused into the projection's GEMM epilogue)."""
-
-    def __init__(self, dim, hidden, kw):
-        super().__init__()
-        self.proj = SVDQW4A4Linear(dim, hidden, **kw)
-
-
-class NunchakuFeedForward(nn.Module):
-    """reference: models/attention.py:76-123 -- ``net = [GELU(proj), Dropout, Linear]``; fc1 -> GELU -> fc2 with the
-    requantisation fused into fc1's epilogue."""
-
-    def __init__(self, dim, kw, mult: int = 4):
-        super().__init__()
-        self.net = nn.ModuleList([_GELUProj(dim, mult * dim, kw), nn.Identity(),
-                                  SVDQW4A4Linear(mult * dim, dim, **{**kw, "act_unsigned": True})])
-
-    def forward(self, x):
-        return fused_gelu_mlp(x, self.net[0].proj, self.net[2])
 
 
 class NunchakuQwenAttention(nn.Module):
@@ -120,28 +96,12 @@ class NunchakuQwenAttention(nn.Module):
         return self.to_out[0](o[:, t_txt:]), self.to_add_out(o[:, :t_txt])
 
     def forward_fused_norm(self, hidden, enc, packed, ln_img, ln_txt, kv_valid=None):
-        """The block's fused path (``NunchakuQwenImageTransformerBlock.forward_fused``): ``hidden`` / ``enc`` are the UN-normalised
-        streams, LayerNorm + modulation run inside the QKV quantiser (``ln_* = (stats, scale incl. +1, shift, ZeroPool)``), both
-        streams share every launch, the attention epilogue emits the output projections' quantised input.  B = 1, token counts
-        multiples of 256.  -> (image stream output, text stream output)."""
-        t_txt, t_img = enc.shape[1], hidden.shape[1]
-        tokens, hd = t_txt + t_img, self.heads * self.head_dim
-        qkv = torch.empty(tokens, 3 * hd, dtype=hidden.dtype, device=hidden.device)
-        vt = torch.empty(hd, tokens, dtype=hidden.dtype, device=hidden.device)
-        ok = fused_qkv_norm_rottary_pair(enc, self.add_qkv_proj, self.norm_added_q, self.norm_added_k, hidden, self.to_qkv, self.norm_q,
-                                         self.norm_k, packed["all"], qkv, out_vt=vt, ln_a=ln_txt, ln_b=ln_img, q_scale=q_prescale(self.head_dim))
-        if not ok:
+        """The attention of :meth:`NunchakuQwenImageTransformerBlock.forward_fused` (models/blocks.py ``joint_attention``): B = 1, token
+        counts multiples of 256, ``ln_* = (stats, scale incl. +1, shift[, ZeroPool])``.  -> (image stream output, text stream output)."""
+        out = blocks.joint_attention(self, hidden, enc, packed["all"], ln_img, ln_txt, kv_valid)
+        if out is None:
             raise RuntimeError("forward_fused_norm: the two streams' projections cannot share a launch (shapes / ranks differ)")
-        qres = attention_packed_quantized(qkv, vt, self.heads, self.to_out[0], lin_first=self.to_add_out, split_rows=t_txt, pool=ln_txt[3],
-                                          q_prescaled=True, kv_valid=kv_valid)
-        if qres is not None:
-            txt, img = linear_pair_quantized(*qres, self.to_add_out, self.to_out[0], t_txt)
-            return img, txt
-        # (shapes the attention epilogue's quantiser does not take -- the two projections' ranks differ, e.g. a runtime LoRA on one of them: the 16-bit
-        #  round trip; Q left the QKV GEMM prescaled all the same)
-        o = attention_packed(qkv, vt, self.heads, q_prescaled=True, kv_valid=kv_valid).unsqueeze(0)
-        txt, img = linear_pair(o[:, :t_txt], self.to_add_out, o[:, t_txt:], self.to_out[0])
-        return img, txt
+        return out
 
     def _reference_ops(self, hidden_states, encoder_hidden_states, packed):
         """NunchakuQwenImageNaiveFA2Processor, op for op: plain quantised projections, torch RMSNorm, rotary as the complex
@@ -253,25 +213,15 @@ class NunchakuQwenImageTransformerBlock(nn.Module):
         return outs
 
     def forward_fused(self, hidden, enc, temb_act, packed_rot, stats, mods=None, kv_valid=None):
-        """The block on this library's fused passes (B = 1, token counts multiples of 256): LayerNorm + modulation inside the
-        quantisers, gated residual + the next LayerNorm's statistics in one element-wise pass per stage (both streams per launch),
-        grouped GEMM launches, attention-side quantiser.  Same 16-bit rounding points as :meth:`forward`'s torch ops (the fused
-        passes are bit-exact restatements of them).  ``stats`` = ((txt stats, ZeroPool), img stats) of the
-        block's inputs; returns (enc, hidden, stats of the outputs)."""
-        (e_stats, pool), h_stats = stats
+        """The block on this library's fused passes (models/blocks.py ``dual_stream_block``; B = 1, token counts multiples of 256).
+        Same 16-bit rounding points as :meth:`forward`'s torch ops (the fused passes are bit-exact restatements of them, DESIGN.md
+        section 6e).  ``stats`` = ((img stats, ZeroPool or None), (txt stats, ZeroPool or None)) of the block's inputs, as in
+        models/flux.py; returns (enc, hidden, stats of the outputs)."""
         im, tm = mods if mods is not None else self.modulation(temb_act)
-        att = self.attn
-        img_a, txt_a = att.forward_fused_norm(hidden, enc, packed_rot, ln_img=(h_stats, im[1], im[0]), ln_txt=(e_stats, tm[1], tm[0], pool),
-                                              kv_valid=kv_valid)
-        mp = _pad256(hidden.shape[1]) + _pad256(enc.shape[1])
-        r_mlp = self.img_mlp.net[0].proj.rank + self.img_mlp.net[2].rank
-        enc, e_stats, hidden, h_stats, pool = residual_gate_stats_pair(enc, txt_a, tm[2], hidden, img_a, im[2], zero_floats=mp * r_mlp)
-        txt_f, img_f = fused_gelu_mlp_pair(enc, self.txt_mlp.net[0].proj, self.txt_mlp.net[2], hidden, self.img_mlp.net[0].proj, self.img_mlp.net[2],
-                                           ln_a=(e_stats, tm[4], tm[3], pool), ln_b=(h_stats, im[4], im[3]))
-        fp16 = hidden.dtype == torch.float16  # the reference clips both streams at the end of an fp16 block (:300-303)
-        enc, e_stats, hidden, h_stats, pool = residual_gate_stats_pair(
-            enc, txt_f, tm[5], hidden, img_f, im[5], zero_floats=mp * (att.to_qkv.rank + att.to_out[0].rank), clamp_fp16_a=fp16, clamp_fp16_b=fp16)
-        return enc, hidden, ((e_stats, pool), h_stats)
+        # the reference clips both streams at the end of an fp16 block (:300-303)
+        return blocks.dual_stream_block(
+            lambda h, e, ln, ln_ctx: self.attn.forward_fused_norm(h, e, packed_rot, ln, ln_ctx, kv_valid=kv_valid), self.attn, self.img_mlp,
+            self.txt_mlp, hidden, enc, stats, im, tm, clamp_img=True)
 
     def forward(self, hidden_states, encoder_hidden_states, encoder_hidden_states_mask=None, temb=None, image_rotary_emb=None,
                 joint_attention_kwargs=None, kv_valid=None):
@@ -375,7 +325,7 @@ class NunchakuQwenImageTransformer2DModel(_DiffusersQwen if HAVE_DIFFUSERS_QWEN 
         self.transformer_blocks = nn.ModuleList([
             NunchakuQwenImageTransformerBlock(dim, heads, hd, rank=rank, torch_dtype=torch_dtype, device=device)
             for _ in range(get("num_layers"))])
-        self.norm_out = nn.ModuleDict({"linear": nn.Linear(dim, 2 * dim, dtype=torch_dtype, device=device)})  # AdaLayerNormContinuous
+        self.norm_out = blocks.AdaLNContinuous(dim, torch_dtype, device)
         self.proj_out = nn.Linear(dim, get("patch_size") ** 2 * get("out_channels"), dtype=torch_dtype, device=device)
         if hasattr(self, "pos_embed"):
             self.pos_embed = nn.Identity()  # rotary tables: qwen_rope_freqs (restated QwenEmbedRope)
@@ -448,33 +398,8 @@ class NunchakuQwenImageTransformer2DModel(_DiffusersQwen if HAVE_DIFFUSERS_QWEN 
 
     @torch.no_grad()
     def init_synthetic_(self, seed: int = 0, codes: str = "uniform"):
-        """Random-init weights of the Qwen-Image shape (no checkpoints in this environment), written in the checkpoint layout
-        (``codes``: models/linear.py ``synthetic_codes_``)."""
-        dev = self.proj_out.weight.device
-        g = torch.Generator(device=dev).manual_seed(seed)
-        for m in self.modules():
-            if isinstance(m, SVDQW4A4Linear):
-                K = m.in_features
-                synthetic_codes_(m.qweight, m.wscales, K, g, codes)
-                if m.bias is not None:
-                    m.bias.copy_(torch.randn(m.bias.shape, generator=g, device=dev) * 0.02)
-                m.smooth_factor.copy_(torch.rand((K,), generator=g, device=dev) + 0.5)
-                m.smooth_factor_orig.copy_(m.smooth_factor)
-                m.proj_down.copy_(torch.randn(m.proj_down.shape, generator=g, device=dev) * (0.5 / math.sqrt(K)))
-                m.proj_up.copy_(torch.randn(m.proj_up.shape, generator=g, device=dev) * (0.5 / math.sqrt(m.rank)))
-                m._amd_layout = False
-            elif isinstance(m, AWQW4A16Linear):
-                sc = 1.0 / (4.6 * math.sqrt(m.in_features))
-                m.qweight.copy_(torch.randint(-2 ** 31, 2 ** 31, m.qweight.shape, generator=g, device=dev, dtype=torch.int64))
-                m.wscales.copy_((torch.rand(m.wscales.shape, generator=g, device=dev) * 0.5 + 0.75) * sc)
-                m.wzeros.copy_(m.wscales.float() * -7.5)
-                m.bias.zero_()
-            elif isinstance(m, nn.Linear):
-                m.weight.copy_(torch.randn(m.weight.shape, generator=g, device=dev) / math.sqrt(m.in_features))
-                m.bias.zero_()
-            elif isinstance(m, nn.RMSNorm):
-                m.weight.fill_(1.0)
-        return self
+        """Random-init weights of the Qwen-Image shape, left in the checkpoint layout (models/blocks.py ``init_synthetic_``)."""
+        return blocks.init_synthetic_(self, seed, codes, linear_divides=True)
 
     def forward(self, hidden_states, encoder_hidden_states=None, encoder_hidden_states_mask=None, timestep=None, img_shapes=None,
                 txt_seq_lens=None, guidance=None, attention_kwargs=None, controlnet_block_samples=None, return_dict: bool = True):
@@ -516,7 +441,7 @@ class NunchakuQwenImageTransformer2DModel(_DiffusersQwen if HAVE_DIFFUSERS_QWEN 
         stats = mods = temb_act = None
         if fused:
             temb_act = F.silu(temb)  # img_mod[0] / txt_mod[0] of every block: the same SiLU of the same embedding
-            stats = ((residual_gate_stats(enc)[1], None), residual_gate_stats(hidden)[1])
+            stats = ((residual_gate_stats(hidden)[1], None), (residual_gate_stats(enc)[1], None))  # (image, text), each with its ZeroPool
             if not self.offload and self.batched_mods:
                 # all 2 x num_layers modulation projections depend on temb only: ONE batched GEMV launch, +1 on the scale rows in two ops
                 lins = [SimpleNamespace(qweight=l.qweight, wscales=l.wscales, wzeros=l.wzeros, bias=l.bias, out_features=l.out_features,
@@ -537,20 +462,13 @@ class NunchakuQwenImageTransformer2DModel(_DiffusersQwen if HAVE_DIFFUSERS_QWEN 
                 enc, hidden = block(hidden_states=hidden, encoder_hidden_states=enc, encoder_hidden_states_mask=encoder_hidden_states_mask,
                                     temb=temb, image_rotary_emb=rot, joint_attention_kwargs=attention_kwargs, kv_valid=kv_valid)
             if controlnet_block_samples is not None:
-                # the reference's (= diffusers') choice of the residual behind block i (transformer_qwenimage.py:546-550): one 16-bit add on the image
-                # stream; the fused path needs the LayerNorm statistics of the sum -- the same pass.  Padded image rows get a zero residual.
-                smp = controlnet_block_samples[i // -(-len(self.transformer_blocks) // len(controlnet_block_samples))].to(hidden.dtype)
-                if smp.shape[1] != hidden.shape[1]:
-                    smp = F.pad(smp, (0, 0, 0, hidden.shape[1] - smp.shape[1]))
-                hidden, h_stats = residual_gate_stats(hidden, smp.contiguous(), want_stats=fused)
+                # the reference's (= diffusers') choice of the residual behind block i (transformer_qwenimage.py:546-550)
+                hidden, h_stats = blocks.add_control(hidden, controlnet_block_samples, i, len(self.transformer_blocks), want_stats=fused)
                 if fused:
-                    stats = (stats[0], h_stats)
+                    stats = ((h_stats, stats[0][1]), stats[1])
             if self.offload:
                 self.offload_manager.step(compute_stream)
-        hidden = hidden[:, :t_img]
-        scale, shift = self.norm_out["linear"](F.silu(temb)).chunk(2, dim=-1)  # AdaLayerNormContinuous
-        hidden = F.layer_norm(hidden, (self.inner_dim,), eps=1e-6) * (1 + scale[:, None]) + shift[:, None]
-        out = self.proj_out(hidden)
+        out = self.proj_out(self.norm_out(hidden[:, :t_img], F.silu(temb)))
         if not return_dict:
             return (out,)
         from .transformer_flux import Transformer2DModelOutput

@@ -26,6 +26,11 @@ class ZeroPool:
         return piece
 
 
+def ln_pool(ln):
+    """The :class:`ZeroPool` an ``ln`` tuple carries -- ``(stats, scale, shift[, pool])`` -- or None (no tuple, no 4th element)."""
+    return ln[3] if ln is not None and len(ln) > 3 else None
+
+
 def residual_gate_stats(res: torch.Tensor, a: torch.Tensor | None = None, gate: torch.Tensor | None = None,
                         b: torch.Tensor | None = None, inplace: bool = True, want_stats: bool = True, eps: float = 1e-6,
                         zero_floats: int = 0, clamp_fp16: bool = False):

@@ -6,6 +6,7 @@ import torch
 
 from ..mode import alloc_lora_act
 from ..utils import ceil_divide
+from .elementwise import ln_pool
 from .gemm import svdq_gemm_w4a4_cuda
 
 
@@ -22,7 +23,7 @@ def fused_gelu_mlp(x: torch.Tensor, fc1, fc2, pad_size: int = 256, ln=None, quan
     dev = x.device
     q_hidden = torch.empty(M_pad, fc1.out_features * 3 // 4, dtype=torch.uint8, device=dev)  # FP6 operand image
     s_hidden = torch.empty(fc1.out_features // 64, M_pad, dtype=x.dtype, device=dev)
-    pool = ln[3] if ln is not None and len(ln) > 3 else None  # scratch cleared by the preceding element-wise pass
+    pool = ln_pool(ln)  # scratch cleared by the preceding element-wise pass
     l_hidden, l_zeroed = alloc_lora_act(M_pad, fc2.proj_down.shape[1], dev, pool)
     fc1._ensure_layout()
     fc2._ensure_layout()
@@ -147,7 +148,7 @@ def fused_gelu_mlp_pair(xa, fc1a, fc2a, xb, fc1b, fc2b, ln_a=None, ln_b=None):
     """``(fc2a(gelu(fc1a(xa))), fc2b(gelu(fc1b(xb))))`` with two GEMM launches instead of four."""
     if not (_pair_ok(fc1a, fc1b, xa, xb) and _pair_ok(fc2a, fc2b, xa, xb)):
         return fused_gelu_mlp(xa, fc1a, fc2a, ln=ln_a), fused_gelu_mlp(xb, fc1b, fc2b, ln=ln_b)
-    pool = ln_a[3] if ln_a is not None and len(ln_a) > 3 else None  # stream a's pool must hold both streams' scratch
+    pool = ln_pool(ln_a)  # stream a's pool must hold both streams' scratch
     act, asc, lact, Ma = _quantize_pair(xa, fc1a, xb, fc1b, ln_a, ln_b, pool=pool)
     for m in (fc2a, fc2b):
         m._ensure_layout()
@@ -175,7 +176,7 @@ def fused_qkv_norm_rottary_pair(xa, proj_a, nq_a, nk_a, xb, proj_b, nq_b, nk_b, 
     layers cannot be grouped (nothing has been written)."""
     if not _pair_ok(proj_a, proj_b, xa, xb) or xb.shape[1] % 256:
         return False
-    pool = ln_a[3] if ln_a is not None and len(ln_a) > 3 else None
+    pool = ln_pool(ln_a)
     act, asc, lact, Ma = _quantize_pair(xa, proj_a, xb, proj_b, ln_a, ln_b, pool=pool)
     svdq_gemm_w4a4_cuda(
         act=act, wgt=proj_a.qweight, out=output, ascales=asc, wscales=proj_a.wscales, lora_act_in=lact, lora_up=proj_a.proj_up,
@@ -195,7 +196,7 @@ def quantize_two(x, lin_a, lin_b, ln=None):
     lin_a._ensure_layout()
     lin_b._ensure_layout()
     R, dev = lin_a.rank, x.device
-    pool = ln[3] if ln is not None and len(ln) > 3 else None
+    pool = ln_pool(ln)
     act = torch.empty(2 * M, K * 3 // 4, dtype=torch.uint8, device=dev)
     asc = torch.empty(K // 64, 2 * M, dtype=x.dtype, device=dev)
     lact, zeroed = alloc_lora_act(2 * M, R, dev, pool)

@@ -7,6 +7,7 @@ import torch
 from .._C import ops
 from ..mode import alloc_lora_act
 from ..utils import ceil_divide
+from .elementwise import ln_pool
 
 
 def svdq_quantize_w4a4_act_fuse_lora_cuda(
@@ -52,7 +53,7 @@ def svdq_quantize_w4a4_act_fuse_lora_cuda(
     if lora_act_out is None:
         # a 4th element of ``ln`` is a ZeroPool of fp32 scratch cleared by the preceding residual_gate_stats pass
         if pool is None:
-            pool = ln[3] if ln is not None and len(ln) > 3 else None
+            pool = ln_pool(ln)
         lora_act_out, zeroed = alloc_lora_act(M_pad, R, dev, pool)  # fp32, or int64 fixed point in deterministic mode
     if ln is None:
         ops.quantize_w4a4_act_fuse_lora(input, output, oscales, lora_down, lora_act_out, smooth, fuse_glu, fp4,
