@@ -494,6 +494,39 @@ typedef struct svdq_modulated_diff_args {
 int svdq_modulated_diff(const svdq_modulated_diff_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Image-prompt cross-attention (IP-Adapter; added WITHOUT a version bump: one new symbol, nothing existing changes, so
+ * SVDQ_ABI_VERSION stays 24.  reference: nunchaku/models/ip_adapter/utils.py:346-372 -- a contiguous copy of Q, three
+ * view-transposes, SDPA, a transpose-reshape copy and the multiply of the scaled add, torch ops there):
+ *   out[t, h, :] = round16( out_scale * round16( softmax_n(scale * q[t, h, :] . k[n, h, :]) . v[n, h, :] ) )
+ * for t in [0, T), h in [0, H), n in [0, N), head dimension 128, no mask.  q is read in place (row stride ldq: the Q third of a packed
+ * [T, 3 * H * 128] QKV buffer needs no copy); k and v are [N, H * 128] row-major with their own row strides -- what the adapter's
+ * nn.Linear projections wrote; there is no transposed side input.  1 <= N <= 256 (K and V of one head stay in LDS; more keys:
+ * SVDQ_E_UNSUPPORTED); any T >= 1, H >= 1.  Rows of k / v at or beyond N and rows of q / out at or beyond T are neither read nor
+ * written.  q_prescaled: q already carries scale * log2(e) (svdq_gemm_args.q_scale) and `scale` is not applied again.
+ * All scores of a row are formed before the softmax (one pass: max, exp2, sum); the probabilities are rounded to 16 bits before they
+ * meet V and the row sum is taken over the rounded values, as in svdq_attention.  out_scale multiplies in fp32 (a 16-bit tensor times
+ * a Python float in the reference: the scale itself is NOT rounded to 16 bits); out_scale == 1 yields round16(o).  The residual add of
+ * the adapter is not part of this kernel: it is one svdq_residual_gate_stats pass (res + a, no gate), which also delivers the next
+ * block's LayerNorm statistics.  No atomics, no workspace: two launches on the same inputs are bit-identical.
+ * Validation (no launch): NULL pointers, N outside 1..256, T or H < 1, a row stride smaller than H * 128, pointers not 16-byte
+ * aligned or strides not a multiple of 8 elements, unknown dtype, head_dim != 128 (SVDQ_E_UNSUPPORTED).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct svdq_ip_attention_args {
+    const void *q;   /* [T, H, 128] 16-bit, row stride ldq */
+    const void *k;   /* [N, H * 128], row stride ldk */
+    const void *v;   /* [N, H * 128], row stride ldv */
+    void *out;       /* [T, H * 128], row stride ldo */
+    int32_t ldq, ldk, ldv, ldo; /* in elements */
+    int32_t T, H, N, head_dim;
+    int32_t dtype;
+    int32_t q_prescaled;
+    float scale;     /* softmax scale (1 / sqrt(128) in the adapter); ignored with q_prescaled */
+    float out_scale; /* fp32 */
+} svdq_ip_attention_args;
+
+int svdq_ip_attention(const svdq_ip_attention_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * AWQ W4A16 GEMV (reference: ops.gemv_awq, nunchaku/csrc/ops.h:123-145 -> src/kernels/awq/gemv_awq.cu:100-286;
  * module nunchaku/models/linear.py:277-414).  The AdaLayerNormZero modulation projections of every block.
  *   out[m, n] = round16( sum_k round16( round16(q[n,k]*scales[k/64,n] + zeros[k/64,n]) * x[m,k] ) ) (+ bias[n])

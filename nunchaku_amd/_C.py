@@ -962,6 +962,35 @@ class _Ops:
         _lib.check(lib.svdq_attention(C.byref(a), _stream()), "attention")
 
 
+    @staticmethod
+    def ip_attention(q, k, v, out, scale, out_scale=1.0, q_prescaled=False):
+        """Extension (IP-Adapter): ``out = round16(out_scale * round16(softmax(scale * q k^T) v))`` per head, head_dim 128, no mask
+        (``svdq_ip_attention``).  ``q`` / ``out``: ``[T, H, 128]`` views with any row stride (the Q third of a packed QKV buffer is read in
+        place), heads 128 elements apart; ``k`` / ``v``: ``[N, H * 128]`` row-major views with their own row strides, ``1 <= N <= 256``.
+        ``out_scale`` multiplies in fp32.  ``q_prescaled``: ``q`` already carries ``scale * log2(e)``."""
+        lib = _lib.load()
+        for name, t in (("q", q), ("out", out)):
+            if t is None or t.dim() != 3 or t.stride(2) != 1 or (t.shape[1] > 1 and t.stride(1) != t.shape[2]):
+                raise ValueError(f"ip_attention: {name} must be a [T, H, D] view with unit channel stride and heads D elements apart")
+        for name, t in (("k", k), ("v", v)):
+            if t is None or t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"ip_attention: {name} must be a [N, H * D] view with unit column stride")
+        if q.dtype not in _DT or k.dtype != q.dtype or v.dtype != q.dtype or out.dtype != q.dtype:
+            raise ValueError("ip_attention: q, k, v, out must share one 16-bit dtype")
+        T, H, D = q.shape
+        if tuple(out.shape) != (T, H, D) or k.shape[1] != H * D or tuple(v.shape) != tuple(k.shape):
+            raise ValueError("ip_attention: expected q/out [T, H, D] and k/v [N, H * D]")
+        for t in (q, k, v, out):
+            if not t.is_cuda:
+                raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
+        a = _lib.IpAttentionArgs()
+        a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+        a.ldq, a.ldk, a.ldv, a.ldo = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
+        a.T, a.H, a.N, a.head_dim, a.dtype = T, H, k.shape[0], D, _DT[q.dtype]
+        a.q_prescaled, a.scale, a.out_scale = 1 if q_prescaled else 0, float(scale), float(out_scale)
+        _lib.check(lib.svdq_ip_attention(C.byref(a), _stream()), "ip_attention")
+
+
 class _Utils:
     """reference: csrc/pybind.cpp:118-123 -- logging / sm_75 toggles; no-ops here."""
 

@@ -63,6 +63,15 @@ class ModulatedDiffArgs(C.Structure):
     ]
 
 
+class IpAttentionArgs(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("out", C.c_void_p),
+        ("ldq", C.c_int32), ("ldk", C.c_int32), ("ldv", C.c_int32), ("ldo", C.c_int32),
+        ("T", C.c_int32), ("H", C.c_int32), ("N", C.c_int32), ("head_dim", C.c_int32),
+        ("dtype", C.c_int32), ("q_prescaled", C.c_int32), ("scale", C.c_float), ("out_scale", C.c_float),
+    ]
+
+
 class GemmArgs(C.Structure):
     _fields_ = [
         ("act", C.c_void_p), ("wgt", C.c_void_p), ("ascales", C.c_void_p), ("wscales", C.c_void_p),
@@ -138,6 +147,7 @@ EXPORTS = {
     "svdq_residual_gate_stats": (C.c_int, [C.POINTER(ResidualArgs), C.c_void_p]),
     "svdq_residual_diff": (C.c_int, [C.POINTER(ResidualDiffArgs), C.c_void_p]),
     "svdq_modulated_diff": (C.c_int, [C.POINTER(ModulatedDiffArgs), C.c_void_p]),
+    "svdq_ip_attention": (C.c_int, [C.POINTER(IpAttentionArgs), C.c_void_p]),
     "svdq_gemm_workspace_bytes": (C.c_int64, []),
     "svdq_gemm_workspace_bytes_for": (C.c_int64, [C.POINTER(GemmArgs)]),
     "svdq_gemm_workspace_status": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -29,7 +29,8 @@ def cached_forward_v2(self, hidden_states, encoder_hidden_states=None, pooled_pr
                                      use_double_fb_cache=self.use_double_fb_cache,
                                      residual_diff_threshold_multi=self.residual_diff_threshold_multi,
                                      residual_diff_threshold_single=self.residual_diff_threshold_single,
-                                     verbose=getattr(self, "verbose", False))
+                                     verbose=getattr(self, "verbose", False),
+                                     ip_hidden_states=(joint_attention_kwargs or {}).get("ip_hidden_states"))
     if not _pipeline_signature(self):
         return out
     from ...models.transformer_flux import Transformer2DModelOutput

@@ -134,6 +134,8 @@ class TeaCache:
                                "(switch First-Block Cache off: residual_diff_threshold_multi < 0)")
         if getattr(model, "offload", False):
             raise NotImplementedError("TeaCache does not support an offloaded model")
+        if getattr(model, "ip_adapter", None) is not None:
+            raise NotImplementedError("TeaCache with an IP-Adapter attached is not supported (the reference has no such combination)")
         if any(hasattr(model, name) for name in STATE):
             raise RuntimeError("TeaCache: this model is already inside a TeaCache context")
         # the instance attribute, if there is one, comes back on exit; a forward found on the class is uncovered again by deleting ours

@@ -23,7 +23,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ..ops.attention import attention_packed, attention_packed_quantized, kv_valid_ranges, q_prescale
+from ..ops.attention import attention_packed, attention_packed_quantized, ip_attention, kv_valid_ranges, q_prescale
 from ..ops.elementwise import ln_pool, modulated_diff, modulated_diff_scratch, residual_add_pair, residual_diff, residual_gate_stats
 from ..ops.gemv import awq_gemv_w4a16_batched
 from ..ops.fused import fused_gelu_mlp, fused_qkv_norm_rottary, fused_qkv_norm_rottary_pair, linear_pair, quantize_two
@@ -430,13 +430,17 @@ class FluxEngineMixin:
         return blocks.init_synthetic_(self, seed, codes, repack=repack, awq_scale_one=True)
 
     def engine_forward(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids,
-                       guidance=None, controlnet_block_samples=None, controlnet_single_block_samples=None, controlnet_blocks_repeat=False):
+                       guidance=None, controlnet_block_samples=None, controlnet_single_block_samples=None, controlnet_blocks_repeat=False,
+                       *, ip_hidden_states=None):
         """hidden_states [1, T_img, 64]; encoder_hidden_states [1, T_txt, 4096]; pooled [1, 768];
         timestep/guidance [1]; img_ids [T_img, 3]; txt_ids [T_txt, 3]  ->  [1, T_img, 64]
         (transformer_flux_v2.py:430-561; batch 1 -- the fused QKV epilogue takes one rotary table).
         ``controlnet_block_samples`` / ``controlnet_single_block_samples``: lists of ``[1, T_img, dim]`` residuals added to the image
         stream behind the joint / single blocks with diffusers' indexing (``FluxTransformer2DModel.forward``: sample
         ``i // ceil(blocks / samples)``, or ``i % samples`` with ``controlnet_blocks_repeat``).
+        ``ip_hidden_states``: the image embeddings of an attached IP-Adapter (``models/ip_adapter.py``) -- a tensor whose last axis is the
+        adapter's ``cross_dim`` and whose other axes are all image-prompt tokens, or the pipeline's list (element 0); None: the stored
+        ``image_embeds``.  Ignored without an adapter; an adapter without any embeddings raises ``ValueError``.
         The step is its stages run back to back (``_prologue``, ``_run_joint``, ``_join``, ``_run_single``, ``_tail``);
         :meth:`engine_forward_cached` is the same stages with the First-Block-Cache decision in between."""
         if hidden_states.shape[0] > 1:
@@ -447,12 +451,16 @@ class FluxEngineMixin:
                 return t[i:i + 1] if t is not None and t.dim() > 0 and t.shape[0] == hidden_states.shape[0] else t
             def per_list(ts, i):
                 return None if ts is None else [per(t, i) for t in ts]
+            def per_ip(i):  # the embeddings of sample i when they carry a batch axis of this batch's size ([B, tokens, cross_dim] or more axes)
+                t = ip_hidden_states[0] if isinstance(ip_hidden_states, (list, tuple)) and len(ip_hidden_states) else ip_hidden_states
+                return t[i:i + 1] if torch.is_tensor(t) and t.dim() >= 3 and t.shape[0] == hidden_states.shape[0] else t
             return torch.cat([self.engine_forward(hidden_states[i:i + 1], encoder_hidden_states[i:i + 1], pooled_projections[i:i + 1],
                                            per(timestep, i), img_ids, txt_ids, per(guidance, i), per_list(controlnet_block_samples, i),
-                                           per_list(controlnet_single_block_samples, i), controlnet_blocks_repeat)
+                                           per_list(controlnet_single_block_samples, i), controlnet_blocks_repeat,
+                                           ip_hidden_states=per_ip(i))
                               for i in range(hidden_states.shape[0])], dim=0)
         st = self._prologue(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance,
-                            controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat)
+                            controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat, ip_hidden_states=ip_hidden_states)
         # every modulation projection depends on the timestep embedding only: one batched GEMV launch for the whole step
         self._launch_mods(st, range(len(self.blocks)), range(len(self.single_blocks)))
         self._run_joint(st, 0, len(self.blocks))
@@ -461,9 +469,13 @@ class FluxEngineMixin:
         return self._tail(st)
 
     def _prologue(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance=None,
-                  controlnet_block_samples=None, controlnet_single_block_samples=None, controlnet_blocks_repeat=False) -> "_Step":
-        """Embedders, rotary tables, padding of the two streams and their first LayerNorm statistics."""
+                  controlnet_block_samples=None, controlnet_single_block_samples=None, controlnet_blocks_repeat=False, *,
+                  ip_hidden_states=None) -> "_Step":
+        """Embedders, rotary tables, padding of the two streams and their first LayerNorm statistics; with an IP-Adapter attached, the
+        image-prompt K / V of every joint block (projected once per embeddings tensor: ``IPAdapter.kv``)."""
         dt = self.dtype_
+        adapter = getattr(self, "ip_adapter", None)
+        ip_kv = None if adapter is None else adapter.kv(adapter.resolve(ip_hidden_states))  # (raises before anything is launched)
         hidden = self.x_embedder(hidden_states)
         # diffusers casts timestep / guidance to the model dtype BEFORE the x1000 (transformer_flux.py: timestep.to(dtype) * 1000)
         temb = self.time_embed(timestep_embedding(timestep.to(dt) * 1000).to(dt))
@@ -514,6 +526,7 @@ class FluxEngineMixin:
         st.t_txt, st.t_img, st.p_txt, st.joined, st.mods = t_txt, t_img, p_txt, False, {}
         st.cn_joint, st.cn_single, st.cn_repeat = controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat
         st.fused = self.fused_norm and hidden.shape[0] == 1
+        st.ip = None if adapter is None else (ip_kv, adapter.ip_adapter_scale)
         st.stats = ((residual_gate_stats(hidden)[1], None), (residual_gate_stats(enc)[1], None)) if st.fused else None
         return st
 
@@ -538,10 +551,58 @@ class FluxEngineMixin:
         for i in range(lo, hi):
             st.enc, st.hidden, st.stats = self.blocks[i](st.hidden, st.enc, st.temb_act, st.rot, st.stats, mods=st.mods.get(("j", i)),
                                                          kv_valid=st.kv_valid, keep_input=keep_input and i == lo)
+            ip_q = self._ip_query(st, i) if st.ip is not None else None  # of the block's output, BEFORE the ControlNet residual (the reference's order)
             if st.cn_joint is not None:
                 st.hidden, h_stats = blocks.add_control(st.hidden, st.cn_joint, i, nj, st.cn_repeat, want_stats=st.fused)
                 if st.fused:
                     st.stats = ((h_stats, st.stats[0][1]), st.stats[1])
+            if st.ip is not None:
+                self._ip_add(st, i, ip_q)
+
+    def _ip_fused(self, st: "_Step", attn) -> bool:
+        """the adapter's step runs on this library's kernels (else: the reference's torch-op sequence)"""
+        return st.fused and attn.attention_impl == "svdq" and attn.head_dim == 128
+
+    def _ip_query(self, st: "_Step", i: int) -> torch.Tensor:
+        """The IP-Adapter query of joint block ``i`` (reference: FluxModel.cpp ``get_q_heads``): NOT the Q its attention used but the
+        block's OUTPUT image stream through this block's ``norm1`` modulation (shift_msa / scale_msa), ``to_qkv``, ``norm_q`` and RoPE
+        with the image table -- a second QKV projection per joint block, kept because it is the reference's arithmetic.  Returns the
+        packed ``[tokens, 3 * dim]`` projection output; its Q third is the query (prescaled by ``q_prescale`` on the fused arm)."""
+        blk = self.blocks[i]
+        attn = blk.attn
+        hidden = st.hidden
+        if self._ip_fused(st, attn):
+            mods = st.mods.get(("j", i))
+            shift_msa, scale_msa = (mods[0] if mods is not None else blk.mod(st.temb_act)).view(6, -1)[:2]
+            # LayerNorm + modulation inside the quantiser, from the statistics that came out of the block's last residual pass.  No
+            # ZeroPool in this tuple: the pools in st.stats belong to the NEXT block's launches; this quantiser clears its own accumulator.
+            ln = (st.stats[0][0], scale_msa, shift_msa)
+            return fused_qkv_norm_rottary(hidden, attn.to_qkv, attn.norm_q, attn.norm_k, st.rot[0], ln=ln,
+                                          q_scale=q_prescale(attn.head_dim))[0]
+        m = blk.mod(st.temb_act).view(st.temb_act.shape[0], 6, -1).permute(1, 0, 2)
+        return fused_qkv_norm_rottary(blk._ln_mod(hidden, m[1], m[0]), attn.to_qkv, attn.norm_q, attn.norm_k, st.rot[0])[0]
+
+    def _ip_add(self, st: "_Step", i: int, qkv: torch.Tensor) -> None:
+        """``hidden += ip_adapter_scale * SDPA(ip_query, k_img, v_img)`` behind joint block ``i`` (reference: ip_adapter/utils.py:361-372).
+        Fused arm: one ``svdq_ip_attention`` launch on the packed buffer (the strength multiplies in fp32 inside it, as torch's
+        ``float * tensor``), then ONE ``svdq_residual_gate_stats`` pass that adds it and delivers the statistics the next block's
+        quantisers need -- the image stream must not change behind the pass that produced its statistics.  Padded image rows take part
+        like any row: tokens nobody reads."""
+        kv, scale = st.ip
+        k_img, v_img = kv[i]
+        attn = self.blocks[i].attn
+        if self._ip_fused(st, attn):
+            o = ip_attention(qkv, k_img, v_img, attn.heads, out_scale=scale, q_prescaled=True)
+            st.hidden, h_stats = residual_gate_stats(st.hidden, o.view(st.hidden.shape))
+            st.stats = ((h_stats, st.stats[0][1]), st.stats[1])
+            return
+        dim = attn.heads * attn.head_dim
+        shp = (1, -1, attn.heads, attn.head_dim)
+        o = F.scaled_dot_product_attention(qkv[:, :dim].contiguous().view(shp).transpose(1, 2), k_img.view(shp).transpose(1, 2),
+                                           v_img.view(shp).transpose(1, 2), attn_mask=None, dropout_p=0.0, is_causal=False)
+        st.hidden = st.hidden + scale * o.transpose(1, 2).reshape(1, -1, dim)
+        if st.fused:  # (fused blocks around a torch-op adapter step: attention impl "sdpa" or a head dim other than 128)
+            st.stats = ((residual_gate_stats(st.hidden)[1], st.stats[0][1]), st.stats[1])
 
     def _join(self, st: "_Step") -> None:
         """[text | image] for the single blocks; the statistics in the same row order."""
@@ -584,7 +645,7 @@ class FluxEngineMixin:
     def engine_forward_cached(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance=None,
                               controlnet_block_samples=None, controlnet_single_block_samples=None, *, use_double_fb_cache: bool = False,
                               residual_diff_threshold_multi: float = 0.12, residual_diff_threshold_single: float = -1.0,
-                              verbose: bool = False):
+                              verbose: bool = False, ip_hidden_states=None):
         """One denoising step with First-Block Cache (reference: caching/utils_v2.py ``cached_forward_v2``): the stages of
         :meth:`engine_forward` with the decision of ``caching.fbcache.check_and_apply_cache`` in between.
 
@@ -596,7 +657,11 @@ class FluxEngineMixin:
 
         Needs an active ``fbcache.cache_context``.  The decision is read on the host, which synchronises the stream.  Refused with an
         error: a stream under capture (``graph.CapturedStep``), batch > 1 (the uncached forward loops over the samples; one cache context
-        holds one sample's residuals) and ControlNet residuals (the reference's cached forward drops them silently)."""
+        holds one sample's residuals) and ControlNet residuals (the reference's cached forward drops them silently).
+
+        With an IP-Adapter attached (``ip_hidden_states`` as in :meth:`engine_forward`) the adapter's step runs behind every joint block
+        that runs: block 0's residual -- what the decision compares -- includes the adapter's contribution, as in the reference's
+        ``IPA_TransformerBlocks``, and a hit launches no image-prompt attention beyond block 0's."""
         from ..caching import fbcache
 
         if hidden_states.is_cuda and torch.cuda.is_current_stream_capturing():
@@ -613,7 +678,8 @@ class FluxEngineMixin:
             raise ValueError("First-Block Cache needs at least one joint block")
         double = bool(use_double_fb_cache) and ns > 0
 
-        st = self._prologue(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance)
+        st = self._prologue(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance,
+                            ip_hidden_states=ip_hidden_states)
         t_txt, t_img, p_txt = st.t_txt, st.t_img, st.p_txt
         self._launch_mods(st, range(0, 1), range(0, 1) if double else range(0))  # of the blocks that run whatever the decision
         h0 = st.hidden
@@ -688,7 +754,10 @@ class FluxEngineMixin:
         hidden_after_embed`` (image rows; one ``svdq_residual_diff`` subtraction into the kept buffer).
 
         Refused with an error: a stream under capture, batch > 1, ControlNet residuals, a model with First-Block Cache switched on, an
-        offloaded model."""
+        offloaded model, a model with an IP-Adapter attached."""
+        if getattr(self, "ip_adapter", None) is not None:
+            raise NotImplementedError("TeaCache with an IP-Adapter attached is not supported (the reference has no such combination): "
+                                      "detach the adapter (undo_all_mods_on_transformer) or use First-Block Cache")
         if hidden_states.is_cuda and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("TeaCache reads its decision on the host, which synchronises the stream: a cached forward cannot be "
                                "captured into a graph (run the uncached forward under capture: TeaCache(..., enabled=False))")
@@ -752,7 +821,7 @@ class _Step:
     ``[text | image]`` stream once ``joined``), the LayerNorm statistics that travel with them on the fused path, and the step's constants."""
 
     __slots__ = ("hidden", "enc", "stats", "temb_act", "rot", "kv_valid", "t_txt", "t_img", "p_txt", "fused", "mods", "joined",
-                 "cn_joint", "cn_single", "cn_repeat")
+                 "cn_joint", "cn_single", "cn_repeat", "ip")
 
 
 class FluxTransformerAMD(nn.Module, FluxEngineMixin):

@@ -193,8 +193,10 @@ class NunchakuFluxTransformer2DModelV2(_Base, FluxEngineMixin, NunchakuModelLoad
             raise ValueError("this checkpoint has guidance embeddings: pass guidance")
         # ControlNet residuals: per-block additions to the image stream with diffusers' indexing (the reference's V2 forward raises here,
         # transformer_flux_v2.py:537-552; its legacy model and diffusers' FluxTransformer2DModel accept them)
+        # an attached IP-Adapter takes its image embeddings from the pipeline's joint_attention_kwargs, else the stored ones
         out = self.engine_forward(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance,
-                                  controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat)
+                                  controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat,
+                                  ip_hidden_states=(joint_attention_kwargs or {}).get("ip_hidden_states"))
         return Transformer2DModelOutput(sample=out) if return_dict else (out,)
 
 

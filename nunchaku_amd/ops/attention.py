@@ -97,3 +97,22 @@ def attention_packed_quantized(qkv: torch.Tensor, vt: torch.Tensor, heads: int, 
     ops.attention(q, k, vt.unflatten(0, (heads, D)), None, 1.0 / math.sqrt(D) if scale is None else scale, None, quant, q_prescaled=q_prescaled,
                   kv_valid=kv_valid)
     return act, asc, lact
+
+
+def ip_attention(qkv_or_q: torch.Tensor, k_ip: torch.Tensor, v_ip: torch.Tensor, heads: int, out: torch.Tensor | None = None,
+                 scale: float | None = None, out_scale: float = 1.0, q_prescaled: bool = False):
+    """Image-prompt cross-attention of IP-Adapter: ``round16(out_scale * round16(softmax(scale * Q K_ip^T) V_ip))`` per head, one launch.
+    ``qkv_or_q``: the packed ``[T, 3*H*128]`` output of a fused QKV GEMM (its Q third is read in place, no copy) or a ``[T, H*128]`` Q;
+    ``k_ip`` / ``v_ip``: ``[N, H*128]`` as the adapter's ``nn.Linear`` projections wrote them, ``1 <= N <= 256``.  ``out_scale`` (the
+    adapter's strength, a Python float) multiplies in fp32 as torch does for ``scale * tensor``.  Returns ``[T, H*128]`` token-major."""
+    T, width = qkv_or_q.shape
+    hd = k_ip.shape[-1]
+    if hd % heads or width not in (hd, 3 * hd):
+        raise ValueError("ip_attention: expected q [T, H*D] or qkv [T, 3*H*D] and k_ip / v_ip [N, H*D]")
+    D = hd // heads
+    if out is None:
+        out = torch.empty(T, hd, dtype=qkv_or_q.dtype, device=qkv_or_q.device)
+    ops.ip_attention(qkv_or_q[:, :hd].unflatten(1, (heads, D)), k_ip.reshape(-1, hd) if k_ip.dim() != 2 else k_ip,
+                     v_ip.reshape(-1, hd) if v_ip.dim() != 2 else v_ip, out.unflatten(1, (heads, D)),
+                     1.0 / math.sqrt(D) if scale is None else scale, out_scale=out_scale, q_prescaled=q_prescaled)
+    return out
