@@ -105,6 +105,6 @@ extern "C" int svdq_modulated_diff(const svdq_modulated_diff_args *a, void *stre
     if (a->dtype != SVDQ_BF16 && a->dtype != SVDQ_FP16) { set_error("svdq_modulated_diff: unknown dtype %d", a->dtype); return SVDQ_E_INVALID; }
     hipStream_t st = (hipStream_t)stream;
     const int rc = a->dtype == SVDQ_BF16 ? launch_modulated_diff<SVDQ_BF16>(a, st) : launch_modulated_diff<SVDQ_FP16>(a, st);
-    if (rc) { set_error("svdq_modulated_diff: C=%d: ceil(C/512) must be one of {1..8, 12, 16, 24, 32}", a->C); return SVDQ_E_INVALID; }
+    if (rc) { set_error("svdq_modulated_diff: C=%d: ceil(C/512) must be one of {1..8, 12, 16, 24, 32}", a->C); return SVDQ_E_UNSUPPORTED; }
     return hip_check(hipGetLastError(), "svdq_modulated_diff launch");
 }

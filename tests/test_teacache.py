@@ -288,7 +288,7 @@ def test_modulated_diff_exported_and_validation_errors_are_returned(built_lib):
     a.stats, a.dtype = 8192, 7
     assert lib.svdq_modulated_diff(C.byref(a), None) == 1 and b"dtype" in lib.svdq_last_error()
     a.dtype, a.C, a.ld = 0, 16384 + 512, 16384 + 512
-    assert lib.svdq_modulated_diff(C.byref(a), None) == 1 and b"ceil(C/512)" in lib.svdq_last_error()
+    assert lib.svdq_modulated_diff(C.byref(a), None) == 2 and b"ceil(C/512)" in lib.svdq_last_error()  # SVDQ_E_UNSUPPORTED, as its two siblings
 
 
 def test_wrapper_refuses_cpu_tensors_and_mismatched_shapes(built_lib):
