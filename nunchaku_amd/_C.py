@@ -24,14 +24,58 @@ from . import mode as _mode
 _DT = {torch.bfloat16: _lib.SVDQ_BF16, torch.float16: _lib.SVDQ_FP16}
 
 
-def _ptr(t: torch.Tensor | None) -> int | None:
+def _ptr(t: torch.Tensor | None, laid_out: bool = False) -> int | None:
+    """``laid_out``: the caller has checked the layout (the row-pass checks below: a row view's row stride may exceed its width)"""
     if t is None:
         return None
     if not t.is_cuda:
         raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
-    if not t.is_contiguous():
+    if not laid_out and not t.is_contiguous():
         raise ValueError("nunchaku_amd ops need contiguous tensors")
     return t.data_ptr()
+
+
+# ---- argument checks of the row passes (residual_gate_stats, residual_diff, modulated_diff; csrc/row_pass.h) ------------------------
+def _row_view(op: str, name: str, t: torch.Tensor) -> tuple:
+    """``(M, C, ld, dtype code)`` of the leading tensor of a row pass.  What these checks let through as None (an optional tensor, or a
+    required one that is missing) the library judges: it knows which tensors an operation needs."""
+    if t.dim() != 2 or t.stride(1) != 1 or t.dtype not in _DT:
+        raise ValueError(f"{op}: {name} must be a 2-D 16-bit view with unit column stride")
+    return t.shape[0], t.shape[1], t.stride(0), _DT[t.dtype]
+
+
+def _same_view(op: str, ref_name: str, ref: torch.Tensor, **tensors) -> None:
+    shape, stride, dtype = ref.shape, ref.stride(), ref.dtype
+    for name, t in tensors.items():
+        if t is not None and (t.shape != shape or t.stride() != stride or t.dtype != dtype):
+            raise ValueError(f"{op}: {name} must match {ref_name} in shape, strides and dtype")
+
+
+def _second_rows(op: str, first: torch.Tensor, lead2: torch.Tensor) -> int:
+    """M2 of a grouped launch: the second problem has its own row count and nothing else of its own"""
+    if lead2.dim() != 2 or lead2.shape[1] != first.shape[1] or lead2.stride() != first.stride() or lead2.dtype != first.dtype:
+        raise ValueError(f"{op}: the second problem must have the width, row stride and dtype of the first")
+    return lead2.shape[0]
+
+
+def _vector(op: str, ref_name: str, ref: torch.Tensor, **tensors) -> None:
+    C, dtype = ref.shape[1], ref.dtype
+    for name, t in tensors.items():
+        if t is not None and (t.numel() != C or t.dtype != dtype or not t.is_contiguous()):
+            raise ValueError(f"{op}: {name} must be a contiguous [C] tensor in the dtype of {ref_name}")
+
+
+def _row_stats(op: str, stats: torch.Tensor | None, rows: int) -> None:
+    if stats is not None and (stats.dtype != torch.float32 or stats.numel() != 2 * rows or not stats.is_contiguous()):
+        raise ValueError(f"{op}: stats must be contiguous float32 [{rows}, 2]")
+
+
+def _decision_scratch(op: str, partials: torch.Tensor | None, result: torch.Tensor | None, rows: int) -> None:
+    """what a decision pass writes besides its output: the rows' partial sums (float32, two per row; a larger scratch will do) and the 32-byte record"""
+    if partials is not None and (partials.dtype != torch.float32 or partials.numel() < 2 * rows or not partials.is_contiguous()):
+        raise ValueError(f"{op}: partials must be contiguous float32 with 2 elements per row")
+    if result is not None and (result.numel() * result.element_size() < C.sizeof(_lib.ResidualDiffResult) or not result.is_contiguous()):
+        raise ValueError(f"{op}: result must be a contiguous buffer of at least 32 bytes")
 
 
 def _stream() -> int:
@@ -625,24 +669,13 @@ class _Ops:
         """Extension: ``out = res + gate * (a [+ b])`` (16-bit torch-op rounding of a block's gated residual)
         and/or the LayerNorm statistics ``stats[m] = (mean, rstd)`` of the result, in one pass.  2-D row-major
         views with a common row stride; ``a`` None = statistics of ``res`` itself; ``out`` may be ``res``."""
-        lib = _lib.load()
-        if res.dim() != 2 or res.stride(1) != 1 or res.dtype not in _DT:
-            raise ValueError("residual_gate_stats: res must be a 2-D 16-bit view with unit column stride")
-        M, Cc = res.shape
-        args = _lib.ResidualArgs()
-        for name, t in (("a", a), ("b", b), ("out", out)):
-            if t is not None and (tuple(t.shape) != (M, Cc) or t.stride() != res.stride() or t.dtype != res.dtype):
-                raise ValueError(f"residual_gate_stats: {name} must match res in shape, strides and dtype")
-        if gate is not None and (gate.numel() != Cc or gate.dtype != res.dtype or not gate.is_contiguous()):
-            raise ValueError("residual_gate_stats: gate must be a contiguous [C] tensor in the dtype of res")
-        if stats is not None and (stats.dtype != torch.float32 or stats.numel() != 2 * M or not stats.is_contiguous()):
-            raise ValueError("residual_gate_stats: stats must be contiguous float32 [M, 2]")
-        for t in (res, a, b, gate, out, stats):
-            if t is not None and not t.is_cuda:
-                raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
-        dp = lambda t: None if t is None else t.data_ptr()
-        args.res, args.a, args.b, args.gate, args.out, args.stats = dp(res), dp(a), dp(b), dp(gate), dp(out), dp(stats)
-        args.M, args.C, args.ld, args.dtype, args.eps = M, Cc, res.stride(0), _DT[res.dtype], float(eps)
+        op, lib, args = "residual_gate_stats", _lib.load(), _lib.ResidualArgs()
+        args.M, args.C, args.ld, args.dtype = _row_view(op, "res", res)
+        _same_view(op, "res", res, a=a, b=b, out=out)
+        _vector(op, "res", res, gate=gate)
+        _row_stats(op, stats, args.M)
+        args.res, args.a, args.b, args.out = _ptr(res, True), _ptr(a, True), _ptr(b, True), _ptr(out, True)
+        args.gate, args.stats, args.eps = _ptr(gate, True), _ptr(stats, True), float(eps)
         args.clamp_fp16 = int(clamp_fp16)  # bit 0 / bit 1: clip the first / second problem's result to +-65504 (fp16 only)
         if zero is not None:  # scratch cleared in the same pass (fp32 low-rank accumulators of the calls that follow)
             if not zero.is_cuda or not zero.is_contiguous() or (zero.numel() * zero.element_size()) % 16:
@@ -650,14 +683,11 @@ class _Ops:
             args.zero_ptr, args.zero_bytes = zero.data_ptr(), zero.numel() * zero.element_size()
         if second is not None:  # (res, a, b, gate, out, stats) of an independent second problem of the same width
             r2, a2, b2, g2, o2, s2 = second
-            if r2.dim() != 2 or r2.shape[1] != Cc or r2.stride() != res.stride() or r2.dtype != res.dtype:
-                raise ValueError("residual_gate_stats: the second problem must have the width, row stride and dtype of the first")
-            for t in (a2, b2, o2):
-                if t is not None and (tuple(t.shape) != tuple(r2.shape) or t.stride() != r2.stride()):
-                    raise ValueError("residual_gate_stats: second problem: a, b, out must match res in shape and strides")
-            args.res2, args.a2, args.b2, args.gate2, args.out2, args.stats2 = dp(r2), dp(a2), dp(b2), dp(g2), dp(o2), dp(s2)
-            args.M2 = r2.shape[0]
-        _lib.check(lib.svdq_residual_gate_stats(C.byref(args), _stream()), "residual_gate_stats")
+            args.M2 = _second_rows(op, res, r2)
+            _same_view(op, "res", r2, **{"second problem: a": a2, "second problem: b": b2, "second problem: out": o2})
+            args.res2, args.a2, args.b2, args.out2 = _ptr(r2, True), _ptr(a2, True), _ptr(b2, True), _ptr(o2, True)
+            args.gate2, args.stats2 = _ptr(g2, True), _ptr(s2, True)
+        _lib.check(lib.svdq_residual_gate_stats(C.byref(args), _stream()), op)
 
     @staticmethod
     def residual_diff(cur, base=None, prev=None, out_res=None, partials=None, result=None, second=None):
@@ -666,38 +696,18 @@ class _Ops:
         record ``result`` (8 x 4 bytes: sum_diff, sum_prev, mean_diff, mean_prev, ratio, rows, -, -).  2-D row-major views with a common
         row stride; ``second`` = ``(cur, base, prev, out_res)`` of a second problem whose terms go into the same sums;
         ``partials``: float32 scratch of 2 x (all rows)."""
-        lib = _lib.load()
-        if cur.dim() != 2 or cur.stride(1) != 1 or cur.dtype not in _DT:
-            raise ValueError("residual_diff: cur must be a 2-D 16-bit view with unit column stride")
-        M, Cc = cur.shape
-        rows = M + (second[0].shape[0] if second is not None else 0)
-
-        def same(t, ref, name):
-            if t is not None and (tuple(t.shape) != tuple(ref.shape) or t.stride() != ref.stride() or t.dtype != ref.dtype):
-                raise ValueError(f"residual_diff: {name} must match cur in shape, strides and dtype")
-
-        for name, t in (("base", base), ("prev", prev), ("out_res", out_res)):
-            same(t, cur, name)
-        if partials is not None and (partials.dtype != torch.float32 or partials.numel() < 2 * rows or not partials.is_contiguous()):
-            raise ValueError("residual_diff: partials must be contiguous float32 with 2 elements per row")
-        if result is not None and (result.numel() * result.element_size() < C.sizeof(_lib.ResidualDiffResult) or not result.is_contiguous()):
-            raise ValueError("residual_diff: result must be a contiguous buffer of at least 32 bytes")
-        tensors = [cur, base, prev, out_res, partials, result] + (list(second) if second is not None else [])
-        for t in tensors:
-            if t is not None and not t.is_cuda:
-                raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
-        dp = lambda t: None if t is None else t.data_ptr()
-        args = _lib.ResidualDiffArgs()
-        args.cur, args.base, args.prev, args.out_res, args.partials, args.result = dp(cur), dp(base), dp(prev), dp(out_res), dp(partials), dp(result)
-        args.M, args.C, args.ld, args.dtype = M, Cc, cur.stride(0), _DT[cur.dtype]
+        op, lib, args = "residual_diff", _lib.load(), _lib.ResidualDiffArgs()
+        args.M, args.C, args.ld, args.dtype = _row_view(op, "cur", cur)
+        _same_view(op, "cur", cur, base=base, prev=prev, out_res=out_res)
         if second is not None:
             c2, b2, p2, o2 = second
-            if c2.dim() != 2 or c2.shape[1] != Cc or c2.stride() != cur.stride() or c2.dtype != cur.dtype:
-                raise ValueError("residual_diff: the second problem must have the width, row stride and dtype of the first")
-            for name, t in (("base", b2), ("prev", p2), ("out_res", o2)):
-                same(t, c2, "second problem: " + name)
-            args.cur2, args.base2, args.prev2, args.out_res2, args.M2 = dp(c2), dp(b2), dp(p2), dp(o2), c2.shape[0]
-        _lib.check(lib.svdq_residual_diff(C.byref(args), _stream()), "residual_diff")
+            args.M2 = _second_rows(op, cur, c2)
+            _same_view(op, "cur", c2, **{"second problem: base": b2, "second problem: prev": p2, "second problem: out_res": o2})
+            args.cur2, args.base2, args.prev2, args.out_res2 = _ptr(c2, True), _ptr(b2, True), _ptr(p2, True), _ptr(o2, True)
+        _decision_scratch(op, partials, result, args.M + args.M2)
+        args.cur, args.base, args.prev, args.out_res = _ptr(cur, True), _ptr(base, True), _ptr(prev, True), _ptr(out_res, True)
+        args.partials, args.result = _ptr(partials, True), _ptr(result, True)
+        _lib.check(lib.svdq_residual_diff(C.byref(args), _stream()), op)
 
     @staticmethod
     def modulated_diff(x, stats, mod_scale, mod_shift, prev=None, out_mod=None, partials=None, result=None):
@@ -705,31 +715,15 @@ class _Ops:
         AdaLayerNormZero front end -- written to ``out_mod`` and, with ``prev``, the fp32 sums of ``|prev - m|`` and ``|prev|`` reduced in a
         fixed order into the device record ``result`` (the layout of :meth:`residual_diff`'s).  2-D row-major views with a common row
         stride; ``out_mod`` may be ``prev``; ``stats``: float32 ``[M, 2]``; ``partials``: float32 scratch of 2 x M."""
-        lib = _lib.load()
-        if x.dim() != 2 or x.stride(1) != 1 or x.dtype not in _DT:
-            raise ValueError("modulated_diff: x must be a 2-D 16-bit view with unit column stride")
-        M, Cc = x.shape
-        for name, t in (("prev", prev), ("out_mod", out_mod)):
-            if t is not None and (tuple(t.shape) != (M, Cc) or t.stride() != x.stride() or t.dtype != x.dtype):
-                raise ValueError(f"modulated_diff: {name} must match x in shape, strides and dtype")
-        for name, t in (("mod_scale", mod_scale), ("mod_shift", mod_shift)):
-            if t is None or t.numel() != Cc or t.dtype != x.dtype or not t.is_contiguous():
-                raise ValueError(f"modulated_diff: {name} must be a contiguous [C] tensor in the dtype of x")
-        if stats is None or stats.dtype != torch.float32 or stats.numel() != 2 * M or not stats.is_contiguous():
-            raise ValueError("modulated_diff: stats must be contiguous float32 [M, 2]")
-        if partials is not None and (partials.dtype != torch.float32 or partials.numel() < 2 * M or not partials.is_contiguous()):
-            raise ValueError("modulated_diff: partials must be contiguous float32 with 2 elements per row")
-        if result is not None and (result.numel() * result.element_size() < C.sizeof(_lib.ResidualDiffResult) or not result.is_contiguous()):
-            raise ValueError("modulated_diff: result must be a contiguous buffer of at least 32 bytes")
-        for t in (x, stats, mod_scale, mod_shift, prev, out_mod, partials, result):
-            if t is not None and not t.is_cuda:
-                raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
-        dp = lambda t: None if t is None else t.data_ptr()
-        args = _lib.ModulatedDiffArgs()
-        args.x, args.stats, args.mod_scale, args.mod_shift = dp(x), dp(stats), dp(mod_scale), dp(mod_shift)
-        args.prev, args.out_mod, args.partials, args.result = dp(prev), dp(out_mod), dp(partials), dp(result)
-        args.M, args.C, args.ld, args.dtype = M, Cc, x.stride(0), _DT[x.dtype]
-        _lib.check(lib.svdq_modulated_diff(C.byref(args), _stream()), "modulated_diff")
+        op, lib, args = "modulated_diff", _lib.load(), _lib.ModulatedDiffArgs()
+        args.M, args.C, args.ld, args.dtype = _row_view(op, "x", x)
+        _same_view(op, "x", x, prev=prev, out_mod=out_mod)
+        _vector(op, "x", x, mod_scale=mod_scale, mod_shift=mod_shift)
+        _row_stats(op, stats, args.M)
+        _decision_scratch(op, partials, result, args.M)
+        args.x, args.prev, args.out_mod, args.stats = _ptr(x, True), _ptr(prev, True), _ptr(out_mod, True), _ptr(stats, True)
+        args.mod_scale, args.mod_shift, args.partials, args.result = _ptr(mod_scale, True), _ptr(mod_shift, True), _ptr(partials, True), _ptr(result, True)
+        _lib.check(lib.svdq_modulated_diff(C.byref(args), _stream()), op)
 
     @staticmethod
     def gemv_awq(in_feats, kernel, scaling_factors, zeros, m, n, k, group_size, bias=None, out_chunks=1):

@@ -232,16 +232,6 @@ struct GemmSchedule {
     }
 };
 
-// ---- the two fp32 sums of a decision pass (residual_diff.hip, modulated_diff.hip) -------------------------------
-// one fixed order for both kernels: every lane has added its own elements in index order; this 6-level butterfly folds the wave
-__device__ __forceinline__ void fold_wave_pair(float &sd, float &sp) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { sd += __shfl_xor(sd, o); sp += __shfl_xor(sp, o); }
-}
-// the finishing stage (residual_diff.hip): one workgroup adds the `rows` pairs of `partials` in a fixed order and fills `result` with the
-// sums, the 16-bit means over rows * C terms and their 16-bit quotient.  dtype: SVDQ_BF16 | SVDQ_FP16 (validated by the caller).
-void launch_diff_reduce(int dtype, const float *partials, int rows, int C, svdq_residual_diff_result *result, hipStream_t st);
-
 // ---- host-side error plumbing --------------------------------------------------------------
 void set_error(const char *fmt, ...);
 int hip_check(hipError_t e, const char *what);

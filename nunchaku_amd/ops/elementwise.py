@@ -114,6 +114,18 @@ class ResidualDiff:
         return self.ratio < threshold  # torch's comparison of a 16-bit tensor with a Python number
 
 
+def _row_views(op: str, ref: torch.Tensor, **tensors) -> list:
+    """The ``[rows, C]`` views of contiguous ``[..., C]`` tensors that hold what ``ref`` holds (None stays None)"""
+    C, views = ref.shape[-1], []
+    for name, t in tensors.items():
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{op}: {name} must be contiguous (row slices of a contiguous tensor are)")
+        if t is not None and (t.shape[-1] != C or t.numel() != ref.numel()):
+            raise ValueError(f"{op}: shapes differ: {name} {tuple(t.shape)} vs {tuple(ref.shape)}")
+        views.append(None if t is None else t.view(-1, C))
+    return views
+
+
 def residual_diff(cur, base=None, prev=None, out=None, want_res: bool | None = None):
     """``r = cur - base`` (``base`` None: ``r = cur``) and, with ``prev``, the relative L1 distance ``mean|prev - r| / mean|prev|`` with
     the rounding points of the reference's 16-bit torch ops (caching/fbcache.py:275-277), in one pass over the tensors.
@@ -130,23 +142,13 @@ def residual_diff(cur, base=None, prev=None, out=None, want_res: bool | None = N
     bases, prevs, outs = (seq(x) if x is not None else [None] * n for x in (base, prev, out))
     if not (len(bases) == len(prevs) == len(outs) == n):
         raise ValueError("residual_diff: base / prev / out must have as many entries as cur")
-    C = curs[0].shape[-1]
     if want_res is None:
         want_res = base is not None
     if want_res and base is None:
         raise ValueError("residual_diff: without a base the residual is cur itself")
     if want_res and out is None:
         outs = [torch.empty(c.shape, dtype=c.dtype, device=c.device) for c in curs]
-    def v(t):
-        if t is not None and not t.is_contiguous():
-            raise ValueError("residual_diff: tensors must be contiguous (row slices of a contiguous tensor are)")
-        return None if t is None else t.view(-1, C)
-
-    probs = [(v(c), v(b), v(p), v(o) if want_res else None) for c, b, p, o in zip(curs, bases, prevs, outs)]
-    for c, b, p, o in probs:
-        for t, s in ((b, c), (p, c), (o, c)):
-            if t is not None and t.shape != s.shape:
-                raise ValueError(f"residual_diff: shapes differ: {tuple(t.shape)} vs {tuple(s.shape)}")
+    probs = [_row_views("residual_diff", c, cur=c, base=b, prev=p, out=o if want_res else None) for c, b, p, o in zip(curs, bases, prevs, outs)]
     rows = sum(p[0].shape[0] for p in probs)
     rec = None
     partials = result = None
@@ -169,21 +171,14 @@ def modulated_diff(x, stats, scale, shift, prev=None, out=None, scratch=None):
     across steps).  ``scratch``: ``(partials, record)`` of an earlier :func:`modulated_diff_scratch` call to reuse instead of allocating (the
     record of the earlier launch must have been read, or be of no interest, by then).  Returns ``(m, ResidualDiff or None)``; ``m`` is ``out``
     when given, else new."""
-    C = x.shape[-1]
     if out is None:
         out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-    for name, t in (("x", x), ("prev", prev), ("out", out)):
-        if t is not None and not t.is_contiguous():
-            raise ValueError(f"modulated_diff: {name} must be contiguous (row slices of a contiguous tensor are)")
-        if t is not None and t.shape != x.shape:
-            raise ValueError(f"modulated_diff: shapes differ: {name} {tuple(t.shape)} vs x {tuple(x.shape)}")
-    x2 = x.view(-1, C)
+    x2, prev2, out2 = _row_views("modulated_diff", x, x=x, prev=prev, out=out)
     rec = partials = result = None
     if prev is not None:
         partials, result = scratch if scratch is not None else modulated_diff_scratch(x2.shape[0], x.device)
         rec = ResidualDiff(result, x.dtype)
-    ops.modulated_diff(x2, stats, scale.reshape(-1), shift.reshape(-1), None if prev is None else prev.view(-1, C), out.view(-1, C),
-                       partials=partials, result=result)
+    ops.modulated_diff(x2, stats, scale.reshape(-1), shift.reshape(-1), prev2, out2, partials=partials, result=result)
     return out, rec
 
 

@@ -100,6 +100,52 @@ def test_validation_errors_are_returned_not_aborted(built_lib):
     assert lib.svdq_repack_lowrank(16, 16, 128, 32, 0, None) == 1  # aliasing
 
 
+# the three one-wave-per-row passes: entry point -> (args struct, a valid set of pointers, the 16-bit pointer to misalign, its outputs, a second problem)
+_ROW_PASSES = {
+    "svdq_residual_gate_stats": (_lib.ResidualArgs, dict(res=4096, a=8192, out=12288, stats=16384), "a", ("out", "stats"), dict(res2=20480, M2=4)),
+    "svdq_residual_diff": (_lib.ResidualDiffArgs, dict(cur=4096, base=8192, out_res=12288), "base", ("out_res",), dict(cur2=20480, M2=4)),
+    "svdq_modulated_diff": (_lib.ModulatedDiffArgs, dict(x=4096, stats=8192, mod_scale=12288, mod_shift=16384, out_mod=20480), "mod_shift",
+                            ("out_mod",), None),
+}
+_ROW_REFUSALS = [  # (changes to a valid call with M = 4, C = ld = 256, bf16; return code; what the message says)
+    (dict(C=12, ld=16), 1, b"multiple of 8"),
+    (dict(ld=256 + 4), 1, b"multiple of 8"),
+    (dict(ld=248), 1, b"ld=248 >= C"),
+    (dict(M=0), 1, b"M=0 > 0"),
+    (dict(misalign=2), 1, b"16-byte aligned"),
+    (dict(dtype=7), 1, b"dtype"),
+    (dict(C=4608, ld=4608), 2, b"ceil(C/512)"),      # classes 9, 17 and 33: no instantiation (SVDQ_E_UNSUPPORTED)
+    (dict(C=8704, ld=8704), 2, b"ceil(C/512)"),
+    (dict(C=16392, ld=16392), 2, b"ceil(C/512)"),
+]
+
+
+@pytest.mark.parametrize("entry", sorted(_ROW_PASSES))
+def test_row_passes_share_their_refusals(built_lib, entry):
+    """csrc/row_pass.h validates for all three: every refusal comes back as a code and a message before anything is launched (no GPU here)"""
+    lib = _lib.load()
+    fn, (cls, ptrs, odd, outputs, second) = getattr(lib, entry), _ROW_PASSES[entry]
+    assert fn(None, None) == 1 and b"NULL" in lib.svdq_last_error()
+
+    def call(**changes):
+        a = cls()
+        for k, v in {**ptrs, "M": 4, "C": 256, "ld": 256, **changes}.items():
+            if k == "misalign":
+                setattr(a, odd, ptrs[odd] + v)
+            else:
+                setattr(a, k, v)
+        return fn(C.byref(a), None), lib.svdq_last_error()
+
+    for changes, code, text in _ROW_REFUSALS:
+        rc, msg = call(**changes)
+        assert rc == code and text in msg and entry.encode() in msg, (entry, changes, rc, msg)
+    rc, msg = call(**{k: None for k in outputs})
+    assert rc == 1 and (b"are required" in msg or b"is required" in msg), (entry, rc, msg)  # nothing to produce
+    if second is not None:  # the second problem lacks what the first one has
+        rc, msg = call(**second)
+        assert rc == 1 and b"must mirror the first" in msg, (entry, rc, msg)
+
+
 def test_python_wrappers_raise_without_gpu(built_lib):
     import torch
 

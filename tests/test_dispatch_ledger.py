@@ -4,9 +4,9 @@ tables of tests/test_gpu_dispatch_classes.py reach.  Whoever adds an instantiati
 one without a case; whoever drops a table row gets one that names the instantiation left unlaunched.
 
 Its limit: it trusts the class rules restated below (``CLASS_RULES``).  If a launcher changes how it maps a shape to an instantiation and
-the rule here is not changed with it, the ledger reports "reached" for a kernel the tables no longer launch.  The launchers'
-switch statements are csrc/residual.hip, residual_diff.hip, modulated_diff.hip (``(C + 511) / 512``), gemv_awq.hip (``M``), gemm_awq.hip
-(``awq_plan``) and ip_attention.hip (``(N + 31) / 32``)."""
+the rule here is not changed with it, the ledger reports "reached" for a kernel the tables no longer launch.  The rules live in
+csrc/row_pass.h (``for_row_class``: ``(C + 511) / 512``, for the three row kernels), gemv_awq.hip (``M``), gemm_awq.hip (``awq_plan``) and
+ip_attention.hip (``(N + 31) / 32``)."""
 import math
 import os
 import re

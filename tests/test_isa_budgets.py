@@ -109,6 +109,24 @@ def test_split_low_rank_down_kernels_fit_two_workgroups_per_cu(built_lib):
         assert r["vgpr_count"] <= 256 and r["group_segment_fixed_size"] <= 40960, (name, r)
 
 
+def test_decision_pass_kernels_keep_eight_waves_per_simd(built_lib):
+    """residual_diff_kernel<DT, NV> and modulated_diff_kernel<DT, NV> (csrc/row_pass.h: one wave per row, nothing of the row kept) hide the HBM latency
+    with occupancy alone: 64 registers is the largest count at which eight waves still fit a SIMD's 512-register file.  No spill, no scratch"""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "tools", "isa_stats.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    from nunchaku_amd import _lib
+
+    for kernel in ("residual_diff_kernel", "modulated_diff_kernel"):
+        res = mod.kernel_resources(_lib.lib_path(), kernel)
+        assert len(res) == 24, sorted(res)  # bf16 / fp16 x the 12 width classes
+        for name, r in res.items():
+            assert r["vgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0, (name, r)
+            assert r["vgpr_count"] <= 64, (name, r)
+
+
 def test_wave_tile_kernel_resources(built_lib):
     """round 6: gemm_w4a4_wt128_kernel<DT> -- loop and plain epilogue generated, one asm statement per whole tile: no scratch (the first build, with a C++ epilogue
     on 128 live accumulators, had 644 B per lane and 1300 AGPR moves per tile), the whole 512-register file of one wave per SIMD, the ring of four stages in LDS;
