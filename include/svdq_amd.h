@@ -50,7 +50,7 @@ enum { SVDQ_BF16 = 0, SVDQ_FP16 = 1 };
 enum {
     SVDQ_OK = 0,
     SVDQ_E_INVALID = 1,     /* bad shape / alignment / missing tensor            */
-    SVDQ_E_UNSUPPORTED = 2, /* valid in the reference, not implemented here (fp4, LiteLA, ...) */
+    SVDQ_E_UNSUPPORTED = 2, /* valid in the reference, not implemented here (fp4, other head sizes, ...) */
     SVDQ_E_HIP = 3          /* a HIP runtime call failed                                    */
 };
 
@@ -525,6 +525,47 @@ typedef struct svdq_ip_attention_args {
 } svdq_ip_attention_args;
 
 int svdq_ip_attention(const svdq_ip_attention_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * ReLU linear attention (SANA's LiteLA; added WITHOUT a version bump: two new symbols and a new args struct, nothing existing changes,
+ * so SVDQ_ABI_VERSION stays 24.  reference: src/SanaModel.cpp:25-106, epilogues.cuh:552-761 -- there an epilogue of the QKV GEMM that
+ * adds into vk with fp32 atomics, and a second kernel for the product with Q; here the QKV GEMM runs its plain epilogue and this call
+ * reads the packed buffer it wrote, in place).  Per batch element b < B and head h < H, over the tokens t < T, head dimension 32:
+ *   vk[b, h, i, j]  = sum_t V[t, i] * relu(K[t, j])      i, j < 32, fp32
+ *   vk[b, h, 32, j] = sum_t relu(K[t, j])
+ *   out[b, t, h, i] = round16( (sum_j relu(Q[t, j]) * vk[i, j]) / (sum_j relu(Q[t, j]) * vk[32, j] + eps) )
+ * q is [T, H, 32] (head h at column 32 h of a row), kv is [T, H, 64] (K of head h at column 64 h, V at 64 h + 32: the order of the
+ * reference's QKV projection behind its Q third), out is [T, H * 32] token-major; each has a row stride and a batch stride in
+ * elements, so the thirds of a packed [B, T, 3 * H * 32] buffer are read in place.  Rows at or beyond T of a batch element are neither
+ * read nor written; batch elements may start on any row.  vk (optional) receives the final sums.  q == NULL && out == NULL: only vk.
+ * vk is fp32 from the matrix core's accumulator to the quotient (at T = 2100 a 16-bit vk overflows).
+ * No atomics: the tokens are cut into chunks of 256, every chunk's [33, 32] fp32 partial goes to `workspace`, a finishing kernel adds
+ * the partials in chunk order: two calls on the same inputs are bit-identical.  At most three kernel launches (two for vk alone), no
+ * allocation, no synchronisation: the call can be captured.  workspace: svdq_linear_attention_workspace_bytes(args) bytes (depends on
+ * B, H, T only), no zero fill needed, contents are scratch; reuse is allowed for calls ordered on one stream.
+ * Validation (no launch): NULL args / kv / workspace, q without out or the reverse, neither and no vk, T / H / B < 1 (or beyond the
+ * grid: H, B <= 65535, H * B <= 2^20, T <= 2^30), a row stride smaller than the row, a batch stride (B > 1) smaller than
+ * (T - 1) * row stride + row width, pointers not 16-byte aligned or strides not a multiple of 8 elements, unknown dtype, eps negative
+ * or not finite, a workspace smaller than the query says (svdq_last_error() names the byte count): SVDQ_E_INVALID;
+ * head_dim != 32: SVDQ_E_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct svdq_linear_attention_args {
+    const void *q;   /* [B][T, H, 32] 16-bit, row stride ldq, batch stride q_bs; NULL (with out): only vk */
+    const void *kv;  /* [B][T, H, 64], row stride ldkv, batch stride kv_bs */
+    void *out;       /* [B][T, H * 32], row stride ldo, batch stride out_bs */
+    float *vk;       /* [B, H, 33, 32] fp32 contiguous, or NULL */
+    void *workspace;
+    int64_t workspace_bytes;
+    int64_t q_bs, kv_bs, out_bs; /* in elements; ignored when B == 1 */
+    int32_t ldq, ldkv, ldo;      /* in elements */
+    int32_t B, T, H, head_dim;
+    int32_t dtype;
+    float eps;       /* 1e-6 in the reference */
+    int32_t reserved;
+} svdq_linear_attention_args;
+
+int svdq_linear_attention(const svdq_linear_attention_args *args, void *stream);
+int64_t svdq_linear_attention_workspace_bytes(const svdq_linear_attention_args *args);
 
 /* ------------------------------------------------------------------------------------------
  * AWQ W4A16 GEMV (reference: ops.gemv_awq, nunchaku/csrc/ops.h:123-145 -> src/kernels/awq/gemv_awq.cu:100-286;

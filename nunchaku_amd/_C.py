@@ -140,6 +140,9 @@ _WORKSPACE_BYTES_LIMIT = 512 << 20  # per kind and device: the cache is bounded 
 _workspaces: "collections.OrderedDict[tuple[int, int, str], _Workspace]" = collections.OrderedDict()
 
 
+_PLAIN_KINDS = ("awq", "linear_attention")  # workspaces that are scratch only
+
+
 def _evict(kind: str, keep) -> None:
     """Drop least recently used workspaces of `kind` on `keep`'s device beyond the entry limit or the byte limit -- never `keep` itself, never one a captured
     graph points at.  The tensor is freed by the caching allocator once the work queued on it has finished."""
@@ -186,11 +189,12 @@ def _workspace(device: torch.device, kind: str = "gemm", min_bytes: int = 0) -> 
         grown = True
     if ws is None:
         lib = _lib.load()
-        # (kind "awq": the fp32 partial tiles of gemm_awq's K-split -- no counters, no status word, sized by the launch)
-        size = lib.svdq_attention_workspace_bytes() if kind == "attention" else 0 if kind == "awq" else lib.svdq_gemm_workspace_bytes()
+        # (kinds "awq" and "linear_attention": the fp32 partial tiles of gemm_awq's K-split / of linear_attention's token chunks -- no counters, no status
+        # word, sized by the launch)
+        size = lib.svdq_attention_workspace_bytes() if kind == "attention" else 0 if kind in _PLAIN_KINDS else lib.svdq_gemm_workspace_bytes()
         with torch.cuda.device(idx):
             buf = torch.zeros(max(int(size), int(min_bytes)), dtype=torch.uint8, device=device)
-        ws = _Workspace(buf, None if kind == "awq" else _status_word())
+        ws = _Workspace(buf, None if kind in _PLAIN_KINDS else _status_word())
         _workspaces[key] = ws
         _evict(kind, key)
     else:
@@ -511,8 +515,28 @@ class _Ops:
             raise NotImplementedError("gemm_w4a4: fp4 (NVFP4) is Blackwell-only; use int4 checkpoints")
         if alpha is not None and float(alpha) != 1.0:
             raise ValueError("gemm_w4a4: alpha must be 1.0 for int4 (launch_impl.cuh:107)")
+        litela = None
         if out_linearattn is not None or out_vk is not None:
-            raise NotImplementedError("gemm_w4a4: the SANA LiteLA epilogue is out of scope")
+            # SANA's LiteLA epilogue (launch_impl.cuh:311-345), a compatibility path like the packed Q / K / V adapter below: the GEMM runs its plain
+            # epilogue into a scratch [B * T_pad, N]; relu(Q) and the sums over ALL T_pad rows of a batch element follow behind the launch
+            if out_linearattn is None or out_vk is None:
+                raise ValueError("gemm_w4a4: out_vk and out_linearattn go together")
+            if out is not None or qout is not None or rotary_emb is not None or out_q is not None or out_k is not None or out_v is not None:
+                raise ValueError("gemm_w4a4: out_vk / out_linearattn exclude every other output and the RMSNorm+RoPE epilogue")
+            if wgt is None:
+                raise ValueError("gemm_w4a4: act, wgt, ascales and wscales are required")
+            n_cols = wgt.shape[0]
+            if out_vk.dtype != torch.float32 or out_vk.dim() != 4 or out_vk.shape[2] != 33 or out_vk.shape[3] != 32 or out_vk.shape[1] * 32 * 3 != n_cols:
+                raise ValueError("gemm_w4a4: out_vk must be float32 [B, H, 33, 32] with H * 32 * 3 == N (launch_impl.cuh:317-321)")
+            if (out_linearattn.dtype not in _DT or out_linearattn.dim() != 3 or out_linearattn.shape[0] != out_vk.shape[0]
+                    or out_linearattn.shape[2] * 3 != n_cols):
+                raise ValueError("gemm_w4a4: out_linearattn must be 16-bit [B, T_pad, N / 3] with the B of out_vk (launch_impl.cuh:325-328)")
+            if out_linearattn.shape[1] % 256:
+                raise ValueError("gemm_w4a4: out_linearattn.shape[1] (T_pad) must be a multiple of 256 (launch_impl.cuh:331)")
+            if not out_vk.is_contiguous() or not out_vk.is_cuda or not out_linearattn.is_cuda:
+                raise ValueError("gemm_w4a4: out_vk must be a contiguous GPU tensor, out_linearattn a GPU tensor")
+            litela = (out_linearattn, out_vk)
+            out = torch.empty(out_vk.shape[0] * out_linearattn.shape[1], n_cols, dtype=out_linearattn.dtype, device=out_linearattn.device)
         packed_qkv = None
         if out_q is not None or out_k is not None or out_v is not None:
             # the reference's "nunchaku-fp16" attention path (attention_processors/flux.py:114-237): Q / K / V go to three
@@ -641,6 +665,12 @@ class _Ops:
                 a.workspace, a.workspace_bytes = ws.buf.data_ptr(), ws.buf.numel()
         _lib.check(lib.svdq_gemm_w4a4(C.byref(a), _stream()), "gemm_w4a4")
         del keep, keep2
+        if litela is not None:
+            o_q, o_vk = litela
+            B, T_pad, hd = o_q.shape
+            qkv = out.view(B, T_pad, 3 * hd)
+            o_q.copy_(torch.relu(qkv[..., :hd]))
+            _Ops.linear_attention(None, qkv[..., hd:].unflatten(2, (hd // 32, 64)), None, vk=o_vk)
         if packed_qkv is not None:
             oq, ok, ov, tokens = packed_qkv
             H, M, T_pad = oq.shape[1], out.shape[0], oq.shape[2]
@@ -983,6 +1013,55 @@ class _Ops:
         a.T, a.H, a.N, a.head_dim, a.dtype = T, H, k.shape[0], D, _DT[q.dtype]
         a.q_prescaled, a.scale, a.out_scale = 1 if q_prescaled else 0, float(scale), float(out_scale)
         _lib.check(lib.svdq_ip_attention(C.byref(a), _stream()), "ip_attention")
+
+    @staticmethod
+    def linear_attention(q, kv, out, vk=None, eps=1e-6):
+        """Extension (SANA): ReLU linear attention per batch element and head, head_dim 32 (``svdq_linear_attention``):
+        ``vk = [V | 1]^T relu(K)`` over the tokens in fp32, ``out = round16(relu(Q) vk[:32]^T / (relu(Q) . vk[32] + eps))``.
+        ``q`` / ``out``: ``[B, T, H, 32]`` views (or ``[T, H, 32]``: one batch element) with any row and batch stride, heads 32 elements apart --
+        the Q third of a packed QKV buffer is read in place; ``kv``: ``[B, T, H, 64]``, K then V of a head.  ``vk``: float32 ``[B, H, 33, 32]``,
+        receives the sums.  ``q is None and out is None``: only ``vk``.  The chunk partials live in the stream's cached workspace
+        (``_workspace(kind="linear_attention")``)."""
+        lib = _lib.load()
+        if (q is None) != (out is None):
+            raise ValueError("linear_attention: q and out go together (both None: only vk)")
+        if q is None and vk is None:
+            raise ValueError("linear_attention: nothing to compute (no q / out and no vk)")
+        if kv is None or kv.dim() not in (3, 4):
+            raise ValueError("linear_attention: kv must be a [B, T, H, 2 * D] (or [T, H, 2 * D]) view")
+        views = {}
+        for name, t in (("q", q), ("kv", kv), ("out", out)):
+            if t is None:
+                continue
+            if t.dim() == 3:
+                t = t.unsqueeze(0)
+            if t.dim() != 4 or t.stride(3) != 1 or (t.shape[2] > 1 and t.stride(2) != t.shape[3]):
+                raise ValueError(f"linear_attention: {name} must be a [B, T, H, D] view with unit channel stride and heads D elements apart")
+            if not t.is_cuda:
+                raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
+            views[name] = t
+        kv = views["kv"]
+        B, T, H, D2 = kv.shape
+        D = D2 // 2
+        if kv.dtype not in _DT or D2 != 2 * D or any(t.dtype != kv.dtype or tuple(t.shape) != (B, T, H, D) for n, t in views.items() if n != "kv"):
+            raise ValueError("linear_attention: expected q / out [B, T, H, D] and kv [B, T, H, 2 * D] in one 16-bit dtype")
+        if vk is not None and (vk.dtype != torch.float32 or tuple(vk.shape) != (B, H, D + 1, D) or not vk.is_contiguous()):
+            raise ValueError("linear_attention: vk must be a contiguous float32 [B, H, D + 1, D] tensor")
+        if vk is not None and not vk.is_cuda:
+            raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
+        a = _lib.LinearAttentionArgs()
+        a.B, a.T, a.H, a.head_dim, a.dtype, a.eps = B, T, H, D, _DT[kv.dtype], float(eps)
+        # (the strides of dimensions of size 1 are arbitrary in torch: the library gets the natural ones)
+        row = lambda t: t.stride(1) if T > 1 else H * t.shape[3]
+        a.kv, a.ldkv, a.kv_bs = kv.data_ptr(), row(kv), kv.stride(0) if B > 1 else 0
+        if q is not None:
+            a.q, a.ldq, a.q_bs = views["q"].data_ptr(), row(views["q"]), views["q"].stride(0) if B > 1 else 0
+            a.out, a.ldo, a.out_bs = views["out"].data_ptr(), row(views["out"]), views["out"].stride(0) if B > 1 else 0
+        a.vk = None if vk is None else vk.data_ptr()
+        need = int(lib.svdq_linear_attention_workspace_bytes(C.byref(a)))
+        ws = _workspace(kv.device, "linear_attention", min_bytes=need)  # (a capture cannot grow the buffer: the library then names the size)
+        a.workspace, a.workspace_bytes = ws.buf.data_ptr(), ws.buf.numel()
+        _lib.check(lib.svdq_linear_attention(C.byref(a), _stream()), "linear_attention")
 
 
 class _Utils:

@@ -72,6 +72,17 @@ class IpAttentionArgs(C.Structure):
     ]
 
 
+class LinearAttentionArgs(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p), ("kv", C.c_void_p), ("out", C.c_void_p), ("vk", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+        ("q_bs", C.c_int64), ("kv_bs", C.c_int64), ("out_bs", C.c_int64),
+        ("ldq", C.c_int32), ("ldkv", C.c_int32), ("ldo", C.c_int32),
+        ("B", C.c_int32), ("T", C.c_int32), ("H", C.c_int32), ("head_dim", C.c_int32),
+        ("dtype", C.c_int32), ("eps", C.c_float), ("reserved", C.c_int32),
+    ]
+
+
 class GemmArgs(C.Structure):
     _fields_ = [
         ("act", C.c_void_p), ("wgt", C.c_void_p), ("ascales", C.c_void_p), ("wscales", C.c_void_p),
@@ -148,6 +159,8 @@ EXPORTS = {
     "svdq_residual_diff": (C.c_int, [C.POINTER(ResidualDiffArgs), C.c_void_p]),
     "svdq_modulated_diff": (C.c_int, [C.POINTER(ModulatedDiffArgs), C.c_void_p]),
     "svdq_ip_attention": (C.c_int, [C.POINTER(IpAttentionArgs), C.c_void_p]),
+    "svdq_linear_attention": (C.c_int, [C.POINTER(LinearAttentionArgs), C.c_void_p]),
+    "svdq_linear_attention_workspace_bytes": (C.c_int64, [C.POINTER(LinearAttentionArgs)]),
     "svdq_gemm_workspace_bytes": (C.c_int64, []),
     "svdq_gemm_workspace_bytes_for": (C.c_int64, [C.POINTER(GemmArgs)]),
     "svdq_gemm_workspace_status": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -5,7 +5,7 @@ import subprocess
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libsvdq_amd.so")
-SOURCES = ["repack.hip", "quantize.hip", "gemm_w4a4.hip", "attention.hip", "gemv_awq.hip", "gemv_awq_lora.hip", "gemm_awq.hip", "residual.hip", "residual_diff.hip", "modulated_diff.hip", "ip_attention.hip"]
+SOURCES = ["repack.hip", "quantize.hip", "gemm_w4a4.hip", "attention.hip", "gemv_awq.hip", "gemv_awq_lora.hip", "gemm_awq.hip", "residual.hip", "residual_diff.hip", "modulated_diff.hip", "ip_attention.hip", "linear_attention.hip"]
 HEADERS = ["svdq_common.h", "row_pass.h", "lowrank_split.h", "attention_loop64_bf16.inc", "attention_loop64_fp16.inc", "gemm_loop2_bf16.inc", "gemm_loop2_fp16.inc", "gemm_loop2_w4_bf16.inc", "gemm_loop2_w4_fp16.inc", "gemm_loop3_bf16.inc", "gemm_loop3_fp16.inc", "gemm_epi3_bf16.inc", "gemm_epi3_fp16.inc", os.path.join("..", "..", "include", "svdq_amd.h")]
 # -ffp-contract=off: the quantiser's arithmetic is specified operation by operation;
 # the hot loop uses explicit fma.

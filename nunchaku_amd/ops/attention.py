@@ -116,3 +116,36 @@ def ip_attention(qkv_or_q: torch.Tensor, k_ip: torch.Tensor, v_ip: torch.Tensor,
                      v_ip.reshape(-1, hd) if v_ip.dim() != 2 else v_ip, out.unflatten(1, (heads, D)),
                      1.0 / math.sqrt(D) if scale is None else scale, out_scale=out_scale, q_prescaled=q_prescaled)
     return out
+
+
+def linear_attention(qkv: torch.Tensor, heads: int, out: torch.Tensor | None = None, tokens: int | None = None, return_vk: bool = False,
+                     eps: float = 1e-6):
+    """SANA's ReLU linear attention over the packed output of the QKV projection, read in place (no copies): per batch element and head
+    (head_dim 32), ``vk = [V | 1]^T relu(K)`` summed over the tokens in fp32 and ``out = relu(Q) vk[:32]^T / (relu(Q) . vk[32] + eps)``,
+    rounded once.  ``qkv``: ``[B, T, 3*H*32]``, or ``[B*T, 3*H*32]`` with ``tokens=T`` (one batch element without it); the columns are the
+    reference's: Q of head h at ``32 h``, then K and V of head h at ``H*32 + 64 h`` and ``H*32 + 64 h + 32``.  Any row and batch stride
+    that keeps rows 16-byte aligned.  Returns ``out`` in the leading shape of ``qkv`` with ``H*32`` columns, token-major (what the output
+    projection's quantiser reads); with ``return_vk`` also the float32 ``[B, H, 33, 32]`` sums.  No atomics: bit-equal from call to call."""
+    if qkv.dim() == 3:
+        B, T = qkv.shape[:2]
+        packed = qkv
+    elif qkv.dim() == 2:
+        T = qkv.shape[0] if tokens is None else int(tokens)
+        if T < 1 or qkv.shape[0] % T:
+            raise ValueError("linear_attention: the rows of a [B*T, 3*H*D] qkv must be a multiple of tokens")
+        B = qkv.shape[0] // T
+        packed = qkv.unflatten(0, (B, T))
+    else:
+        raise ValueError("linear_attention: expected qkv [B, T, 3*H*D] or [B*T, 3*H*D]")
+    hd = packed.shape[-1] // 3
+    D = hd // heads
+    if packed.shape[-1] != 3 * heads * D or (tokens is not None and qkv.dim() == 3 and int(tokens) != T):
+        raise ValueError("linear_attention: expected qkv [B, T, 3*H*D] or [B*T, 3*H*D] (+ tokens)")
+    if out is None:
+        out = torch.empty(*qkv.shape[:-1], hd, dtype=qkv.dtype, device=qkv.device)
+    if tuple(out.shape) not in ((B, T, hd), (B * T, hd)):
+        raise ValueError("linear_attention: out must be [B, T, H*D] or [B*T, H*D]")
+    out4 = (out if out.dim() == 3 else out.unflatten(0, (B, T))).unflatten(-1, (heads, D))
+    vk = torch.empty(B, heads, D + 1, D, dtype=torch.float32, device=qkv.device) if return_vk else None
+    ops.linear_attention(packed[..., :hd].unflatten(-1, (heads, D)), packed[..., hd:].unflatten(-1, (heads, 2 * D)), out4, vk, eps)
+    return (out, vk) if return_vk else out

@@ -19,7 +19,7 @@ def svdq_gemm_w4a4_cuda(
     lora_down: T | None = None, lora_act_out: T | None = None,              # ... of the NEXT layer (GELU_QUANT epilogue)
     norm_q: T | None = None, norm_k: T | None = None, rotary_emb: T | None = None,   # RMSNorm + RoPE epilogue
     bias: T | None = None, smooth_factor: T | None = None,
-    out_vk: T | None = None, out_linearattn: T | None = None,               # SANA LiteLA: not supported
+    out_vk: T | None = None, out_linearattn: T | None = None,               # SANA LiteLA: fp32 [B, H, 33, 32] sums / relu(Q) [B, T_pad, N/3]
     act_unsigned: bool = False, lora_scales: list[float] | None = None, fuse_silu: bool = False,
     fp4: bool = False, alpha: float | None = 1.0, wcscales: T | None = None,          # NVFP4 only
     out_q: T | None = None, out_k: T | None = None, out_v: T | None = None, attn_tokens: int = 0,
