@@ -6,7 +6,6 @@ import subprocess
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libsvdq_amd.so")
 SOURCES = ["repack.hip", "quantize.hip", "gemm_w4a4.hip", "attention.hip", "gemv_awq.hip", "gemv_awq_lora.hip", "gemm_awq.hip", "residual.hip", "residual_diff.hip", "modulated_diff.hip", "ip_attention.hip", "linear_attention.hip"]
-HEADERS = ["svdq_common.h", "row_pass.h", "lowrank_split.h", "attention_loop64_bf16.inc", "attention_loop64_fp16.inc", "gemm_loop2_bf16.inc", "gemm_loop2_fp16.inc", "gemm_loop2_w4_bf16.inc", "gemm_loop2_w4_fp16.inc", "gemm_loop3_bf16.inc", "gemm_loop3_fp16.inc", "gemm_epi3_bf16.inc", "gemm_epi3_fp16.inc", os.path.join("..", "..", "include", "svdq_amd.h")]
 # -ffp-contract=off: the quantiser's arithmetic is specified operation by operation;
 # the hot loop uses explicit fma.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared"]
@@ -16,7 +15,9 @@ def _stale() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + HEADERS)
+    # every header and generated .inc file in csrc, whether listed anywhere or not: a forgotten one would leave a stale library in place
+    deps = SOURCES + [f for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))] + [os.path.join("..", "..", "include", "svdq_amd.h")]
+    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in deps)
 
 
 def build(force: bool = False, verbose: bool = False) -> str:

@@ -61,18 +61,13 @@
 #define SVDQ_PROBE_VROW 0
 #endif
 
-// generated main loops (tools/gen_gemm_loop2.py); the probe build substitutes option variants
-#ifndef SVDQ_LOOP_INC_8_BF16
-#define SVDQ_LOOP_INC_8_BF16 "gemm_loop2_bf16.inc"
+// generated main loops (tools/gen_gemm_loop2.py); the probe build substitutes option variants.  One file serves both dtypes: asm_tokens_{bf16,fp16}.h,
+// included in front of each asm statement, defines the token that differs
+#ifndef SVDQ_LOOP_INC_8
+#define SVDQ_LOOP_INC_8 "gemm_loop2.inc"
 #endif
-#ifndef SVDQ_LOOP_INC_8_FP16
-#define SVDQ_LOOP_INC_8_FP16 "gemm_loop2_fp16.inc"
-#endif
-#ifndef SVDQ_LOOP_INC_4_BF16
-#define SVDQ_LOOP_INC_4_BF16 "gemm_loop2_w4_bf16.inc"
-#endif
-#ifndef SVDQ_LOOP_INC_4_FP16
-#define SVDQ_LOOP_INC_4_FP16 "gemm_loop2_w4_fp16.inc"
+#ifndef SVDQ_LOOP_INC_4
+#define SVDQ_LOOP_INC_4 "gemm_loop2_w4.inc"
 #endif
 #ifndef SVDQ_LOOP3_INC_BF16   // the 128 x 64 wave tile kernel: main loop and plain epilogue (tools/gen_gemm_loop3.py)
 #define SVDQ_LOOP3_INC_BF16 "gemm_loop3_bf16.inc"
@@ -577,20 +572,24 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm_w4a4_kernel(const GemmParams 
                   "{s59}"(npre), "{s60}"(ncnt), "{s[62:63]}"(nA), "{s[64:65]}"(nX1), "{s[66:67]}"(nX2), "{s68}"(landed)            \
                 : "memory", "scc", "m0", "s53", "s55", "s56", "s57", "s61", "s69", "s84", "s85", "s86", "s87", SVDQ_LOOP_CLOBBER_V
             if constexpr (NW == 8 && DT == SVDQ_BF16) {
+#include "asm_tokens_bf16.h"
                 asm volatile(
-#include SVDQ_LOOP_INC_8_BF16
+#include SVDQ_LOOP_INC_8
                     SVDQ_LOOP2_OPERANDS);
             } else if constexpr (NW == 8) {
+#include "asm_tokens_fp16.h"
                 asm volatile(
-#include SVDQ_LOOP_INC_8_FP16
+#include SVDQ_LOOP_INC_8
                     SVDQ_LOOP2_OPERANDS);
             } else if constexpr (DT == SVDQ_BF16) {
+#include "asm_tokens_bf16.h"
                 asm volatile(
-#include SVDQ_LOOP_INC_4_BF16
+#include SVDQ_LOOP_INC_4
                     SVDQ_LOOP2_OPERANDS);
             } else {
+#include "asm_tokens_fp16.h"
                 asm volatile(
-#include SVDQ_LOOP_INC_4_FP16
+#include SVDQ_LOOP_INC_4
                     SVDQ_LOOP2_OPERANDS);
             }
 #undef SVDQ_LOOP2_OPERANDS

@@ -1,6 +1,7 @@
 """The generated kernel sources in the tree are what their generators emit, and the attention iteration plan is complete.
 
-CPU-only: no GPU, no compiler.  (tools/gen_gemm_loop2.py -> gemm_loop2_*.inc: the GEMM main loops; tools/gen_attn_step.py ->
+CPU-only: no GPU, no compiler.  (tools/gen_gemm_loop2.py -> gemm_loop2.inc, gemm_loop2_w4.inc: the GEMM main loops, each one
+file for bf16 and fp16 through the token splices of tools/asm_tokens.py; tools/gen_attn_step.py ->
 attention_step64.inc: the slot placement of one KV-tile iteration of the 4 x 64 attention kernel.)"""
 import os
 import re
@@ -14,11 +15,47 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 def test_gemm_loops_in_tree_match_their_generator(tmp_path):
     import gen_gemm_loop2 as G2
 
-    for name, mfma, nw in (("gemm_loop2_bf16.inc", "v_mfma_f32_32x32x16_bf16", 8), ("gemm_loop2_fp16.inc", "v_mfma_f32_32x32x16_f16", 8),
-                           ("gemm_loop2_w4_bf16.inc", "v_mfma_f32_32x32x16_bf16", 4), ("gemm_loop2_w4_fp16.inc", "v_mfma_f32_32x32x16_f16", 4)):
+    for name, nw in (("gemm_loop2.inc", 8), ("gemm_loop2_w4.inc", 4)):
         out = tmp_path / name
-        G2.emit(str(out), mfma, "", nw=nw)
+        G2.emit(str(out), "", nw=nw)
         assert out.read_text() == open(os.path.join(CSRC, name)).read(), f"{name} is stale: run python tools/gen_gemm_loop2.py"
+
+
+def test_token_headers_in_tree_match_the_token_table():
+    import asm_tokens
+
+    for dt in asm_tokens.DTYPES:
+        name = f"asm_tokens_{dt}.h"
+        assert asm_tokens.header(dt) == open(os.path.join(CSRC, name)).read(), f"{name} is stale: run python tools/asm_tokens.py"
+
+
+def test_neutral_gemm_loops_expand_to_each_dtypes_generated_lines():
+    """The committed dtype-neutral files, expanded with each dtype's tokens, are the concrete lines the generator builds for that dtype: the text
+    the LDS-DMA walk below reasons about is the text the compiler gets."""
+    import asm_tokens
+    import gen_gemm_loop2 as G2
+
+    for name, nw in (("gemm_loop2.inc", 8), ("gemm_loop2_w4.inc", 4)):
+        neutral = open(os.path.join(CSRC, name)).read().splitlines()
+        for dt in asm_tokens.DTYPES:
+            lines = asm_tokens.expand(neutral, dt)
+            assert lines == G2.Gen(dt, "", nw).build(), (name, dt)
+            assert sum(ln.startswith(asm_tokens.tok(dt, "MFMA_K8") + " ") for ln in lines) == 3 * 8 + 3  # 8 per ring body, 1 per ring entry
+
+
+def test_a_dtype_specific_instruction_without_a_token_is_refused(tmp_path):
+    """one file for two dtypes is safe because write_neutral() compares them: an instruction only one dtype has, outside the token table, is not written"""
+    import asm_tokens
+
+    lines = {dt: [f"{asm_tokens.tok(dt, 'MFMA_K8')} v[80:95], v[176:177], v[180:181], 0"] for dt in asm_tokens.DTYPES}
+    assert asm_tokens.write_neutral(str(tmp_path / "ok.inc"), "a test", lines) == 1
+    lines["fp16"].append("v_pk_min_f16 v1, v1, s99")
+    try:
+        asm_tokens.write_neutral(str(tmp_path / "bad.inc"), "a test", lines)
+    except AssertionError:
+        assert not (tmp_path / "bad.inc").exists()
+    else:
+        raise AssertionError("a line only fp16 has went unnoticed")
 
 
 def test_attention_loops_in_tree_match_their_generator(tmp_path):
@@ -237,7 +274,7 @@ def test_gemm_loop_lds_dma_discipline():
     import gen_gemm_loop2 as G2
 
     for nw in (8, 4):
-        g = G2.Gen("v_mfma_f32_32x32x16_bf16", "", nw)
+        g = G2.Gen("bf16", "", nw)
         lines = [ln for ln in g.build() if not ln.startswith(";")]
         since_m0 = None  # instructions since the last M0 write (None: M0 not written yet)
         for ln in lines:

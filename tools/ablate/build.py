@@ -45,11 +45,10 @@ def build(opts: str = "", opts3: str = ""):
         suffix = "_wt_" + opts3.replace("+", "_")
     if opts:
         suffix += "_" + opts.replace("+", "_")
-        for nw, tag in ((8, "8"), (4, "4")):
-            for dt, mf in (("BF16", "v_mfma_f32_32x32x16_bf16"), ("FP16", "v_mfma_f32_32x32x16_f16")):
-                name = f"gemm_loop2_w{nw}_{dt.lower()}{suffix}.inc"
-                G2.emit(os.path.join(GEN, name), mf, opts, nw=nw)
-                flags.append(f'-DSVDQ_LOOP_INC_{tag}_{dt}="{name}"')
+        for nw in (8, 4):
+            name = f"gemm_loop2_w{nw}{suffix}.inc"
+            G2.emit(os.path.join(GEN, name), opts, nw=nw)
+            flags.append(f'-DSVDQ_LOOP_INC_{nw}="{name}"')
     # SVDQ_PROBE_DEFS="-DSVDQ_PROBE_ROT=1 ..." SVDQ_PROBE_TAG=rot1: compile-time timing variants of an epilogue (gemm_w4a4.hip "compile-time timing variants")
     if os.environ.get("SVDQ_PROBE_DEFS"):
         flags += os.environ["SVDQ_PROBE_DEFS"].split()

@@ -2,7 +2,9 @@
 """Generate main loop v2 of svdq_gemm_w4a4 (gfx950): same arithmetic and register image as tools/gen_gemm_loop.py
 (bit-identical results), ~40 fewer instructions per K-step.
 
-    python tools/gen_gemm_loop2.py        # writes nunchaku_amd/csrc/gemm_loop2_{bf16,fp16}.inc
+    python tools/gen_gemm_loop2.py        # writes nunchaku_amd/csrc/gemm_loop2.inc (8 waves) and gemm_loop2_w4.inc (4 waves)
+
+Each file serves bf16 and fp16: the one dtype-dependent mnemonic (the scale-tile MFMA) is a macro splice (tools/asm_tokens.py).
 
 Why (profiles/r2_gemm_ablation_cycles.txt): the loop is bound by instruction ISSUE, not by any pipe -- a SIMD with its
 two waves retires ~1 instruction per 4.5 cycles whatever the mix, MFMA and VALU barely overlap (P+S 64 cycles, P+S+16 fma
@@ -32,6 +34,8 @@ Register plan (the C++ side pins its asm operands to the same registers, gemm_w4
   s68 leading K-steps known to have landed (0 or s59)   s53 s55 s56 s57 s61 s84 s85 s86 s87 scratch
 """
 import os
+
+import asm_tokens
 
 CHUNK, PLANE = 3072, 1024
 
@@ -88,8 +92,8 @@ def sr(a, n=1):
 
 
 class Gen:
-    def __init__(self, smfma, opts="", nw=8):
-        self.smfma = smfma
+    def __init__(self, dt, opts="", nw=8):
+        self.dt = dt           # "bf16" | "fp16"
         self.opts = set(o for o in opts.split("+") if o)
         self.geo = Geometry(nw, 4 if "st4" in self.opts else None)  # "st4": the former ring of four (nw = 8; timing only: the kernel's LDS map assumes three)
         self.lines = []
@@ -158,8 +162,7 @@ class Gen:
         # round 6: the scale tile S = 2 ws as needs two non-zero k-slots; the legacy K = 8 form of the 16-bit MFMA (k-slots 0 and 4: the two registers of a tuple)
         # computes the same bits in the same 8 passes (tools/ablate/mfma_k8_probe: 32.6 cycles either way) and reads half the operand registers:
         # -3.5 % loop cycles, -2.5 ... -3.2 % launch time on the wave-tile probe, bit-exact (profiles/r6_gemm_wave_tile_probe.txt section 5)
-        op = "v_mfma_f32_32x32x8bf16_1k" if self.smfma.endswith("bf16") else "v_mfma_f32_32x32x8f16"
-        return f"{op} {vr(SBUF[dst_buf], 16)}, {vr(SCL[buf] + ni * TS, 2)}, {vr(SCL[buf] + (2 + mi) * TS, 2)}, 0"
+        return f"{asm_tokens.tok(self.dt, 'MFMA_K8')} {vr(SBUF[dst_buf], 16)}, {vr(SCL[buf] + ni * TS, 2)}, {vr(SCL[buf] + (2 + mi) * TS, 2)}, 0"
 
     def fma(self, t, pb, lo, hi):
         """acc += P * S for registers lo .. hi-1 of tile t.  "pkf": packed fp32 FMAs (v_pk_fma_f32: two accumulators per
@@ -481,21 +484,13 @@ class Gen:
         return self.lines
 
 
-def emit(path, smfma, opts="", nw=8):
-    g = Gen(smfma, opts, nw)
-    lines = g.build()
-    with open(path, "w") as f:
-        f.write("// GENERATED by tools/gen_gemm_loop2.py -- do not edit.\n")
-        for ln in lines:
-            f.write('"' + ln + '\\n"\n')
-    return len(lines)
+def emit(path, opts="", nw=8):
+    return asm_tokens.write_neutral(path, "tools/gen_gemm_loop2.py", {dt: Gen(dt, opts, nw).build() for dt in asm_tokens.DTYPES})
 
 
 if __name__ == "__main__":
     root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "nunchaku_amd", "csrc")
     opts = os.environ.get("SVDQ_GEN2_OPTS", "")
-    n = emit(os.path.join(root, "gemm_loop2_bf16.inc"), "v_mfma_f32_32x32x16_bf16", opts)
-    emit(os.path.join(root, "gemm_loop2_fp16.inc"), "v_mfma_f32_32x32x16_f16", opts)
-    n4 = emit(os.path.join(root, "gemm_loop2_w4_bf16.inc"), "v_mfma_f32_32x32x16_bf16", opts, nw=4)
-    emit(os.path.join(root, "gemm_loop2_w4_fp16.inc"), "v_mfma_f32_32x32x16_f16", opts, nw=4)
-    print(f"wrote gemm_loop2_{{bf16,fp16}}.inc ({n} lines each), gemm_loop2_w4_{{bf16,fp16}}.inc ({n4} lines each)")
+    n = emit(os.path.join(root, "gemm_loop2.inc"), opts)
+    n4 = emit(os.path.join(root, "gemm_loop2_w4.inc"), opts, nw=4)
+    print(f"wrote gemm_loop2.inc ({n} lines), gemm_loop2_w4.inc ({n4} lines)")
