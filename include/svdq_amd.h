@@ -568,6 +568,39 @@ int svdq_linear_attention(const svdq_linear_attention_args *args, void *stream);
 int64_t svdq_linear_attention_workspace_bytes(const svdq_linear_attention_args *args);
 
 /* ------------------------------------------------------------------------------------------
+ * Depthwise 3x3 convolution (SANA's GLU-MBConv; added WITHOUT a version bump: one new symbol and a new args struct, nothing existing
+ * changes, so SVDQ_ABI_VERSION stays 24.  reference: DWCONV, src/Linear.cpp:542-551 -> dwconv_f16, src/kernels/dwconv.cu -- a CUTLASS
+ * direct-convolution template; called between the two GEMMs of SanaGLUMBConv, src/SanaModel.cpp:192-213).
+ * Cross-correlation, stride 1, zero padding 1, channels-last: x and out are [B][H * W, C] token rows -- the GEMM's [B * T, C] output
+ * with T = H * W -- each with a row stride (per token) and a batch stride in elements, so each may be a column slice of a wider buffer.
+ * Per element, in fp32 and in exactly this order (which makes a CPU restatement bit-equal):
+ *   acc = bias[c] (or +0);  for ky = 0..2, for kx = 0..2:  acc += weight[ky * 3 + kx, c] * x[h + ky - 1, w + kx - 1, c];
+ *   out[h, w, c] = round16(acc)        (round to nearest even, once)
+ * A tap outside the image contributes the product with a zero, as conv2d's padding does.  The reference accumulates in the 16-bit
+ * type (ElementAccumulator = half_t, dwconv.cu:223): nine roundings where this call has one.
+ * weight is the TAP-MAJOR image [9, C] of the module's [C, 3, 3, 1] parameter (weight[ky * 3 + kx, c] = w[c, ky, kx, 0]: 8 channels
+ * of a tap are one 16-byte load), in the activation dtype; bias [C] or NULL.
+ * One launch, no workspace, no atomics, no allocation, no synchronisation: the call can be captured; two calls are bit-identical.
+ * Nothing outside x[:, :H * W, :C] is read and nothing outside out[:, :H * W, :C] is written; every offset is formed in 64 bits.
+ * Validation (no launch), SVDQ_E_INVALID: NULL args / x / weight / out, unknown dtype, B / H / W / C < 1, C % 8, a row stride below
+ * C or not a multiple of 8, a batch stride (B > 1) below H * W * row stride or not a multiple of 8, pointers not 16-byte aligned,
+ * x and out overlapping (in place is not supported), B > 65535 or more than 2^31 - 1 tiles.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct svdq_dwconv3x3_args {
+    const void *x;      /* [B][H * W, C] 16-bit, row stride ldx, batch stride x_bs */
+    const void *weight; /* [9, C] tap-major, contiguous */
+    const void *bias;   /* [C] or NULL */
+    void *out;          /* [B][H * W, C], row stride ldo, batch stride out_bs */
+    int64_t x_bs, out_bs; /* in elements; ignored when B == 1 */
+    int32_t ldx, ldo;     /* in elements */
+    int32_t B, H, W, C;
+    int32_t dtype;
+    int32_t reserved;
+} svdq_dwconv3x3_args;
+
+int svdq_dwconv3x3(const svdq_dwconv3x3_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * AWQ W4A16 GEMV (reference: ops.gemv_awq, nunchaku/csrc/ops.h:123-145 -> src/kernels/awq/gemv_awq.cu:100-286;
  * module nunchaku/models/linear.py:277-414).  The AdaLayerNormZero modulation projections of every block.
  *   out[m, n] = round16( sum_k round16( round16(q[n,k]*scales[k/64,n] + zeros[k/64,n]) * x[m,k] ) ) (+ bias[n])

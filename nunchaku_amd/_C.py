@@ -1063,6 +1063,48 @@ class _Ops:
         a.workspace, a.workspace_bytes = ws.buf.data_ptr(), ws.buf.numel()
         _lib.check(lib.svdq_linear_attention(C.byref(a), _stream()), "linear_attention")
 
+    @staticmethod
+    def dwconv3x3(x, weight, bias, out):
+        """Extension (SANA): depthwise 3x3 cross-correlation, stride 1, zero padding 1, channels-last (``svdq_dwconv3x3``):
+        ``out[b, h, w, c] = round16(bias[c] + sum_ky sum_kx weight[c, ky, kx, 0] * x[b, h + ky - 1, w + kx - 1, c])``, fp32, the nine taps added in
+        row-major order, rounded once.  ``x`` / ``out``: ``[B, H, W, C]`` views of token rows: unit channel stride, ``stride(1) == W * stride(2)``,
+        any row and batch stride that keeps rows 16-byte aligned -- each may be a column slice of a wider buffer; they must not overlap.
+        ``weight``: the reference's ``[C, 3, 3, 1]`` parameter, ``bias``: ``[C]`` or None, both in the dtype of ``x``.  The kernel reads a tap-major
+        ``[9, C]`` image of ``weight``; it is formed once per storage and version (``_cached_conversion``, like the low-rank fragment images)."""
+        lib = _lib.load()
+        if x is None or out is None or x.dim() != 4 or out.dim() != 4:
+            raise ValueError("dwconv3x3: x and out must be [B, H, W, C] views")
+        B, H, W, Cc = x.shape
+        if x.dtype not in _DT or out.dtype != x.dtype or weight.dtype != x.dtype or (bias is not None and bias.dtype != x.dtype):
+            raise ValueError("dwconv3x3: x, weight, bias and out must share one 16-bit dtype (bfloat16 or float16)")
+        if tuple(out.shape) != (B, H, W, Cc) or min(B, H, W, Cc) < 1:
+            raise ValueError(f"dwconv3x3: out must have the shape of x, {tuple(x.shape)} (every extent at least 1), got {tuple(out.shape)}")
+        if Cc % 8:
+            raise ValueError(f"dwconv3x3: C={Cc} must be a multiple of 8")
+        if tuple(weight.shape) != (Cc, 3, 3, 1) or (bias is not None and tuple(bias.shape) != (Cc,)):
+            raise ValueError(f"dwconv3x3: weight must be [C, 3, 3, 1] and bias [C] with C={Cc}, got {tuple(weight.shape)}"
+                             + ("" if bias is None else f" and {tuple(bias.shape)}"))
+        for name, t in (("x", x), ("out", out)):
+            if t.stride(3) != 1 or (H > 1 and W > 1 and t.stride(1) != W * t.stride(2)):
+                raise ValueError(f"dwconv3x3: {name} must be a [B, H, W, C] view of token rows: unit channel stride and stride(1) == W * stride(2)")
+        if not (x.is_cuda and out.is_cuda and weight.is_cuda and (bias is None or bias.is_cuda)):
+            raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
+        taps = _cached_conversion(weight, "dwconv_taps", lambda src: src.reshape(Cc, 9).t().contiguous())
+        if bias is not None and not bias.is_contiguous():
+            bias = bias.contiguous()
+        a = _lib.Dwconv3x3Args()
+        a.B, a.H, a.W, a.C, a.dtype = B, H, W, Cc, _DT[x.dtype]
+
+        # (the strides of dimensions of size 1 are arbitrary in torch: the library gets the natural ones)
+        def row(t):
+            return t.stride(2) if W > 1 else t.stride(1) if H > 1 else Cc
+
+        a.x, a.ldx, a.x_bs = x.data_ptr(), row(x), x.stride(0) if B > 1 else 0
+        a.out, a.ldo, a.out_bs = out.data_ptr(), row(out), out.stride(0) if B > 1 else 0
+        a.weight, a.bias = taps.data_ptr(), None if bias is None else bias.data_ptr()
+        _lib.check(lib.svdq_dwconv3x3(C.byref(a), _stream()), "dwconv3x3")
+        del taps
+
 
 class _Utils:
     """reference: csrc/pybind.cpp:118-123 -- logging / sm_75 toggles; no-ops here."""

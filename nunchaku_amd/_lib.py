@@ -83,6 +83,16 @@ class LinearAttentionArgs(C.Structure):
     ]
 
 
+class Dwconv3x3Args(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("weight", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p),
+        ("x_bs", C.c_int64), ("out_bs", C.c_int64),
+        ("ldx", C.c_int32), ("ldo", C.c_int32),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32),
+        ("dtype", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 class GemmArgs(C.Structure):
     _fields_ = [
         ("act", C.c_void_p), ("wgt", C.c_void_p), ("ascales", C.c_void_p), ("wscales", C.c_void_p),
@@ -161,6 +171,7 @@ EXPORTS = {
     "svdq_ip_attention": (C.c_int, [C.POINTER(IpAttentionArgs), C.c_void_p]),
     "svdq_linear_attention": (C.c_int, [C.POINTER(LinearAttentionArgs), C.c_void_p]),
     "svdq_linear_attention_workspace_bytes": (C.c_int64, [C.POINTER(LinearAttentionArgs)]),
+    "svdq_dwconv3x3": (C.c_int, [C.POINTER(Dwconv3x3Args), C.c_void_p]),
     "svdq_gemm_workspace_bytes": (C.c_int64, []),
     "svdq_gemm_workspace_bytes_for": (C.c_int64, [C.POINTER(GemmArgs)]),
     "svdq_gemm_workspace_status": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -240,17 +240,28 @@ class SVDQW4A4Linear(nn.Module):
         output = self.forward_quant(qx, ascales, lora_act, output)
         return output.reshape(B, S, -1)
 
-    def quantize(self, x: torch.Tensor, pad_size: int = 256, ln=None, pool=None):
+    def quantize(self, x: torch.Tensor, pad_size: int = 256, ln=None, pool=None, fuse_glu: bool = False):
         """x [N, in] -> (FP6 code image [N_pad, 3*in/4] uint8, ascales [in/64, N_pad], lora_act [N_pad, rank] f32).
         ``ln = (stats, scale, shift)``: quantise ``layer_norm(x) * scale + shift`` (fused AdaLayerNormZero, scale incl. +1);
-        ``pool``: a ``ZeroPool`` of pre-cleared fp32 scratch for the low-rank accumulator (ops/elementwise.py)."""
+        ``pool``: a ``ZeroPool`` of pre-cleared fp32 scratch for the low-rank accumulator (ops/elementwise.py);
+        ``fuse_glu``: x is [N, 2 * in] interleaved (value, gate) pairs, quantised as ``value * silu(gate)`` (reference: GEMM_W4A4::quantize(x, true),
+        src/Linear.cpp:444-470 -- SANA's GLU-MBConv)."""
         self._ensure_layout()
         return svdq_quantize_w4a4_act_fuse_lora_cuda(
-            x, lora_down=self.proj_down, smooth=self.smooth_factor, fp4=False, pad_size=pad_size, ln=ln, pool=pool
+            x, lora_down=self.proj_down, smooth=self.smooth_factor, fuse_glu=fuse_glu, fp4=False, pad_size=pad_size, ln=ln, pool=pool
         )
 
-    def forward_quant(self, quantized_x, ascales, lora_act, output: torch.Tensor | None = None) -> torch.Tensor:
-        """GEMM on pre-quantised input (codes from :meth:`quantize` or from a fused GELU epilogue)."""
+    def forward_silu(self, x: torch.Tensor, output: torch.Tensor | None = None) -> torch.Tensor:
+        """``silu(forward(x))`` with the SiLU in the GEMM's epilogue: one GEMM launch (reference: GEMM_W4A4::forward_silu, src/Linear.cpp:160-162).
+        ``output``: a [B * S, out] buffer (any row stride the GEMM takes) to write into."""
+        B, S, C_in = x.shape
+        if output is None:
+            output = torch.empty(B * S, self.out_features, dtype=x.dtype, device=x.device)
+        qx, ascales, lora_act = self.quantize(x.reshape(B * S, C_in))
+        return self.forward_quant(qx, ascales, lora_act, output, fuse_silu=True).reshape(B, S, -1)
+
+    def forward_quant(self, quantized_x, ascales, lora_act, output: torch.Tensor | None = None, fuse_silu: bool = False) -> torch.Tensor:
+        """GEMM on pre-quantised input (codes from :meth:`quantize` or from a fused GELU epilogue); ``fuse_silu``: SiLU in the epilogue."""
         self._ensure_layout()
         if output is None:
             output = torch.empty(
@@ -259,7 +270,7 @@ class SVDQW4A4Linear(nn.Module):
         svdq_gemm_w4a4_cuda(
             act=quantized_x, wgt=self.qweight, out=output, ascales=ascales, wscales=self.wscales,
             lora_act_in=lora_act, lora_up=self.proj_up, bias=self.bias, fp4=False, alpha=self.wtscale,
-            wcscales=self.wcscales, act_unsigned=self.act_unsigned, lora_scales=self.lora_scales,
+            wcscales=self.wcscales, act_unsigned=self.act_unsigned, lora_scales=self.lora_scales, fuse_silu=fuse_silu,
         )
         return output
 

@@ -1,8 +1,10 @@
-"""SANA's linear-attention layer (reference: src/SanaModel.cpp:13-136 ``SanaLinearAttention``).
+"""SANA's linear-attention layer and feed-forward (reference: src/SanaModel.cpp:13-136 ``SanaLinearAttention``, :192-213 ``SanaGLUMBConv``).
 
-The first part of the SANA family: the QKV projection, ReLU linear attention over its packed output (``svdq_linear_attention``: a new
-kernel, where the reference folds the K/V reduction into the GEMM's epilogue with atomics) and the output projection.  The GLU-MBConv
-with its depthwise convolution, the cross-attention, the block and the model class are not here yet.
+The first two parts of the SANA family.  The attention: the QKV projection, ReLU linear attention over its packed output
+(``svdq_linear_attention``: a kernel of its own, where the reference folds the K/V reduction into the GEMM's epilogue with atomics) and the
+output projection.  The feed-forward (GLU-MBConv): a GEMM with a SiLU epilogue, a depthwise 3x3 convolution over the token grid
+(``svdq_dwconv3x3``: a kernel of its own, where the reference instantiates a CUTLASS template) and a GEMM whose quantiser applies the GLU.
+The cross-attention, the transformer block and the model class ``NunchakuSanaTransformer2DModel`` are not here yet.
 """
 
 from __future__ import annotations
@@ -12,6 +14,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..ops.attention import linear_attention
+from ..ops.conv import dwconv3x3, grid_of
 from .linear import SVDQW4A4Linear
 
 HEAD_DIM = 32
@@ -74,6 +77,75 @@ class SanaLinearAttention(nn.Module):
         return out
 
 
+class SanaDepthwiseConv(nn.Module):
+    """The reference's ``DWCONV`` (src/Linear.cpp:542-551): ``weight`` [C, 3, 3, 1] and ``bias`` [C] in the activation dtype, a depthwise 3x3
+    cross-correlation with zero padding 1 over a channels-last ``[B, H, W, C]`` activation (``ops.conv.dwconv3x3``)."""
+
+    def __init__(self, channels: int, bias: bool = True, torch_dtype: torch.dtype = torch.bfloat16, device: str | torch.device | None = None):
+        super().__init__()
+        self.channels = channels
+        self.weight = nn.Parameter(torch.empty(channels, 3, 3, 1, dtype=torch_dtype, device=device), requires_grad=False)
+        self.bias = nn.Parameter(torch.empty(channels, dtype=torch_dtype, device=device), requires_grad=False) if bias else None
+
+    def forward(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """x [B, H, W, C] -> [B, H, W, C] (into ``out`` when given: it may be a column slice of a wider buffer)"""
+        return dwconv3x3(x, self.weight, self.bias, out=out)
+
+
+def _ceil128(n: int) -> int:
+    return (n + 127) // 128 * 128
+
+
+class SanaGLUMBConv(nn.Module):
+    """``point_conv(glu(depth_conv(silu(inverted_conv(x)))))`` over a grid of ``H x W`` tokens (SanaModel.cpp:192-213).
+
+    Sub-modules carry the reference's names (SanaModel.cpp:195-198): ``inverted_conv`` [in_pad -> C_gemm] with bias, ``depth_conv``
+    (``weight`` [C_gemm, 3, 3, 1], ``bias`` [C_gemm]) and ``point_conv`` [hid_pad -> in_pad] without bias, where ``in_pad = ceil128(in_features)``,
+    ``C_gemm = ceil128(2 * hidden_features)`` and ``hid_pad = ceil128(hidden_features)``: the reference's 4-bit GEMM pads both of its feature
+    counts to 128 (src/Linear.cpp:92-107), and the convolution runs on what the first GEMM wrote, so its parameters have that width too
+    (a ``depth_conv`` tensor of ``2 * hidden_features`` channels is padded with zeros behind its last channel before it is loaded).
+    SANA-1.6B: (2240, 5600) -> (2304, 11264, 5632); SANA-0.6B: (1152, 2880) -> (1152, 5760, 2944).
+
+    ``point_conv``'s quantiser reads ``2 * hid_pad`` interleaved (value, gate) columns, which is ``C_gemm`` for the first and 128 more than
+    ``C_gemm`` for the second: the convolution writes its ``C_gemm`` channels into a buffer ``2 * hid_pad`` wide whose tail columns are zeroed
+    where it is allocated -- ``0 * silu(0) = 0``, so the padded input channels of ``point_conv`` see zeros.
+    Legacy key names are mapped by :func:`convert_sana_ff_state_dict`; the result loads with ``strict=True``."""
+
+    def __init__(self, in_features: int, hidden_features: int, rank: int = 32, torch_dtype: torch.dtype = torch.bfloat16,
+                 device: str | torch.device | None = None):
+        super().__init__()
+        self.in_features, self.hidden_features = in_features, hidden_features
+        self.in_pad, self.c_gemm, self.hid_pad = _ceil128(in_features), _ceil128(2 * hidden_features), _ceil128(hidden_features)
+        kw = dict(rank=rank, torch_dtype=torch_dtype, device=device)
+        self.inverted_conv = SVDQW4A4Linear(self.in_pad, self.c_gemm, bias=True, **kw)
+        self.depth_conv = SanaDepthwiseConv(self.c_gemm, bias=True, torch_dtype=torch_dtype, device=device)
+        self.point_conv = SVDQW4A4Linear(self.hid_pad, self.in_pad, bias=False, **kw)
+
+    def gated_input(self, x: torch.Tensor, H: int | None = None, W: int | None = None) -> torch.Tensor:
+        """x [B, T, in_features] -> the [B, T, 2 * hid_pad] (value, gate) buffer ``point_conv``'s quantiser reads: ``depth_conv(silu(inverted_conv(x)))``
+        in its first ``C_gemm`` columns, zeros behind them."""
+        if x.dim() != 3 or x.shape[-1] != self.in_features:
+            raise ValueError(f"SanaGLUMBConv: expected x [B, T, {self.in_features}], got {tuple(x.shape)}")
+        B, T = x.shape[:2]
+        H, W = grid_of(T, H, W)
+        if self.in_pad != self.in_features:
+            x = F.pad(x, (0, self.in_pad - self.in_features))
+        y = self.inverted_conv.forward_silu(x)                               # [B, T, C_gemm]: one GEMM launch, SiLU in its epilogue
+        wide = torch.empty(B, T, 2 * self.hid_pad, dtype=y.dtype, device=y.device)
+        if 2 * self.hid_pad != self.c_gemm:
+            wide[..., self.c_gemm:].zero_()                                  # (the tail of THIS allocation; the convolution never writes it)
+        self.depth_conv(y.unflatten(1, (H, W)), out=wide[..., : self.c_gemm].unflatten(1, (H, W)))
+        return wide
+
+    def forward(self, x: torch.Tensor, H: int | None = None, W: int | None = None) -> torch.Tensor:
+        """x [B, T, in_features] on a grid of ``H x W = T`` tokens (without the pair: a square grid; one missing side is derived) -> [B, T, in_features]"""
+        wide = self.gated_input(x, H, W)
+        B, T = wide.shape[:2]
+        qx, ascales, lora_act = self.point_conv.quantize(wide.view(B * T, -1), fuse_glu=True)
+        out = torch.empty(B * T, self.in_pad, dtype=wide.dtype, device=wide.device)
+        return self.point_conv.forward_quant(qx, ascales, lora_act, out).view(B, T, -1)[..., : self.in_features]
+
+
 def convert_sana_attention_state_dict(sd: dict) -> dict:
     """Legacy parameter names -> this project's (what the reference's FLUX converter does, transformer_flux_v2.py:591-596, 623-628):
     ``lora_down`` -> ``proj_down``, ``lora_up`` -> ``proj_up``, ``smooth`` -> ``smooth_factor``, ``smooth_orig`` -> ``smooth_factor_orig``.
@@ -88,3 +160,9 @@ def convert_sana_attention_state_dict(sd: dict) -> dict:
                 nk = nk.replace(".smooth", ".smooth_factor")
         new[nk] = v
     return new
+
+
+def convert_sana_ff_state_dict(sd: dict) -> dict:
+    """The same mapping for the keys of one ``ff`` block (``inverted_conv.*``, ``point_conv.*``); ``depth_conv.weight`` and ``depth_conv.bias`` carry
+    none of the legacy names and pass through."""
+    return convert_sana_attention_state_dict(sd)
