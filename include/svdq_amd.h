@@ -601,6 +601,46 @@ typedef struct svdq_dwconv3x3_args {
 int svdq_dwconv3x3(const svdq_dwconv3x3_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Variable-length cross-attention (SANA's text cross-attention; added WITHOUT a version bump: one new symbol and a new args struct,
+ * nothing existing changes, so SVDQ_ABI_VERSION stays 24.  reference: MultiHeadCrossAttention::forward, src/SanaModel.cpp:147-190 ->
+ * flash-attention's mha_varlen_fwd).  Per sample b < B, query t < T and head h < H:
+ *   out[b, t, h, :] = round16( softmax_n(scale * q[b, t, h, :] . k[n, h, :]) . v[n, h, :] )
+ *   for n in [key_offsets[b], key_offsets[b] + key_counts[b])
+ * q and out are [B * T, H * head_dim] token rows (sample b owns rows b * T .. b * T + T - 1) with row strides ldq / ldo, so each may be
+ * a column slice of a wider buffer; k and v are [Nrows, H * head_dim] with row strides ldk / ldv -- the two column halves of one
+ * [Nrows, 2 * H * head_dim] projection are read in place.  head_dim 72, 112 or 128 (anything else: SVDQ_E_UNSUPPORTED).
+ * key_offsets and key_counts are DEVICE int32[B] and are read by the kernel only: no synchronisation, the call can be captured.  The
+ * packed layout of flash-attention is offsets = cu[:-1], counts = cu[1:] - cu[:-1]; a padded [B, L, .] condition is offsets = b * L,
+ * counts = mask.sum(1).  The kernel clamps what it read: a count below 0 acts as 0, a count above max_keys as max_keys, an offset
+ * outside [0, Nrows) gives an empty range and a range is cut at Nrows.  A sample without keys gets zero rows.
+ * max_keys is the host's upper bound on any count, 0 <= max_keys <= 320 (K and V of one sample and head stay in LDS, 160 KiB at
+ * head_dim 128; more: SVDQ_E_UNSUPPORTED, no launch).
+ * The keys are walked in chunks of 64 from the sample's first key with an online softmax (exp2 with scale * log2(e); the probabilities
+ * are rounded to 16 bits before they meet V, the row sum is taken over the rounded values, the normalisation follows the last MFMA, as
+ * in svdq_attention): a row's arithmetic depends on its own sample's keys only.  One launch, no atomics, no workspace: two launches
+ * are bit-identical.  Rows of k / v outside every range, rows of q / out beyond B * T and columns beyond H * head_dim are neither read
+ * nor written.
+ * Validation (no launch), SVDQ_E_INVALID: NULL args or pointers, B / T / H < 1, max_keys or Nrows < 0, a row stride below
+ * H * head_dim, pointers not 16-byte aligned (range arrays: 4-byte) or strides not a multiple of 8 elements, unknown dtype, a scale
+ * that is not finite and positive, B * H > 65535 or T > 2^30.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct svdq_cross_attention_args {
+    const void *q;   /* [B * T, H * head_dim] 16-bit, row stride ldq */
+    const void *k;   /* [Nrows, H * head_dim], row stride ldk */
+    const void *v;   /* [Nrows, H * head_dim], row stride ldv */
+    void *out;       /* [B * T, H * head_dim], row stride ldo */
+    const int32_t *key_offsets; /* device int32[B] */
+    const int32_t *key_counts;  /* device int32[B] */
+    int32_t ldq, ldk, ldv, ldo; /* in elements */
+    int32_t B, T, H, head_dim;
+    int32_t Nrows, max_keys;
+    int32_t dtype;
+    float scale;     /* head_dim^-0.5 in the reference */
+} svdq_cross_attention_args;
+
+int svdq_cross_attention(const svdq_cross_attention_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * AWQ W4A16 GEMV (reference: ops.gemv_awq, nunchaku/csrc/ops.h:123-145 -> src/kernels/awq/gemv_awq.cu:100-286;
  * module nunchaku/models/linear.py:277-414).  The AdaLayerNormZero modulation projections of every block.
  *   out[m, n] = round16( sum_k round16( round16(q[n,k]*scales[k/64,n] + zeros[k/64,n]) * x[m,k] ) ) (+ bias[n])

@@ -1105,6 +1105,45 @@ class _Ops:
         _lib.check(lib.svdq_dwconv3x3(C.byref(a), _stream()), "dwconv3x3")
         del taps
 
+    @staticmethod
+    def cross_attention(q, k, v, out, key_offsets, key_counts, max_keys, scale):
+        """Extension (SANA): ``out[b] = round16(softmax(scale * q[b] k_b^T) v_b)`` per head, where ``k_b`` / ``v_b`` are the rows
+        ``key_offsets[b] .. + key_counts[b]`` of ``k`` / ``v`` (``svdq_cross_attention``); head_dim 72, 112 or 128.  ``q`` / ``out``: ``[B, T, H, D]``
+        views whose batch stride is ``T`` rows (the token rows of a ``[B * T, .]`` buffer), any row stride, heads D elements apart; ``k`` / ``v``:
+        ``[Nrows, H * D]`` views with their own row strides (the column halves of one projection).  ``key_offsets`` / ``key_counts``: int32 ``[B]``
+        on the device, read by the kernel only; ``max_keys``: the host's bound on any count (at most 320)."""
+        lib = _lib.load()
+        for name, t in (("q", q), ("out", out)):
+            if t is None or t.dim() != 4 or t.stride(3) != 1 or (t.shape[2] > 1 and t.stride(2) != t.shape[3]):
+                raise ValueError(f"cross_attention: {name} must be a [B, T, H, D] view with unit channel stride and heads D elements apart")
+        for name, t in (("k", k), ("v", v)):
+            if t is None or t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"cross_attention: {name} must be a [Nrows, H * D] view with unit column stride")
+        if q.dtype not in _DT or k.dtype != q.dtype or v.dtype != q.dtype or out.dtype != q.dtype:
+            raise ValueError("cross_attention: q, k, v, out must share one 16-bit dtype (bfloat16 or float16)")
+        B, T, H, D = q.shape
+        if tuple(out.shape) != (B, T, H, D) or k.shape[1] != H * D or tuple(v.shape) != tuple(k.shape):
+            raise ValueError("cross_attention: expected q / out [B, T, H, D] and k / v [Nrows, H * D]")
+        for name, t in (("key_offsets", key_offsets), ("key_counts", key_counts)):
+            if t is None or t.dtype != torch.int32 or tuple(t.shape) != (B,) or not t.is_contiguous():
+                raise ValueError(f"cross_attention: {name} must be a contiguous int32 [B] tensor with B={B}")
+        for t in (q, k, v, out, key_offsets, key_counts):
+            if not t.is_cuda:
+                raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
+        # (the strides of dimensions of size 1 are arbitrary in torch: the library gets the natural ones)
+        row = lambda t: t.stride(1) if T > 1 else t.stride(0) if B > 1 else H * D
+        for name, t in (("q", q), ("out", out)):
+            if B > 1 and T > 1 and t.stride(0) != T * t.stride(1):
+                raise ValueError(f"cross_attention: {name} must hold its samples T rows apart (stride(0) == T * stride(1))")
+        a = _lib.CrossAttentionArgs()
+        a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+        a.key_offsets, a.key_counts = key_offsets.data_ptr(), key_counts.data_ptr()
+        a.ldq, a.ldo = row(q), row(out)
+        a.ldk, a.ldv = (k.stride(0), v.stride(0)) if k.shape[0] > 1 else (max(k.stride(0), H * D),) * 2
+        a.B, a.T, a.H, a.head_dim, a.Nrows, a.max_keys = B, T, H, D, k.shape[0], int(max_keys)
+        a.dtype, a.scale = _DT[q.dtype], float(scale)
+        _lib.check(lib.svdq_cross_attention(C.byref(a), _stream()), "cross_attention")
+
 
 class _Utils:
     """reference: csrc/pybind.cpp:118-123 -- logging / sm_75 toggles; no-ops here."""

@@ -156,6 +156,17 @@ class GemmAwqArgs(C.Structure):
     ]
 
 
+class CrossAttentionArgs(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("out", C.c_void_p),
+        ("key_offsets", C.c_void_p), ("key_counts", C.c_void_p),
+        ("ldq", C.c_int32), ("ldk", C.c_int32), ("ldv", C.c_int32), ("ldo", C.c_int32),
+        ("B", C.c_int32), ("T", C.c_int32), ("H", C.c_int32), ("head_dim", C.c_int32),
+        ("Nrows", C.c_int32), ("max_keys", C.c_int32),
+        ("dtype", C.c_int32), ("scale", C.c_float),
+    ]
+
+
 EXPORTS = {
     "svdq_quantize_w4a4_act_fuse_lora": (C.c_int, [C.POINTER(QuantizeArgs), C.c_void_p]),
     "svdq_gemm_w4a4": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
@@ -172,6 +183,7 @@ EXPORTS = {
     "svdq_linear_attention": (C.c_int, [C.POINTER(LinearAttentionArgs), C.c_void_p]),
     "svdq_linear_attention_workspace_bytes": (C.c_int64, [C.POINTER(LinearAttentionArgs)]),
     "svdq_dwconv3x3": (C.c_int, [C.POINTER(Dwconv3x3Args), C.c_void_p]),
+    "svdq_cross_attention": (C.c_int, [C.POINTER(CrossAttentionArgs), C.c_void_p]),
     "svdq_gemm_workspace_bytes": (C.c_int64, []),
     "svdq_gemm_workspace_bytes_for": (C.c_int64, [C.POINTER(GemmArgs)]),
     "svdq_gemm_workspace_status": (C.c_int, [C.c_void_p, C.c_void_p]),

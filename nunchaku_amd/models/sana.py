@@ -1,10 +1,13 @@
-"""SANA's linear-attention layer and feed-forward (reference: src/SanaModel.cpp:13-136 ``SanaLinearAttention``, :192-213 ``SanaGLUMBConv``).
+"""SANA's linear-attention layer, cross-attention and feed-forward (reference: src/SanaModel.cpp:13-136 ``SanaLinearAttention``, :138-190
+``MultiHeadCrossAttention``, :192-213 ``SanaGLUMBConv``).
 
-The first two parts of the SANA family.  The attention: the QKV projection, ReLU linear attention over its packed output
+The first three parts of the SANA family.  The attention: the QKV projection, ReLU linear attention over its packed output
 (``svdq_linear_attention``: a kernel of its own, where the reference folds the K/V reduction into the GEMM's epilogue with atomics) and the
 output projection.  The feed-forward (GLU-MBConv): a GEMM with a SiLU epilogue, a depthwise 3x3 convolution over the token grid
 (``svdq_dwconv3x3``: a kernel of its own, where the reference instantiates a CUTLASS template) and a GEMM whose quantiser applies the GLU.
-The cross-attention, the transformer block and the model class ``NunchakuSanaTransformer2DModel`` are not here yet.
+The cross-attention: a W4A4 query projection, a 16-bit K/V projection of the text condition, attention over per-sample key ranges
+(``svdq_cross_attention``: a kernel of its own, where the reference calls flash-attention's ``mha_varlen_fwd``) and a W4A4 output projection.
+The transformer block and the model class ``NunchakuSanaTransformer2DModel`` are not here yet.
 """
 
 from __future__ import annotations
@@ -13,7 +16,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ..ops.attention import linear_attention
+from ..ops.attention import CROSS_ATTENTION_MAX_KEYS, cross_attention, linear_attention
 from ..ops.conv import dwconv3x3, grid_of
 from .linear import SVDQW4A4Linear
 
@@ -146,6 +149,81 @@ class SanaGLUMBConv(nn.Module):
         return self.point_conv.forward_quant(qx, ascales, lora_act, out).view(B, T, -1)[..., : self.in_features]
 
 
+class SanaCrossAttention(nn.Module):
+    """``out_proj(cross_attention(q_linear(x), kv_linear(cond)))`` over per-sample ranges of text tokens (SanaModel.cpp:138-190).
+
+    Sub-modules carry the reference's names (SanaModel.cpp:141-144): ``q_linear`` and ``out_proj`` are W4A4 [dim_pad -> dim_pad] with bias, where
+    ``dim = num_heads * head_dim`` and ``dim_pad = ceil128(dim)`` (the reference's 4-bit GEMM pads both feature counts to 128, src/Linear.cpp:92-107;
+    SANA-1.6B: 20 x 112 = 2240 -> 2304, SANA-0.6B: 16 x 72 = 1152); ``kv_linear`` is an ``nn.Linear(dim, 2 * dim)`` in the activation dtype (the
+    reference's ``GEMM_F16``, not padded): K in its first ``dim`` output columns, V in the rest.  ``head_dim`` 72, 112 or 128.
+    Legacy key names are mapped by :func:`convert_sana_cross_attention_state_dict`; the result loads with ``strict=True``.
+
+    The attention reads Q in place from the first ``dim`` columns of ``q_linear``'s ``dim_pad``-wide rows and K / V in place from the two column
+    halves of ``kv_linear``'s output, and writes into the first ``dim`` columns of a ``dim_pad``-wide buffer whose tail is zeroed where it is
+    allocated: ``out_proj``'s padded input channels see zeros.  A sample has at most 320 text tokens (``max_sequence_length`` is 300).
+    K and V of a condition are computed on every call; they do not change over the denoising steps, so the model class can cache them."""
+
+    def __init__(self, num_heads: int, head_dim: int, rank: int = 32, torch_dtype: torch.dtype = torch.bfloat16,
+                 device: str | torch.device | None = None):
+        super().__init__()
+        if head_dim not in (72, 112, 128):
+            raise ValueError(f"SanaCrossAttention: head_dim={head_dim}: the cross-attention kernel has 72, 112 and 128")
+        self.num_heads, self.head_dim = num_heads, head_dim
+        self.dim = num_heads * head_dim
+        self.dim_pad = _ceil128(self.dim)
+        kw = dict(rank=rank, bias=True, torch_dtype=torch_dtype, device=device)
+        self.q_linear = SVDQW4A4Linear(self.dim_pad, self.dim_pad, **kw)
+        self.kv_linear = nn.Linear(self.dim, 2 * self.dim, bias=True, dtype=torch_dtype, device=device)
+        self.kv_linear.requires_grad_(False)
+        self.out_proj = SVDQW4A4Linear(self.dim_pad, self.dim_pad, **kw)
+
+    def _attend(self, x: torch.Tensor, cond2: torch.Tensor, max_keys: int, **ranges) -> torch.Tensor:
+        B, T = x.shape[:2]
+        if self.dim_pad != self.dim:
+            x = F.pad(x, (0, self.dim_pad - self.dim))
+        q = self.q_linear(x)                                                 # [B, T, dim_pad]; the first dim columns are Q
+        kv = self.kv_linear(cond2)                                           # [Ntxt, 2 * dim]: K | V
+        wide = torch.empty(B, T, self.dim_pad, dtype=q.dtype, device=q.device)
+        if self.dim_pad != self.dim:
+            wide[..., self.dim:].zero_()                                     # (the tail of THIS allocation; the attention never writes it)
+        cross_attention(q, kv[:, : self.dim], kv[:, self.dim:], self.num_heads, self.head_dim, max_keys=max_keys, out=wide[..., : self.dim], **ranges)
+        return self.out_proj(wide)[..., : self.dim]
+
+    def _check_x(self, x: torch.Tensor):
+        if x.dim() != 3 or x.shape[-1] != self.dim:
+            raise ValueError(f"SanaCrossAttention: expected x [B, T, {self.dim}], got {tuple(x.shape)}")
+
+    def forward(self, x: torch.Tensor, cond: torch.Tensor, cu_seqlens_img: torch.Tensor | None, cu_seqlens_txt: torch.Tensor) -> torch.Tensor:
+        """x [B, T, dim], cond [Ntxt, dim] (the samples' text tokens, packed), cu_seqlens_txt int32 [B + 1] on the device -> [B, T, dim].
+        ``cu_seqlens_img`` may be None and is otherwise checked for its length only: every sample has T image tokens (the reference's Python
+        always builds it uniform).  A sample may hold at most 320 text tokens: the ranges are not read on the host, the kernel is given
+        ``max_keys = min(Ntxt, 320)`` and a longer sample is cut to its first 320 tokens WITHOUT an error (:meth:`forward_padded` refuses ``L > 320``)."""
+        self._check_x(x)
+        B = x.shape[0]
+        if cond.dim() != 2 or cond.shape[-1] != self.dim:
+            raise ValueError(f"SanaCrossAttention: expected cond [Ntxt, {self.dim}], got {tuple(cond.shape)}")
+        if cu_seqlens_txt is None or cu_seqlens_txt.dim() != 1 or cu_seqlens_txt.shape[0] != B + 1:
+            raise ValueError(f"SanaCrossAttention: cu_seqlens_txt must be [B + 1] = [{B + 1}], got {None if cu_seqlens_txt is None else tuple(cu_seqlens_txt.shape)}")
+        if cu_seqlens_img is not None and (cu_seqlens_img.dim() != 1 or cu_seqlens_img.shape[0] != B + 1):
+            raise ValueError(f"SanaCrossAttention: cu_seqlens_img must be [B + 1] = [{B + 1}] or None, got {tuple(cu_seqlens_img.shape)}")
+        return self._attend(x, cond, min(cond.shape[0], CROSS_ATTENTION_MAX_KEYS), cu_seqlens=cu_seqlens_txt)
+
+    def forward_padded(self, x: torch.Tensor, cond: torch.Tensor, key_counts: torch.Tensor) -> torch.Tensor:
+        """x [B, T, dim], cond [B, L, dim] (every sample's text tokens first, padding behind them), key_counts int32 [B] on the device
+        (``mask.sum(1)``) -> [B, T, dim].  No boolean index, no host synchronisation: the call can be captured."""
+        self._check_x(x)
+        B = x.shape[0]
+        if cond.dim() != 3 or cond.shape[0] != B or cond.shape[-1] != self.dim:
+            raise ValueError(f"SanaCrossAttention: expected cond [{B}, L, {self.dim}], got {tuple(cond.shape)}")
+        L = cond.shape[1]
+        if L > CROSS_ATTENTION_MAX_KEYS:
+            raise ValueError(f"SanaCrossAttention: L={L} text tokens per sample: at most {CROSS_ATTENTION_MAX_KEYS}")
+        if key_counts is None or tuple(key_counts.shape) != (B,):
+            raise ValueError(f"SanaCrossAttention: key_counts must be [B] = [{B}], got {None if key_counts is None else tuple(key_counts.shape)}")
+        offsets = torch.arange(0, B * L, L, dtype=torch.int32, device=x.device) if L > 0 else torch.zeros(B, dtype=torch.int32, device=x.device)
+        return self._attend(x, cond.reshape(B * L, self.dim), L, key_offsets=offsets, key_counts=key_counts)
+
+
 def convert_sana_attention_state_dict(sd: dict) -> dict:
     """Legacy parameter names -> this project's (what the reference's FLUX converter does, transformer_flux_v2.py:591-596, 623-628):
     ``lora_down`` -> ``proj_down``, ``lora_up`` -> ``proj_up``, ``smooth`` -> ``smooth_factor``, ``smooth_orig`` -> ``smooth_factor_orig``.
@@ -164,5 +242,11 @@ def convert_sana_attention_state_dict(sd: dict) -> dict:
 
 def convert_sana_ff_state_dict(sd: dict) -> dict:
     """The same mapping for the keys of one ``ff`` block (``inverted_conv.*``, ``point_conv.*``); ``depth_conv.weight`` and ``depth_conv.bias`` carry
+    none of the legacy names and pass through."""
+    return convert_sana_attention_state_dict(sd)
+
+
+def convert_sana_cross_attention_state_dict(sd: dict) -> dict:
+    """The same mapping for the keys of one ``cross_attn`` block (``q_linear.*``, ``out_proj.*``); ``kv_linear.weight`` and ``kv_linear.bias`` carry
     none of the legacy names and pass through."""
     return convert_sana_attention_state_dict(sd)

@@ -149,3 +149,85 @@ def linear_attention(qkv: torch.Tensor, heads: int, out: torch.Tensor | None = N
     vk = torch.empty(B, heads, D + 1, D, dtype=torch.float32, device=qkv.device) if return_vk else None
     ops.linear_attention(packed[..., :hd].unflatten(-1, (heads, D)), packed[..., hd:].unflatten(-1, (heads, 2 * D)), out4, vk, eps)
     return (out, vk) if return_vk else out
+
+
+CROSS_ATTENTION_MAX_KEYS = 320  # keys per sample: K and V of one (sample, head) stay in LDS (csrc/cross_attention.hip, XA_MAX_KEYS)
+
+
+def cross_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, head_dim: int, *, cu_seqlens: torch.Tensor | None = None,
+                    key_offsets: torch.Tensor | None = None, key_counts: torch.Tensor | None = None, max_keys: int | None = None,
+                    scale: float | None = None, out: torch.Tensor | None = None):
+    """SANA's text cross-attention, one launch: per sample ``b`` and head, ``round16(softmax(scale * Q_b K_b^T) V_b)`` where ``K_b`` / ``V_b`` are
+    the rows of ``k`` / ``v`` in sample ``b``'s key range.  ``head_dim`` 72, 112 or 128; ``scale`` defaults to ``head_dim ** -0.5``.
+
+    ``q``: ``[B, T, >= H*D]`` (the output of ``q_linear``, whose rows may be wider than ``H*D``: the first ``H*D`` columns are read in place) or,
+    with ``cu_seqlens``, ``[B*T, >= H*D]`` with ``B = len(cu_seqlens) - 1``.  ``k`` / ``v``: ``[Nrows, H*D]``; they may be the two column halves of
+    one ``[Nrows, 2*H*D]`` tensor (what ``kv_linear`` wrote), no copy.  A ``[B, L, H*D]`` pair is taken as its ``[B*L, H*D]`` rows.
+
+    The key ranges, exactly one of
+      * ``cu_seqlens``: int32 ``[B + 1]``, flash-attention's packed layout: sample ``b`` owns rows ``cu[b] .. cu[b+1]``;
+      * ``key_offsets`` and ``key_counts``: int32 ``[B]`` each; a padded ``[B, L, .]`` condition is ``offsets = b * L, counts = mask.sum(1)``.
+    They live on q's device and are read by the kernel only: no host synchronisation, the call can be captured in a graph.  ``max_keys`` is
+    the host's bound on any count (default ``k.shape[0]``), at most 320; the kernel clamps a count to ``[0, max_keys]`` and cuts a range at the
+    last row of ``k``.  A sample without keys gets zero rows (a ``k`` without rows: all of them).
+
+    Returns ``out`` in the leading shape of ``q`` with ``H*D`` columns, token-major; a given ``out`` may be a column slice of a wider buffer."""
+    hd = heads * head_dim
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"cross_attention: {name} must be a tensor")
+        if t.dtype not in (torch.bfloat16, torch.float16):
+            raise TypeError(f"cross_attention: {name} must be bfloat16 or float16, got {t.dtype}")
+    if k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError(f"cross_attention: k ({k.dtype}) and v ({v.dtype}) must have q's dtype {q.dtype}")
+    if (cu_seqlens is None) == (key_offsets is None and key_counts is None):
+        raise ValueError("cross_attention: pass either cu_seqlens or the key_offsets / key_counts pair (exactly one of the two forms)")
+    if cu_seqlens is None and (key_offsets is None or key_counts is None):
+        raise ValueError("cross_attention: key_offsets and key_counts go together")
+    for name, t in (("cu_seqlens", cu_seqlens), ("key_offsets", key_offsets), ("key_counts", key_counts)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise TypeError(f"cross_attention: {name} must be an int32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+        if t.device != q.device:
+            raise ValueError(f"cross_attention: {name} must live on q's device {q.device}, got {t.device}")
+        if t.dim() != 1:
+            raise ValueError(f"cross_attention: {name} must be one-dimensional, got {tuple(t.shape)}")
+    if cu_seqlens is not None:
+        B = cu_seqlens.shape[0] - 1
+        if B < 1:
+            raise ValueError("cross_attention: cu_seqlens must have B + 1 >= 2 entries")
+        key_offsets, key_counts = cu_seqlens[:-1], cu_seqlens[1:] - cu_seqlens[:-1]
+    else:
+        B = key_offsets.shape[0]
+        if B < 1 or key_counts.shape[0] != B:
+            raise ValueError(f"cross_attention: key_offsets {tuple(key_offsets.shape)} and key_counts {tuple(key_counts.shape)} must both be [B]")
+    if q.dim() == 2 and cu_seqlens is not None and q.shape[0] % B == 0 and q.shape[0] >= B:
+        q3 = q.unflatten(0, (B, q.shape[0] // B))
+    elif q.dim() == 3 and q.shape[0] == B:
+        q3 = q
+    else:
+        raise ValueError(f"cross_attention: q must be [B, T, >= H*D] (or [B*T, >= H*D] with cu_seqlens) with B={B}, got {tuple(q.shape)}")
+    T = q3.shape[1]
+    if q3.shape[-1] < hd or T < 1:
+        raise ValueError(f"cross_attention: q must have at least heads * head_dim = {hd} columns and one row, got {tuple(q.shape)}")
+    if k.dim() == 3 and v.dim() == 3:
+        k, v = k.flatten(0, 1), v.flatten(0, 1)
+    if k.dim() != 2 or k.shape[-1] != hd or tuple(v.shape) != tuple(k.shape):
+        raise ValueError(f"cross_attention: k and v must be [Nrows, heads * head_dim = {hd}] of one shape, got {tuple(k.shape)} and {tuple(v.shape)}")
+    if max_keys is None:
+        max_keys = k.shape[0]
+    if out is None:
+        out = torch.empty(*q.shape[:-1], hd, dtype=q.dtype, device=q.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != q.dtype or out.device != q.device or tuple(out.shape) != (*q.shape[:-1], hd):
+        raise ValueError(f"cross_attention: out must be a {q.dtype} tensor of shape {(*q.shape[:-1], hd)} on {q.device}, got "
+                         f"{getattr(out, 'dtype', None)} {tuple(getattr(out, 'shape', ()))}")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not t.is_cuda:
+            raise ValueError(f"cross_attention: {name} must be a GPU tensor (there is no CPU path)")
+    if k.shape[0] == 0:  # no key rows at all: every range is empty (an empty tensor has no address to hand to the library)
+        return out.zero_()
+    out3 = out if out.dim() == 3 else out.unflatten(0, (B, T))
+    ops.cross_attention(q3[..., :hd].unflatten(-1, (heads, head_dim)), k, v, out3.unflatten(-1, (heads, head_dim)),
+                        key_offsets.contiguous(), key_counts.contiguous(), int(max_keys), head_dim ** -0.5 if scale is None else scale)
+    return out
