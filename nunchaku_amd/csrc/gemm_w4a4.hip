@@ -61,19 +61,19 @@
 #define SVDQ_PROBE_VROW 0
 #endif
 
-// generated main loops (tools/gen_gemm_loop2.py); the probe build substitutes option variants.  One file serves both dtypes: asm_tokens_{bf16,fp16}.h,
-// included in front of each asm statement, defines the token that differs
+// generated main loops and the wave-tile kernel's epilogue (tools/gen_gemm_loop2.py, tools/gen_gemm_loop3.py); the probe build substitutes option variants.
+// One file serves both dtypes: asm_tokens_{bf16,fp16}.h, included in front of each asm statement, defines the tokens that differ
 #ifndef SVDQ_LOOP_INC_8
 #define SVDQ_LOOP_INC_8 "gemm_loop2.inc"
 #endif
 #ifndef SVDQ_LOOP_INC_4
 #define SVDQ_LOOP_INC_4 "gemm_loop2_w4.inc"
 #endif
-#ifndef SVDQ_LOOP3_INC_BF16   // the 128 x 64 wave tile kernel: main loop and plain epilogue (tools/gen_gemm_loop3.py)
-#define SVDQ_LOOP3_INC_BF16 "gemm_loop3_bf16.inc"
-#define SVDQ_LOOP3_INC_FP16 "gemm_loop3_fp16.inc"
-#define SVDQ_EPI3_INC_BF16 "gemm_epi3_bf16.inc"
-#define SVDQ_EPI3_INC_FP16 "gemm_epi3_fp16.inc"
+#ifndef SVDQ_LOOP3_INC   // the 128 x 64 wave tile kernel: main loop and plain epilogue
+#define SVDQ_LOOP3_INC "gemm_loop3.inc"
+#endif
+#ifndef SVDQ_EPI3_INC
+#define SVDQ_EPI3_INC "gemm_epi3.inc"
 #endif
 
 namespace svdq {
@@ -1557,16 +1557,18 @@ __global__ __launch_bounds__(256, 1) void gemm_w4a4_wt128_kernel(const GemmParam
                 // a whole tile: loop + epilogue as ONE asm statement -- the accumulators (v[0:127]) and the epilogue operands (a[120:200]) never become compiler
                 // values (as outputs of one statement and inputs of the next, this clang moved all 128 accumulators through AGPRs around the schedule code)
                 if constexpr (DT == SVDQ_BF16) {
+#include "asm_tokens_bf16.h"
                     asm volatile(
-#include SVDQ_LOOP3_INC_BF16
+#include SVDQ_LOOP3_INC
                         SVDQ_PROBE_WT_MID_ASM
-#include SVDQ_EPI3_INC_BF16
+#include SVDQ_EPI3_INC
                         : SVDQ_PROBE_WT_MID_OUT SVDQ_LOOP3_IO : SVDQ_LOOP3_IN, SVDQ_EPI3_IN : SVDQ_LOOP3_CLOB, SVDQ_EPI3_CLOB, SVDQ_WT_CLOB_ACC, SVDQ_WT_CLOB_EP);
                 } else {
+#include "asm_tokens_fp16.h"
                     asm volatile(
-#include SVDQ_LOOP3_INC_FP16
+#include SVDQ_LOOP3_INC
                         SVDQ_PROBE_WT_MID_ASM
-#include SVDQ_EPI3_INC_FP16
+#include SVDQ_EPI3_INC
                         : SVDQ_PROBE_WT_MID_OUT SVDQ_LOOP3_IO : SVDQ_LOOP3_IN, SVDQ_EPI3_IN : SVDQ_LOOP3_CLOB, SVDQ_EPI3_CLOB, SVDQ_WT_CLOB_ACC, SVDQ_WT_CLOB_EP);
                 }
                 landed = min(3u, ncnt); // the epilogue waited for vmcnt(0) before its first store: the next tile's prefetch has landed, the next loop call need not drain the stores
@@ -1582,12 +1584,14 @@ __global__ __launch_bounds__(256, 1) void gemm_w4a4_wt128_kernel(const GemmParam
       "={v[64:79]}"(acc[1][0]), "={v[80:95]}"(acc[1][1]), "={v[96:111]}"(acc[1][2]), "={v[112:127]}"(acc[1][3]),                                          \
       "={a[120:135]}"(ep_a[0]), "={a[136:151]}"(ep_a[1]), "={a[152:167]}"(ep_a[2]), "={a[168:183]}"(ep_a[3]), "={a[184:199]}"(ep_u), "={a200}"(ep_b)
                 if constexpr (DT == SVDQ_BF16) {
+#include "asm_tokens_bf16.h"
                     asm volatile(
-#include SVDQ_LOOP3_INC_BF16
+#include SVDQ_LOOP3_INC
                         : SVDQ_LOOP3_ACC_OUT, SVDQ_LOOP3_IO : SVDQ_LOOP3_IN : SVDQ_LOOP3_CLOB);
                 } else {
+#include "asm_tokens_fp16.h"
                     asm volatile(
-#include SVDQ_LOOP3_INC_FP16
+#include SVDQ_LOOP3_INC
                         : SVDQ_LOOP3_ACC_OUT, SVDQ_LOOP3_IO : SVDQ_LOOP3_IN : SVDQ_LOOP3_CLOB);
                 }
                 landed = 0;
@@ -1647,12 +1651,14 @@ __global__ __launch_bounds__(256, 1) void gemm_w4a4_wt128_kernel(const GemmParam
 #define SVDQ_EPI3_EP_IN                                                                                                                                  \
       "{a[120:135]}"(ep_a[0]), "{a[136:151]}"(ep_a[1]), "{a[152:167]}"(ep_a[2]), "{a[168:183]}"(ep_a[3]), "{a[184:199]}"(ep_u), "{a200}"(ep_b)
                     if constexpr (DT == SVDQ_BF16) {
+#include "asm_tokens_bf16.h"
                         asm volatile(
-#include SVDQ_EPI3_INC_BF16
+#include SVDQ_EPI3_INC
                             : SVDQ_EPI3_ACC_IO : SVDQ_EPI3_EP_IN, SVDQ_EPI3_IN : "memory", "scc", "s84", "s85", "s70", "s71", "v215", SVDQ_EPI3_CLOB, SVDQ_WT_CLOB_T);
                     } else {
+#include "asm_tokens_fp16.h"
                         asm volatile(
-#include SVDQ_EPI3_INC_FP16
+#include SVDQ_EPI3_INC
                             : SVDQ_EPI3_ACC_IO : SVDQ_EPI3_EP_IN, SVDQ_EPI3_IN : "memory", "scc", "s84", "s85", "s70", "s71", "v215", SVDQ_EPI3_CLOB, SVDQ_WT_CLOB_T);
                     }
                     landed = min(3u, ncnt);

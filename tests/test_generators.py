@@ -1,8 +1,9 @@
 """The generated kernel sources in the tree are what their generators emit, and the attention iteration plan is complete.
 
-CPU-only: no GPU, no compiler.  (tools/gen_gemm_loop2.py -> gemm_loop2.inc, gemm_loop2_w4.inc: the GEMM main loops, each one
-file for bf16 and fp16 through the token splices of tools/asm_tokens.py; tools/gen_attn_step.py ->
-attention_step64.inc: the slot placement of one KV-tile iteration of the 4 x 64 attention kernel.)"""
+CPU-only: no GPU, no compiler.  (tools/gen_gemm_loop2.py -> gemm_loop2.inc, gemm_loop2_w4.inc: the GEMM main loops, and
+tools/gen_gemm_loop3.py -> gemm_loop3.inc, gemm_epi3.inc: loop and plain epilogue of the 128 x 64 wave tile kernel, each one file for
+bf16 and fp16 through the token splices of tools/asm_tokens.py;
+tools/gen_attn_loop.py -> attention_loop64_{bf16,fp16}.inc: the tile loop of the 4 x 64 attention kernel with its slot placement.)"""
 import os
 import re
 import sys
@@ -34,13 +35,32 @@ def test_neutral_gemm_loops_expand_to_each_dtypes_generated_lines():
     the LDS-DMA walk below reasons about is the text the compiler gets."""
     import asm_tokens
     import gen_gemm_loop2 as G2
+    import gen_gemm_loop3 as G3
+
+    def count(lines, dt, name):
+        return sum(ln.startswith(asm_tokens.tok(dt, name) + " ") for ln in lines)
 
     for name, nw in (("gemm_loop2.inc", 8), ("gemm_loop2_w4.inc", 4)):
         neutral = open(os.path.join(CSRC, name)).read().splitlines()
         for dt in asm_tokens.DTYPES:
             lines = asm_tokens.expand(neutral, dt)
             assert lines == G2.Gen(dt, "", nw).build(), (name, dt)
-            assert sum(ln.startswith(asm_tokens.tok(dt, "MFMA_K8") + " ") for ln in lines) == 3 * 8 + 3  # 8 per ring body, 1 per ring entry
+            assert count(lines, dt, "MFMA_K8") == 3 * 8 + 3  # 8 per ring body, 1 per ring entry
+    neutral = open(os.path.join(CSRC, "gemm_loop3.inc")).read().splitlines()
+    for dt in asm_tokens.DTYPES:
+        lines = asm_tokens.expand(neutral, dt)
+        assert lines == G3.Gen3(dt, G3.PRODUCT_OPTS).build(), dt
+        assert count(lines, dt, "MFMA_K8") == 4 * 16 + 4 and count(lines, dt, "MFMA_K16") == 0  # 16 per ring body, 1 per ring entry
+    neutral = open(os.path.join(CSRC, "gemm_epi3.inc")).read().splitlines()
+    for dt in asm_tokens.DTYPES:
+        lines = asm_tokens.expand(neutral, dt)
+        assert lines == G3.GenEpi3(dt).build(), dt
+        assert count(lines, dt, "MFMA_K16") == 8 + 16 and count(lines, dt, "CVT_PK") == 64 + 64   # low-rank activations (plain + scaled path), outputs
+        assert sum(ln.endswith(", " + asm_tokens.tok(dt, "ONE")) for ln in lines) == 1
+        # the clamp: one constant and 64 min / max pairs for fp16; the same 129 lines as comments for bf16
+        clamp = [ln for ln in lines if "v_pk_min_f16" in ln or "v_pk_max_f16" in ln or "0x7bff7bff" in ln]
+        assert [ln.lstrip("; ").split()[0] for ln in clamp] == ["s_mov_b32"] + ["v_pk_min_f16", "v_pk_max_f16"] * 64
+        assert all(ln.startswith("; ") == (dt == "bf16") for ln in clamp)
 
 
 def test_a_dtype_specific_instruction_without_a_token_is_refused(tmp_path):
@@ -56,6 +76,38 @@ def test_a_dtype_specific_instruction_without_a_token_is_refused(tmp_path):
         assert not (tmp_path / "bad.inc").exists()
     else:
         raise AssertionError("a line only fp16 has went unnoticed")
+    # ... nor is it when bf16 carries it as a comment, as long as the generator has not declared it
+    lines["bf16"].append("; v_pk_min_f16 v1, v1, s99")
+    try:
+        asm_tokens.write_neutral(str(tmp_path / "bad.inc"), "a test", lines)
+    except AssertionError:
+        assert not (tmp_path / "bad.inc").exists()
+    else:
+        raise AssertionError("an undeclared line only fp16 has went unnoticed")
+
+
+def test_a_declared_fp16_only_line_is_a_comment_for_bf16(tmp_path):
+    """The one way a file may hold a line for one dtype alone: the generator emits it through fp16_only() and declares its index.  bf16 then gets
+    a comment where fp16 gets the instruction; a declared index whose line was not emitted that way is refused."""
+    import asm_tokens
+
+    clamp = "v_pk_min_f16 v1, v1, s99"
+    lines = {dt: [f"{asm_tokens.tok(dt, 'CVT_PK')} v1, v2, v3", asm_tokens.fp16_only(dt, clamp), "s_nop 1"] for dt in asm_tokens.DTYPES}
+    assert asm_tokens.write_neutral(str(tmp_path / "ok.inc"), "a test", lines, {1}) == 3
+    neutral = (tmp_path / "ok.inc").read_text().splitlines()
+    assert asm_tokens.expand(neutral, "fp16") == ["v_cvt_pk_f16_f32 v1, v2, v3", clamp, "s_nop 1"]
+    bf16 = asm_tokens.expand(neutral, "bf16")
+    assert bf16 == ["v_cvt_pk_bf16_f32 v1, v2, v3", "; " + clamp, "s_nop 1"]
+    assert [ln for ln in bf16 if not ln.startswith(";")] == ["v_cvt_pk_bf16_f32 v1, v2, v3", "s_nop 1"]   # no instruction where fp16 has the clamp
+    for dt in asm_tokens.DTYPES:   # a declared index whose line one dtype did not emit through fp16_only(): refused
+        bad = {d: list(v) for d, v in lines.items()}
+        bad[dt][1] = clamp if dt == "bf16" else "; " + clamp
+        try:
+            asm_tokens.write_neutral(str(tmp_path / "bad.inc"), "a test", bad, {1})
+        except AssertionError:
+            assert not (tmp_path / "bad.inc").exists()
+        else:
+            raise AssertionError(f"a declared line that {dt} did not emit through fp16_only() went unnoticed")
 
 
 def test_attention_loops_in_tree_match_their_generator(tmp_path):
@@ -311,13 +363,12 @@ def test_wave_tile_loop_and_epilogue_in_tree_match_their_generator(tmp_path):
     """round 6: the 128 x 64 wave tile kernel's loop (tools/gen_gemm_loop3.py, product options) and its generated epilogue"""
     import gen_gemm_loop3 as G3
 
-    for dt, mfma in (("bf16", "v_mfma_f32_32x32x16_bf16"), ("fp16", "v_mfma_f32_32x32x16_f16")):
-        out = tmp_path / f"gemm_loop3_{dt}.inc"
-        G3.emit(str(out), mfma, G3.PRODUCT_OPTS)
-        assert out.read_text() == open(os.path.join(CSRC, out.name)).read(), f"{out.name} is stale: run python tools/gen_gemm_loop3.py"
-        out = tmp_path / f"gemm_epi3_{dt}.inc"
-        G3.emit_epilogue(str(out), dt)
-        assert out.read_text() == open(os.path.join(CSRC, out.name)).read(), f"{out.name} is stale: run python tools/gen_gemm_loop3.py"
+    out = tmp_path / "gemm_loop3.inc"
+    G3.emit(str(out), G3.PRODUCT_OPTS)
+    assert out.read_text() == open(os.path.join(CSRC, out.name)).read(), f"{out.name} is stale: run python tools/gen_gemm_loop3.py"
+    out = tmp_path / "gemm_epi3.inc"
+    G3.emit_epilogue(str(out))
+    assert out.read_text() == open(os.path.join(CSRC, out.name)).read(), f"{out.name} is stale: run python tools/gen_gemm_loop3.py"
 
 
 def _reg_range(tok):
@@ -334,11 +385,18 @@ def test_wave_tile_loop_register_plan_and_dma_discipline():
     36 LDS reads and the K-step's 10 LDS-DMA instructions; an LDS-DMA never issues right behind its M0 write; the registers the text names stay inside the plan the
     C++ side pins and clobbers (acc v[0:127], P / S v[128:191], inputs v[192:208] + the operand-load temporaries v[212:214], fragments / tuples a[0:119], the
     epilogue operands a[120:200]); the product MFMA is the unscaled form and the scale tile the K = 8 form (round 6)."""
+    import asm_tokens
+
+    for dt in asm_tokens.DTYPES:
+        _walk_wave_tile_loop(dt)
+
+
+def _walk_wave_tile_loop(dt):
+    import asm_tokens
     import gen_gemm_loop3 as G3
 
-    g = G3.Gen3("v_mfma_f32_32x32x16_bf16", G3.PRODUCT_OPTS)
-    lines = [ln for ln in g.build() if not ln.startswith(";")]
-    assert not any("v_mfma_scale" in ln or "32x32x16_bf16" in ln for ln in lines)
+    lines = [ln for ln in G3.Gen3(dt, G3.PRODUCT_OPTS).build() if not ln.startswith(";")]
+    assert not any("v_mfma_scale" in ln or "32x32x16" in ln for ln in lines)
     since_m0 = None
     for ln in lines:
         op = ln.split()[0]
@@ -367,7 +425,7 @@ def test_wave_tile_loop_register_plan_and_dma_discipline():
     for b, e in zip(bodies, bodies[1:] + [end]):
         body = [ln for ln in lines[b:e] if not ln.endswith(":")]
         ops = [ln.split()[0] for ln in body]
-        assert ops.count("v_mfma_f32_32x32x64_f8f6f4") == 16 and ops.count("v_mfma_f32_32x32x8bf16_1k") == 16
+        assert ops.count("v_mfma_f32_32x32x64_f8f6f4") == 16 and ops.count(asm_tokens.tok(dt, "MFMA_K8")) == 16
         fm = [ln for ln in body if ln.startswith("v_fmac_f32")]
         assert len(fm) == 256
         dst = [int(re.match(r"v_fmac_f32 v(\d+),", ln).group(1)) for ln in fm]

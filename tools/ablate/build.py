@@ -36,11 +36,9 @@ def build(opts: str = "", opts3: str = ""):
     os.makedirs(GEN, exist_ok=True)
     o3 = G3.PRODUCT_OPTS + "+stamp" + ("+" + opts3 if opts3 else "")
     s3 = "_" + o3.replace("+", "_")
-    for dt, mf in (("bf16", "v_mfma_f32_32x32x16_bf16"), ("fp16", "v_mfma_f32_32x32x16_f16")):
-        G3.emit(os.path.join(GEN, f"gemm_loop3_{dt}{s3}.inc"), mf, o3)
-        G3.emit_epilogue(os.path.join(GEN, f"gemm_epi3_{dt}{s3}.inc"), dt, o3)
-        flags += [f'-DSVDQ_LOOP3_INC_{dt.upper()}="gemm_loop3_{dt}{s3}.inc"', f'-DSVDQ_EPI3_INC_{dt.upper()}="gemm_epi3_{dt}{s3}.inc"']
-    flags.append(f"-I{GEN}")
+    G3.emit(os.path.join(GEN, f"gemm_loop3{s3}.inc"), o3)
+    G3.emit_epilogue(os.path.join(GEN, f"gemm_epi3{s3}.inc"), o3)
+    flags += [f'-DSVDQ_LOOP3_INC="gemm_loop3{s3}.inc"', f'-DSVDQ_EPI3_INC="gemm_epi3{s3}.inc"', f"-I{GEN}"]
     if opts3:
         suffix = "_wt_" + opts3.replace("+", "_")
     if opts:

@@ -4,7 +4,7 @@
 // product's tile, LDS stage image, operand images (F6 / S), XCD-aware persistent schedule (whole tiles, whole rounds) and cross-tile prefetch protocol --
 // with the plain epilogue (no bias, no low-rank branch: the 16-bit store only), so that its output can be compared BIT FOR BIT with svdq_gemm_w4a4 of the
 // product library on the same operands (R = 0, bias = NULL, geometry 1) and timed beside it on the same box.
-//   build: python tools/gen_gemm_loop3.py && hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Inunchaku_amd/csrc -Itools/ablate/gen -o tools/ablate/gemm128_probe tools/ablate/gemm128_probe.hip -ldl
+//   build: python tools/gen_gemm_loop3.py && hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Itools/ablate/gen -Inunchaku_amd/csrc -o tools/ablate/gemm128_probe tools/ablate/gemm128_probe.hip -ldl
 //   run:   tools/ablate/gemm128_probe --shape 4608 3072 3072 [--fp16] [--grid G] [--lib path/to/libsvdq_amd.so]
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -19,11 +19,8 @@
 
 #include "svdq_common.h"
 
-#ifndef SVDQ_LOOP3_BF16
-#define SVDQ_LOOP3_BF16 "gemm_loop3_bf16.inc"
-#endif
-#ifndef SVDQ_LOOP3_FP16
-#define SVDQ_LOOP3_FP16 "gemm_loop3_fp16.inc"
+#ifndef SVDQ_LOOP3_INC   // one file for both dtypes: asm_tokens_{bf16,fp16}.h in front of the asm statement defines the tokens that differ
+#define SVDQ_LOOP3_INC "gemm_loop3.inc"
 #endif
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); exit(1); } } while (0)
@@ -132,12 +129,14 @@ __global__ __launch_bounds__(256, 1) void gemm128_kernel(const P128 p) {
       "{s[62:63]}"(nA), "{s[64:65]}"(nX1), "{s[66:67]}"(nX2), "{s68}"(landed)                                                                     \
     : "memory", "scc", "m0", "s51", "s53", "s55", "s56", "s57", "s61", "s84", "s85", "s86", "s87", CLOB_V, CLOB_A
             if constexpr (DT == SVDQ_BF16) {
+#include "asm_tokens_bf16.h"
                 asm volatile(
-#include SVDQ_LOOP3_BF16
+#include SVDQ_LOOP3_INC
                     LOOP3_OPERANDS);
             } else {
+#include "asm_tokens_fp16.h"
                 asm volatile(
-#include SVDQ_LOOP3_FP16
+#include SVDQ_LOOP3_INC
                     LOOP3_OPERANDS);
             }
             ring = (ring + (kp_s % NSTAGE) * STAGE_BYTES) % (NSTAGE * STAGE_BYTES);

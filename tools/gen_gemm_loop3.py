@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
-"""PROBE generator (round 6, VERDICT r5 #2 i): the W4A4 main loop with a 128 x 64 wave tile, ONE wave per SIMD.
+"""The W4A4 main loop with a 128 x 64 wave tile, ONE wave per SIMD.
 
-    python tools/gen_gemm_loop3.py        # writes tools/ablate/gen/gemm_loop3_{bf16,fp16}.inc (used by tools/ablate/gemm128_probe.hip only)
+    python tools/gen_gemm_loop3.py        # writes nunchaku_amd/csrc/gemm_loop3.inc and gemm_epi3.inc (gemm_w4a4.hip: gemm_w4a4_wt128_kernel)
+    SVDQ_GEN3_OPTS=<opts> python tools/gen_gemm_loop3.py    # probe variants: tools/ablate/gen/gemm_{loop3,epi3}[_<opts>].inc (tools/ablate/build128.sh)
+
+Each file serves bf16 and fp16: the dtype-dependent mnemonics and constants are macro splices, and the lines only fp16 has (the epilogue's clamp) sit
+behind the SVDQ_ASM_FP16_ONLY splice, which makes them comments for bf16 (tools/asm_tokens.py).
 
 Same arithmetic as tools/gen_gemm_loop2.py (one FP6 product MFMA + one 16-bit scale-tile MFMA + 16 v_fmac per 32 x 32 x 64 tile-group, groups in
 ascending order: bit-identical accumulators), same workgroup tile (256 x 128), same LDS stage image (8 A chunks, 4 W chunks, two scale images = 38 912 B,
@@ -19,6 +23,8 @@ against 16 + 128 + 24 + 5 for the 64 x 64 wave tile: per tile-group 20.9 vector-
 four waves at the K-step rendezvous instead of eight.  325 registers per wave: one wave per SIMD.
 """
 import os
+
+import asm_tokens
 
 CHUNK, PLANE = 3072, 1024
 NSTAGE = 3
@@ -64,8 +70,8 @@ def sr(a, n=1):
 
 
 class Gen3:
-    def __init__(self, smfma, opts=""):
-        self.smfma = smfma
+    def __init__(self, dt, opts=""):
+        self.dt = dt           # "bf16" | "fp16"
         self.opts = set(o for o in opts.split("+") if o)
         self.lines = []
         self.label = 0
@@ -125,9 +131,8 @@ class Gen3:
             # the legacy K = 8 form on the first two registers of each tuple (k-slots 0 and 4 hold the scale: the same S = 2 ws as, bit for bit).  Same 8 passes on
             # gfx950 (tools/ablate/mfma_k8_probe: 32.6 cycles either way), half the operand registers read: 130 -> 126 / 114 -> 110 cycles per tile-group on the
             # probe (profiles/r6_gemm_wave_tile_probe.txt section 5).  "k16": the K = 16 form of rounds 1-5
-            op = "v_mfma_f32_32x32x8bf16_1k" if self.smfma.endswith("bf16") else "v_mfma_f32_32x32x8f16"
-            return f"{op} {vr(SBUF[dst_buf], 16)}, {ar(SCL[buf] + 4 * ni, 2)}, {ar(SCL[buf] + 8 + 4 * mi, 2)}, 0"
-        return f"{self.smfma} {vr(SBUF[dst_buf], 16)}, {ar(SCL[buf] + 4 * ni, 4)}, {ar(SCL[buf] + 8 + 4 * mi, 4)}, 0"
+            return f"{asm_tokens.tok(self.dt, 'MFMA_K8')} {vr(SBUF[dst_buf], 16)}, {ar(SCL[buf] + 4 * ni, 2)}, {ar(SCL[buf] + 8 + 4 * mi, 2)}, 0"
+        return f"{asm_tokens.tok(self.dt, 'MFMA_K16')} {vr(SBUF[dst_buf], 16)}, {ar(SCL[buf] + 4 * ni, 4)}, {ar(SCL[buf] + 8 + 4 * mi, 4)}, 0"
 
     def fma(self, t, pb, lo, hi):
         return [f"v_fmac_f32 {vr(ACC + 16 * t + r)}, {vr(PBUF[pb] + r)}, {vr(SBUF[pb] + r)}" for r in range(lo, hi)]
@@ -499,6 +504,7 @@ class GenEpi3:
         self.dt = dt           # "bf16" | "fp16"
         self.opts = set(o for o in opts.split("+") if o)
         self.lines = []
+        self.fp16_only = set()   # indices of the lines only fp16 has
         self.label = 0
 
     def stamp(self, i):
@@ -511,17 +517,20 @@ class GenEpi3:
     def e(self, s):
         self.lines.append(s)
 
+    def e16(self, s):
+        """a line only fp16 has (bf16: the same line as a comment)"""
+        self.fp16_only.add(len(self.lines))
+        self.e(asm_tokens.fp16_only(self.dt, s))
+
     def new_label(self, tag):
         self.label += 1
         return f".Lsvdq3e_{tag}{self.label}_%="
 
     def mfma(self, t, a, b):
-        op = "v_mfma_f32_32x32x16_bf16" if self.dt == "bf16" else "v_mfma_f32_32x32x16_f16"
-        return f"{op} {vr(ACC + 16 * t, 16)}, {a}, {b}, {vr(ACC + 16 * t, 16)}"
+        return f"{asm_tokens.tok(self.dt, 'MFMA_K16')} {vr(ACC + 16 * t, 16)}, {a}, {b}, {vr(ACC + 16 * t, 16)}"
 
     def cvt(self, dst, a, b):
-        op = "v_cvt_pk_bf16_f32" if self.dt == "bf16" else "v_cvt_pk_f16_f32"
-        return f"{op} {vr(dst)}, {vr(a)}, {vr(b)}"
+        return f"{asm_tokens.tok(self.dt, 'CVT_PK')} {vr(dst)}, {vr(a)}, {vr(b)}"
 
     def build(self):
         e = self.e
@@ -532,7 +541,7 @@ class GenEpi3:
         e(f"s_bitcmp1_b32 {sr(E_S_FLAGS)}, 1")
         e(f"s_cbranch_scc0 {Lnob}")
         e(f"v_accvgpr_read_b32 {vr(E_T)}, {ar(A_EP + 80)}")
-        e(f"v_mov_b32 {vr(E_T + 1)}, {'0x3f80' if self.dt == 'bf16' else '0x3c00'}")
+        e(f"v_mov_b32 {vr(E_T + 1)}, {asm_tokens.tok(self.dt, 'ONE')}")
         e(f"v_mov_b32 {vr(E_T + 2)}, 0")
         for ni in range(2):
             for k in range(1, 4):
@@ -609,8 +618,7 @@ class GenEpi3:
             for mi in range(1, 4):
                 e(f"s_mul_i32 {sr(E_S_TMP)}, {sr(E_S_RTB)}, {mi}")
                 e(f"v_add_u32 {vr(E_OFF[mi])}, {sr(E_S_TMP)}, {vr(E_OFF[0])}")
-        if self.dt == "fp16":
-            e(f"s_mov_b32 {sr(E_S_TMP)}, 0x7bff7bff")     # (65504.0, 65504.0) as an fp16 pair
+        self.e16(f"s_mov_b32 {sr(E_S_TMP)}, 0x7bff7bff")     # (65504.0, 65504.0) as an fp16 pair
         for mi in range(4):
             k = 0
             for ni in range(2):
@@ -619,16 +627,13 @@ class GenEpi3:
                     for half in range(2):          # x (columns 8 c + 4 h + e of c = 2 j), y (c = 2 j + 1)
                         for d in range(2):
                             a0 = ACC + 16 * t + (2 * j + half) * 4 + 2 * d
-                            if self.dt == "fp16":
-                                # convert, then clamp the fp16 PAIR as the reference does (gemm_base.cuh:692-693) and cvt_clamp_pk_fp16() of the C++ epilogue:
-                                # min with 65504 FIRST, then max with -65504 -- v_pk_min / v_pk_max return the non-NaN operand, so a NaN becomes +65504
-                                # (one v_med3_f32 per element returned min3 = -65504 for it).  Same instruction count as the two v_med3_f32.
-                                o = E_OUT + 4 * k + 2 * half + d
-                                e(self.cvt(o, a0, a0 + 1))
-                                e(f"v_pk_min_f16 {vr(o)}, {vr(o)}, {sr(E_S_TMP)}")
-                                e(f"v_pk_max_f16 {vr(o)}, {vr(o)}, {sr(E_S_TMP)} neg_lo:[0,1] neg_hi:[0,1]")
-                            else:
-                                e(self.cvt(E_OUT + 4 * k + 2 * half + d, a0, a0 + 1))
+                            # convert; fp16 then clamps the PAIR as the reference does (gemm_base.cuh:692-693) and cvt_clamp_pk_fp16() of the C++ epilogue:
+                            # min with 65504 FIRST, then max with -65504 -- v_pk_min / v_pk_max return the non-NaN operand, so a NaN becomes +65504
+                            # (one v_med3_f32 per element returned min3 = -65504 for it).  Same instruction count as the two v_med3_f32.
+                            o = E_OUT + 4 * k + 2 * half + d
+                            e(self.cvt(o, a0, a0 + 1))
+                            self.e16(f"v_pk_min_f16 {vr(o)}, {vr(o)}, {sr(E_S_TMP)}")
+                            self.e16(f"v_pk_max_f16 {vr(o)}, {vr(o)}, {sr(E_S_TMP)} neg_lo:[0,1] neg_hi:[0,1]")
                     k += 1
             e("s_nop 1")
             for k in range(4):
@@ -665,46 +670,29 @@ class GenEpi3:
         return self.lines
 
 
-def emit_epilogue(path, dt, opts=""):
-    lines = GenEpi3(dt, opts).build()
-    with open(path, "w") as f:
-        f.write("// GENERATED by tools/gen_gemm_loop3.py (plain epilogue of the 128 x 64 wave tile kernel) -- do not edit.\n")
-        for ln in lines:
-            f.write('"' + ln + '\\n"\n')
-    return len(lines)
+def emit_epilogue(path, opts=""):
+    gens = {dt: GenEpi3(dt, opts) for dt in asm_tokens.DTYPES}
+    built = {dt: g.build() for dt, g in gens.items()}
+    assert gens["bf16"].fp16_only == gens["fp16"].fp16_only
+    return asm_tokens.write_neutral(path, "tools/gen_gemm_loop3.py (plain epilogue of the 128 x 64 wave tile kernel)", built, gens["fp16"].fp16_only)
 
 
-def emit(path, smfma, opts=""):
-    lines = Gen3(smfma, opts).build()
-    with open(path, "w") as f:
-        f.write(f"// GENERATED by tools/gen_gemm_loop3.py (128 x 64 wave tile, one wave per SIMD; options {opts!r}) -- do not edit.\n")
-        for ln in lines:
-            f.write('"' + ln + '\\n"\n')
-    return len(lines)
+def emit(path, opts=""):
+    return asm_tokens.write_neutral(path, f"tools/gen_gemm_loop3.py (128 x 64 wave tile, one wave per SIMD; options {opts!r})",
+                                    {dt: Gen3(dt, opts).build() for dt in asm_tokens.DTYPES})
 
 
 PRODUCT_OPTS = "b2+ep"   # the loop the library ships: ring of four, barrier every other K-step, DMAs spread over the tile-group slots
 
 
 if __name__ == "__main__":
-    here = os.path.dirname(os.path.abspath(__file__))
     opts = os.environ.get("SVDQ_GEN3_OPTS")
-    if opts is None:
-        # the product loops: nunchaku_amd/csrc/gemm_loop3_{bf16,fp16}.inc (included by gemm_w4a4.hip: gemm_w4a4_wt128_kernel)
-        root = os.path.join(os.path.dirname(here), "nunchaku_amd", "csrc")
-        n = emit(os.path.join(root, "gemm_loop3_bf16.inc"), "v_mfma_f32_32x32x16_bf16", PRODUCT_OPTS)
-        emit(os.path.join(root, "gemm_loop3_fp16.inc"), "v_mfma_f32_32x32x16_f16", PRODUCT_OPTS)
-        print(f"wrote nunchaku_amd/csrc/gemm_loop3_{{bf16,fp16}}.inc ({n} lines each, options {PRODUCT_OPTS!r})")
-        n = emit_epilogue(os.path.join(root, "gemm_epi3_bf16.inc"), "bf16")
-        emit_epilogue(os.path.join(root, "gemm_epi3_fp16.inc"), "fp16")
-        print(f"wrote nunchaku_amd/csrc/gemm_epi3_{{bf16,fp16}}.inc ({n} lines)")
-    else:
-        # probe variants (tools/ablate/build128.sh): tools/ablate/gen/gemm_loop3_{bf16,fp16}[_<opts>].inc
-        root = os.path.join(here, "ablate", "gen")
-        os.makedirs(root, exist_ok=True)
-        sfx = ("_" + opts.replace("+", "_")) if opts else ""
-        n = emit(os.path.join(root, f"gemm_loop3_bf16{sfx}.inc"), "v_mfma_f32_32x32x16_bf16", opts)
-        emit(os.path.join(root, f"gemm_loop3_fp16{sfx}.inc"), "v_mfma_f32_32x32x16_f16", opts)
-        emit_epilogue(os.path.join(root, f"gemm_epi3_bf16{sfx}.inc"), "bf16", opts)
-        emit_epilogue(os.path.join(root, f"gemm_epi3_fp16{sfx}.inc"), "fp16", opts)
-        print(f"wrote tools/ablate/gen/gemm_{{loop3,epi3}}_{{bf16,fp16}}{sfx}.inc ({n} lines each)")
+    if opts is None:   # the product loop and epilogue (included by gemm_w4a4.hip: gemm_w4a4_wt128_kernel)
+        where, sfx, opts_loop, opts_epi = "nunchaku_amd/csrc", "", PRODUCT_OPTS, ""
+    else:              # probe variants (tools/ablate/build128.sh)
+        where, sfx, opts_loop, opts_epi = "tools/ablate/gen", ("_" + opts.replace("+", "_")) if opts else "", opts, opts
+    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), where)
+    os.makedirs(root, exist_ok=True)
+    n = emit(os.path.join(root, f"gemm_loop3{sfx}.inc"), opts_loop)
+    ne = emit_epilogue(os.path.join(root, f"gemm_epi3{sfx}.inc"), opts_epi)
+    print(f"wrote {where}/gemm_loop3{sfx}.inc ({n} lines, options {opts_loop!r}), gemm_epi3{sfx}.inc ({ne} lines)")
