@@ -641,6 +641,60 @@ typedef struct svdq_cross_attention_args {
 int svdq_cross_attention(const svdq_cross_attention_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * SANA block glue (the element-wise passes between the three layers of a SANA block; added WITHOUT a version bump: one new symbol and a
+ * new args struct, nothing existing changes, so SVDQ_ABI_VERSION stays 24.  reference: SanaLinearTransformerBlock::forward,
+ * src/SanaModel.cpp:234-322 -- a copy of timestep, one add of scale_shift_table, two LayerNorms and five mul_add_batch launches per block;
+ * here one row pass does the gated residual, the LayerNorm of the result, the next layer's per-sample modulation and the padding to the
+ * GEMM operand width).  Rows are B * T tokens, row r belongs to sample b = r / T.  round16 = round to nearest even to `dtype`;
+ * clip = min(max(., -65504), 65504) for SVDQ_FP16 and the identity for SVDQ_BF16 (mul_add_kernel, misc_kernels_impl.cuh:60-63); everything
+ * between two roundings is fp32:
+ *   mod(tab, i)[b, c] = clip(round16(timestep[b, i, c] + tab[i, c]))
+ *   t = res                                                      (a NULL)
+ *   t = clip(round16(a + res))                                   (a given, gate_row < 0: the cross-attention residual)
+ *   t = clip(round16(round16(a * g) + res)),  g = mod(gate_table, gate_row)[b]
+ *   out[r, :C] = t;  out[r, C:C_pad] = +0                        (if out)
+ *   mean, rstd = the two-pass fp32 statistics of the C stored values t, formed as svdq_residual_gate_stats forms them
+ *   stats[r] = (mean, rstd)                                      (if stats)
+ *   n = round16((t - mean) * rstd)
+ *   s = round16(mod(mod_table, scale_row)[b] + 1);  h = mod(mod_table, shift_row)[b]
+ *   out_mod[r, :C] = clip(round16(round16(n * s) + h));  out_mod[r, C:C_pad] = +0       (if out_mod)
+ * These are the rounding points of the reference's SEPARATE operations (SanaModel.cpp:255,272,278,292,304,310;
+ * layernorm_kernels_impl.cuh:14,132).  nvcc is free to contract the reference's `x * (scale + 1) + bias` into one fma, which drops the
+ * rounding of the product; this project fixes the reading above (the library is built with -ffp-contract=off).
+ * gate_table and mod_table are separate [6, C] tables: the pass behind the feed-forward gates with its own block's table and modulates
+ * with the next block's.  timestep is [B, 6, C] with batch stride timestep_bs (elements), row i of a sample C elements behind row i - 1.
+ * Every tensor has its own row stride (a is the first C columns of a C_pad-wide GEMM output).  C % 8 == 0, C <= C_pad, C_pad % 8 == 0,
+ * ceil(C_pad / 512) in {1..8, 12, 16, 24, 32} (else SVDQ_E_UNSUPPORTED).  out may alias res when ld_out == ld_res; out_mod may alias nothing
+ * that is read.  Nothing is read outside res[:, :C], a[:, :C], the two tables and the rows of timestep[b] that are used; nothing is written
+ * outside the C_pad columns of the two outputs or past row B * T.  One launch, no workspace, no atomics, no synchronisation: the call can
+ * be captured and two calls on the same inputs are bit-identical.
+ * Validation (no launch), SVDQ_E_INVALID: NULL args or res, none of out / out_mod / stats, a gate row without a, a gate / scale / shift row
+ * outside 0..5, out_mod without timestep or mod_table, a gate without timestep or gate_table, B / T / C < 1, C > C_pad, a stride smaller
+ * than its row, pointers not 16-byte aligned (stats: 8-byte) or a stride that is not a multiple of 8, unknown dtype, an eps that is
+ * negative or not finite, B * T > 2^31 - 1.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct svdq_sana_glue_args {
+    const void *res;        /* [B * T, C] 16-bit, row stride ld_res */
+    const void *a;          /* [B * T, C], row stride ld_a, or NULL */
+    const void *timestep;   /* [B, 6, C], batch stride timestep_bs; NULL when neither a gate nor out_mod is asked for */
+    const void *gate_table; /* [6, C] contiguous, or NULL (no gate) */
+    const void *mod_table;  /* [6, C] contiguous, or NULL (no out_mod) */
+    void *out;              /* [B * T, C_pad], row stride ld_out, or NULL */
+    void *out_mod;          /* [B * T, C_pad], row stride ld_mod, or NULL */
+    float *stats;           /* [B * T, 2] fp32 or NULL */
+    int64_t timestep_bs;    /* in elements, >= 6 * C, a multiple of 8 */
+    int32_t ld_res, ld_a, ld_out, ld_mod; /* in elements */
+    int32_t B, T, C, C_pad;
+    int32_t gate_row;       /* 0..5, or < 0: no gate */
+    int32_t scale_row, shift_row; /* 0..5 (looked at only with out_mod) */
+    int32_t dtype;
+    float eps;
+    int32_t reserved;
+} svdq_sana_glue_args;
+
+int svdq_sana_glue(const svdq_sana_glue_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * AWQ W4A16 GEMV (reference: ops.gemv_awq, nunchaku/csrc/ops.h:123-145 -> src/kernels/awq/gemv_awq.cu:100-286;
  * module nunchaku/models/linear.py:277-414).  The AdaLayerNormZero modulation projections of every block.
  *   out[m, n] = round16( sum_k round16( round16(q[n,k]*scales[k/64,n] + zeros[k/64,n]) * x[m,k] ) ) (+ bias[n])

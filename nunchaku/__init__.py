@@ -7,15 +7,16 @@ positional signatures, reference-sized opaque buffers and checkpoint-layout para
 reference's own ``ops/*.py`` / ``models/linear.py`` callers run against it unchanged (tests/test_nunchaku_shim.py).
 ``from nunchaku import NunchakuT5EncoderModel`` is the 4-bit T5 text encoder of the FLUX pipelines (AWQ W4A16 group-128
 linears on ``ops.gemm_awq``); transformers is imported on first access of that name, so ``import nunchaku`` works without it.
-Model families outside these (SANA, Z-Image) are not part of this package.
+``from nunchaku import NunchakuSanaTransformer2DModel`` is SANA (``nunchaku_amd/models/transformer_sana.py``).  Z-Image is not part of this package.
 """
 from .models import (  # noqa: F401
     NunchakuFluxTransformer2dModel,
     NunchakuFluxTransformer2DModelV2,
     NunchakuQwenImageTransformer2DModel,
+    NunchakuSanaTransformer2DModel,
 )
 
-__all__ = ["NunchakuFluxTransformer2dModel", "NunchakuFluxTransformer2DModelV2", "NunchakuQwenImageTransformer2DModel"]  # (+ NunchakuT5EncoderModel, lazily)
+__all__ = ["NunchakuFluxTransformer2dModel", "NunchakuFluxTransformer2DModelV2", "NunchakuQwenImageTransformer2DModel", "NunchakuSanaTransformer2DModel"]  # (+ NunchakuT5EncoderModel, lazily)
 
 
 def __getattr__(name):

@@ -3,4 +3,5 @@ from .transformers import (  # noqa: F401
     NunchakuFluxTransformer2dModel,
     NunchakuFluxTransformer2DModelV2,
     NunchakuQwenImageTransformer2DModel,
+    NunchakuSanaTransformer2DModel,
 )

@@ -1144,6 +1144,45 @@ class _Ops:
         a.dtype, a.scale = _DT[q.dtype], float(scale)
         _lib.check(lib.svdq_cross_attention(C.byref(a), _stream()), "cross_attention")
 
+    @staticmethod
+    def sana_glue(res, a, timestep, gate_table, mod_table, out, out_mod, stats, T, C_feat, C_pad, lds, gate_row=-1, scale_row=0, shift_row=0, eps=1e-6):
+        """Extension (SANA): the glue pass of a SANA block (``svdq_sana_glue``): the gated residual ``t`` of ``res`` and ``a``, written to ``out``,
+        its LayerNorm statistics to ``stats`` and the LayerNorm modulated per sample with rows ``scale_row`` / ``shift_row`` of
+        ``timestep[b] + mod_table`` to ``out_mod``; both outputs ``C_pad`` wide with zeros behind column ``C_feat``.  ``res`` / ``a`` / ``out`` /
+        ``out_mod``: ``[B, T, .]`` or ``[B * T, .]`` views of token rows with unit column stride, the samples ``T`` rows apart; ``lds``: their four
+        row strides in elements (0 for an absent tensor) -- ``ops.elementwise.sana_glue`` checks the shapes and forms them; ``timestep``:
+        ``[B, 6, C_feat]`` with a contiguous ``[6, C_feat]`` per sample; the tables: contiguous ``[6, C_feat]``; ``stats``: float32 ``[B * T, 2]``.
+        What is None here and required there the library judges."""
+        op, lib, args = "sana_glue", _lib.load(), _lib.SanaGlueArgs()
+        if res is None or res.dtype not in _DT:
+            raise ValueError(f"{op}: res must be a 16-bit view of token rows")
+        dtype = res.dtype
+        M = res.numel() // res.shape[-1]
+        for name, t in (("res", res), ("a", a), ("out", out), ("out_mod", out_mod)):
+            if t is not None and (t.dtype != dtype or t.stride(-1) != 1):
+                raise ValueError(f"{op}: {name} must have unit column stride and the dtype of res")
+        B = 1
+        if timestep is not None:
+            if (timestep.dim() != 3 or timestep.shape[1] != 6 or timestep.shape[2] != C_feat or timestep.dtype != dtype or timestep.stride(2) != 1
+                    or timestep.stride(1) != C_feat):
+                raise ValueError(f"{op}: timestep must be [B, 6, {C_feat}] in the dtype of res with a contiguous [6, {C_feat}] per sample")
+            B = timestep.shape[0]
+        if T < 1 or M % T or (timestep is not None and M != B * T):
+            raise ValueError(f"{op}: {M} rows are not B={B} samples of T={T} tokens")
+        for name, t in (("gate_table", gate_table), ("mod_table", mod_table)):
+            if t is not None and (t.dim() != 2 or t.shape[0] != 6 or t.shape[1] != C_feat or t.dtype != dtype or not t.is_contiguous()):
+                raise ValueError(f"{op}: {name} must be a contiguous [6, {C_feat}] tensor in the dtype of res")
+        _row_stats(op, stats, M)
+        args.res, args.a, args.out, args.out_mod = _ptr(res, True), _ptr(a, True), _ptr(out, True), _ptr(out_mod, True)
+        args.timestep, args.gate_table, args.mod_table = _ptr(timestep, True), _ptr(gate_table, True), _ptr(mod_table, True)
+        args.stats = _ptr(stats, True)
+        args.ld_res, args.ld_a, args.ld_out, args.ld_mod = lds
+        args.timestep_bs = 0 if timestep is None else timestep.stride(0) if B > 1 else 6 * C_feat
+        args.B, args.T, args.C, args.C_pad = M // T, int(T), int(C_feat), int(C_pad)
+        args.gate_row, args.scale_row, args.shift_row = int(gate_row), int(scale_row), int(shift_row)
+        args.dtype, args.eps = _DT[dtype], float(eps)
+        _lib.check(lib.svdq_sana_glue(C.byref(args), _stream()), op)
+
 
 class _Utils:
     """reference: csrc/pybind.cpp:118-123 -- logging / sm_75 toggles; no-ops here."""

@@ -167,6 +167,18 @@ class CrossAttentionArgs(C.Structure):
     ]
 
 
+class SanaGlueArgs(C.Structure):
+    _fields_ = [
+        ("res", C.c_void_p), ("a", C.c_void_p), ("timestep", C.c_void_p), ("gate_table", C.c_void_p), ("mod_table", C.c_void_p),
+        ("out", C.c_void_p), ("out_mod", C.c_void_p), ("stats", C.c_void_p),
+        ("timestep_bs", C.c_int64),
+        ("ld_res", C.c_int32), ("ld_a", C.c_int32), ("ld_out", C.c_int32), ("ld_mod", C.c_int32),
+        ("B", C.c_int32), ("T", C.c_int32), ("C", C.c_int32), ("C_pad", C.c_int32),
+        ("gate_row", C.c_int32), ("scale_row", C.c_int32), ("shift_row", C.c_int32),
+        ("dtype", C.c_int32), ("eps", C.c_float), ("reserved", C.c_int32),
+    ]
+
+
 EXPORTS = {
     "svdq_quantize_w4a4_act_fuse_lora": (C.c_int, [C.POINTER(QuantizeArgs), C.c_void_p]),
     "svdq_gemm_w4a4": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
@@ -184,6 +196,7 @@ EXPORTS = {
     "svdq_linear_attention_workspace_bytes": (C.c_int64, [C.POINTER(LinearAttentionArgs)]),
     "svdq_dwconv3x3": (C.c_int, [C.POINTER(Dwconv3x3Args), C.c_void_p]),
     "svdq_cross_attention": (C.c_int, [C.POINTER(CrossAttentionArgs), C.c_void_p]),
+    "svdq_sana_glue": (C.c_int, [C.POINTER(SanaGlueArgs), C.c_void_p]),
     "svdq_gemm_workspace_bytes": (C.c_int64, []),
     "svdq_gemm_workspace_bytes_for": (C.c_int64, [C.POINTER(GemmArgs)]),
     "svdq_gemm_workspace_status": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -185,3 +185,93 @@ def modulated_diff(x, stats, scale, shift, prev=None, out=None, scratch=None):
 def modulated_diff_scratch(rows: int, device):
     """``(partials [rows, 2], record [8])`` float32: what a :func:`modulated_diff` launch with ``prev`` writes besides ``out``"""
     return torch.empty(rows, 2, dtype=torch.float32, device=device), torch.empty(8, dtype=torch.float32, device=device)
+
+
+SANA_MSA = (0, 1, 2)  # rows (shift, scale, gate) of a SANA block's ``timestep + scale_shift_table`` for the linear attention
+SANA_MLP = (3, 4, 5)  # ... and for the feed-forward (src/SanaModel.cpp:262)
+
+
+def sana_glue(res: torch.Tensor, a: torch.Tensor | None = None, *, timestep: torch.Tensor | None = None, gate_table: torch.Tensor | None = None,
+              gate_row: int | None = None, mod_table: torch.Tensor | None = None, scale_row: int | None = None, shift_row: int | None = None,
+              channels: int | None = None, pad_to: int | None = None, out: torch.Tensor | bool | None = None,
+              out_mod: torch.Tensor | bool | None = None, want_stats: bool = False, eps: float = 1e-6):
+    """The glue pass of a SANA block in one launch (``svdq_sana_glue``; reference: src/SanaModel.cpp:234-322, nine launches per block there).
+
+    ``res`` / ``a``: ``[B, T, >= channels]`` with unit stride on the last axis (a column slice of a wider buffer will do); ``timestep``: ``[B, 6, channels]``
+    or ``[B, 6 * channels]``; the tables: ``[6, channels]``.  With ``mod(tab, i)[b] = clip(timestep[b, i] + tab[i])`` (one 16-bit rounding per
+    operation throughout, ``clip`` to +-65504 for fp16 only)::
+
+        t = res  |  clip(a + res)  |  clip(a * mod(gate_table, gate_row)[b] + res)          (no a | gate_row None | gate_row 0..5)
+        out = t;   out_mod = clip(layer_norm(t) * (mod(mod_table, scale_row)[b] + 1) + mod(mod_table, shift_row)[b])
+
+    ``channels`` defaults to ``res.shape[-1]``, ``pad_to`` to ``ceil(channels / 128) * 128``: both outputs are ``[B, T, pad_to]`` with zeros behind
+    column ``channels``.  ``out`` / ``out_mod``: a tensor to write into (``out`` may be ``res``), True to allocate one, None / False for none;
+    ``out_mod`` defaults to "when ``mod_table`` is given", ``out`` to "when ``a`` is given".  Returns ``(out, out_mod, stats)`` with None for what
+    was not asked for; ``stats`` is the float32 ``[B * T, 2]`` (mean, rstd) of ``t``."""
+    op = "sana_glue"
+    if not isinstance(res, torch.Tensor) or res.dim() != 3:
+        raise ValueError(f"{op}: res must be a [B, T, C] tensor")
+    if res.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"{op}: res must be bfloat16 or float16, got {res.dtype}")
+    B, T = res.shape[:2]
+    C = res.shape[-1] if channels is None else int(channels)
+    C_pad = (C + 127) // 128 * 128 if pad_to is None else int(pad_to)
+    if C < 8 or C % 8 or C_pad % 8 or C_pad < C or res.shape[-1] < C or B < 1 or T < 1:
+        raise ValueError(f"{op}: need channels={C} a multiple of 8 within res {tuple(res.shape)} and pad_to={C_pad} >= channels, a multiple of 8")
+    if out is None:
+        out = a is not None
+    if out_mod is None:
+        out_mod = mod_table is not None
+    out = torch.empty(B, T, C_pad, dtype=res.dtype, device=res.device) if out is True else None if out is False else out
+    out_mod = torch.empty(B, T, C_pad, dtype=res.dtype, device=res.device) if out_mod is True else None if out_mod is False else out_mod
+    if out is None and out_mod is None and not want_stats:
+        raise ValueError(f"{op}: nothing to do: none of out, out_mod and stats is asked for")
+    if gate_row is not None and (a is None or gate_table is None or timestep is None):
+        raise ValueError(f"{op}: a gate needs a, gate_table and timestep")
+    if out_mod is not None and (mod_table is None or timestep is None or scale_row is None or shift_row is None):
+        raise ValueError(f"{op}: out_mod needs timestep, mod_table, scale_row and shift_row")
+    for name, row in (("gate_row", gate_row), ("scale_row", scale_row), ("shift_row", shift_row)):
+        if row is not None and not 0 <= int(row) <= 5:
+            raise ValueError(f"{op}: {name}={row}: the tables have rows 0..5")
+    if not (eps >= 0.0) or eps == float("inf"):
+        raise ValueError(f"{op}: eps={eps} must be finite and not negative")
+
+    def row_stride(name, t, width):
+        """the row stride of a [B, T, >= width] view whose samples lie T rows apart (0 for None)"""
+        if t is None:
+            return 0
+        if not isinstance(t, torch.Tensor) or t.dtype != res.dtype:
+            raise TypeError(f"{op}: {name} must be a {res.dtype} tensor like res")
+        if t.device != res.device:
+            raise ValueError(f"{op}: {name} must live on res's device {res.device}, got {t.device}")
+        if t.dim() != 3 or t.shape[0] != B or t.shape[1] != T or t.shape[2] < width:
+            raise ValueError(f"{op}: {name} must be [{B}, {T}, >= {width}], got {tuple(t.shape)}")
+        s0, s1, s2 = t.stride()
+        if s2 != 1 or (B > 1 and T > 1 and s0 != T * s1):
+            raise ValueError(f"{op}: {name} must have unit stride on its last axis and hold its samples T rows apart")
+        # (the strides of dimensions of size 1 are arbitrary in torch: the library gets the natural ones)
+        return s1 if T > 1 else s0 if B > 1 else max(t.shape[2], width)
+
+    if out is not None and out.shape[-1] != C_pad:
+        raise ValueError(f"{op}: out must be [{B}, {T}, {C_pad}], got {tuple(out.shape)}")
+    if out_mod is not None and (not isinstance(out_mod, torch.Tensor) or out_mod.shape[-1] != C_pad):
+        raise ValueError(f"{op}: out_mod must be [{B}, {T}, {C_pad}], got {tuple(getattr(out_mod, 'shape', ()))}")
+    lds = (row_stride("res", res, C), row_stride("a", a, C), row_stride("out", out, C_pad), row_stride("out_mod", out_mod, C_pad))
+    if timestep is not None:
+        if not isinstance(timestep, torch.Tensor) or timestep.dtype != res.dtype:
+            raise TypeError(f"{op}: timestep must be a {res.dtype} tensor like res")
+        if timestep.dim() == 2 and timestep.shape == (B, 6 * C) and timestep.stride(1) == 1:
+            timestep = timestep.unflatten(1, (6, C))
+        if tuple(timestep.shape) != (B, 6, C) or timestep.stride(2) != 1 or timestep.stride(1) != C:
+            raise ValueError(f"{op}: timestep must be [{B}, 6, {C}] or [{B}, {6 * C}] with contiguous samples, got {tuple(timestep.shape)}")
+    for name, t in (("gate_table", gate_table), ("mod_table", mod_table)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != res.dtype or tuple(t.shape) != (6, C) or not t.is_contiguous()):
+            raise ValueError(f"{op}: {name} must be a contiguous {res.dtype} [6, {C}] tensor")
+    for name, t in (("res", res), ("a", a), ("timestep", timestep), ("gate_table", gate_table), ("mod_table", mod_table), ("out", out), ("out_mod", out_mod)):
+        if t is not None and not t.is_cuda:
+            raise ValueError(f"{op}: {name} must be a GPU tensor (there is no CPU path)")
+    stats = torch.empty(B * T, 2, dtype=torch.float32, device=res.device) if want_stats else None
+    ops.sana_glue(res, a, timestep, gate_table if gate_row is not None else None, mod_table if out_mod is not None else None, out, out_mod, stats,
+                  T, C, C_pad, gate_row=-1 if gate_row is None else int(gate_row), scale_row=int(scale_row or 0), shift_row=int(shift_row or 0),
+                  eps=eps, lds=lds)
+    return out, out_mod, stats
