@@ -645,7 +645,8 @@ static int launch_quantize(const svdq_quantize_args *a, hipStream_t st) {
     const int KP = a->K / 128, tiles = a->M_pad / 32;
     // enough workgroups to fill 256 CUs several times over, but at least one chunk per wave
     int cpw = 4; // chunks per workgroup = 4 waves x 1 chunk: many short waves hide the HBM round trip
-    while ((long)tiles * ((KP + cpw - 1) / cpw) > 8192) cpw *= 2;
+    // (the doubling ends at cpw >= KP: one slice per row tile is all there is to merge -- beyond 8192 row tiles, M_pad > 262144, the grid is simply larger)
+    while (cpw < KP && (long)tiles * ((KP + cpw - 1) / cpw) > 8192) cpw *= 2;
     if (cpw > KP) cpw = ((KP + 3) / 4) * 4;
     const int slices = (KP + cpw - 1) / cpw;
     const int q32 = a->lora_act_format == SVDQ_LORA_ACT_Q32 || a->lora_act_format == SVDQ_LORA_ACT_Q32_RUNS;

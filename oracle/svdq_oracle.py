@@ -747,7 +747,7 @@ def gemm_w4a4(
     if fuse == "gelu_quant":
         # EpilogueGelu (epilogues.cuh:22-44) -> 16-bit
         g16 = round16(gelu_tanh(y16), dtype)
-        res = {}
+        res = {"g16": g16}  # (the 16-bit GELU output itself: what the next layer's low-rank down projection sums)
         if next_lora_down is not None:
             # EpilogueLoraDown on the GELU output, before shift/smooth (launch_impl.cuh:226-262)
             res["lora_act_out"] = lora_down_project(g16, next_lora_down)
