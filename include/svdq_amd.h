@@ -241,7 +241,8 @@ typedef struct svdq_gemm_args {
 
 int svdq_gemm_w4a4(const svdq_gemm_args *args, void *stream);
 
-/* ABI 21: the fragment images above.  ld = [R2][N] rank-major (svdq_repack_lowrank(down=1) order), R2 in 48 .. 160, N % 256 == 0 -> out, svdq_pack_lora_down_bytes(N, R2)
+/* ABI 21: the fragment images above.  ld = [R2][N] rank-major (svdq_repack_lowrank(down=1) order), R2 in 48 .. 160, N % 256 == 0 (or R2 = 16 / 32, N % 128 == 0: the
+ * one-block image the attention epilogue's quantiser reads, svdq_attention_args.qlora_down_packed) -> out, svdq_pack_lora_down_bytes(N, R2)
  * bytes ([N / 16 units][ceil(R2 / 32) rank blocks][64 lanes][8] 16-bit, ranks >= R2 zero); lu = [N][R] natural -> out, svdq_pack_lora_up_bytes(N, R) bytes
  * ([N / 32][R / 16][64 lanes][8]).  Pure permutations (a weight changes only under a set_lora): pack once, pass with every launch. */
 int64_t svdq_pack_lora_down_bytes(int32_t N, int32_t R2);
@@ -356,7 +357,11 @@ typedef struct svdq_attention_args {
      * q_prescaled, L % 256 == 0 and no mask; an explicit geometry uses the persistent schedule when a workspace is given. */
     int32_t geometry;
     /* ABI 21, optional: qlora_down(2) as the fragment image of svdq_pack_lora_down (N = H * 128) for a launch whose fused quantiser runs its low-rank down
-     * projection split (rank 48 .. 160 with the workspace of svdq_attention_workspace_bytes_for()); NULL = packed by the launch */
+     * projection split (rank 48 .. 160 with the workspace of svdq_attention_workspace_bytes_for()); NULL = packed by the launch.
+     * Also read at qR = 16 / 32 (an addition within ABI 24: until now the fields were ignored at these ranks, and svdq_pack_lora_down refused them, so no
+     * existing caller can have set them): the same image at one rank block (svdq_pack_lora_down(N = H * 128, R2 = qR); ranks >= qR zero), 16-byte aligned.  The
+     * epilogue's low-rank pass then requests the head's factor once per task as lane-contiguous 16-byte loads instead of row-per-lane 8-byte loads per row
+     * tile; same results bit for bit.  A launch with two weight sets (qsmooth2) takes this path only when BOTH images are given; NULL = the rank-major rows. */
     const void *qlora_down_packed, *qlora_down_packed2;
 } svdq_attention_args;
 

@@ -265,6 +265,9 @@ class _SideTable:
 
 _fp6_images = _SideTable()    # storage of a reference-sized code buffer -> {K: image over the whole storage}
 _converted = _SideTable()     # storage of a checkpoint-layout parameter -> {(kind, offset, shape): (version, converted)}
+_epilogue_images = _SideTable()  # storage of a rank 16 / 32 down factor -> {("frag_down", offset, shape): (version, one-block fragment image)}: what the attention
+                                 # epilogue's quantiser reads (_packed_fragments(epilogue=True)).  Same key, version rule and invalidate() as _converted; a table of its
+                                 # own because at these ranks _converted holds no entry for a marked parameter (tests/test_gpu_qwenimage.py pins that for offload slots)
 _packed_rows = _SideTable()   # storage of a packed K buffer -> {row offset: (valid rows, padded rows)}
 
 
@@ -308,18 +311,20 @@ def invalidate(t: torch.Tensor | None) -> None:
     ``.data`` -- such writes do not bump ``t._version``, so the cache cannot see them)."""
     if t is not None:
         _converted.pop(t)
+        _epilogue_images.pop(t)
 
 
-def _cached_conversion(t: torch.Tensor, kind: str, convert):
+def _cached_conversion(t: torch.Tensor, kind: str, convert, table=None):
+    table = _converted if table is None else table
     key = (kind, t.storage_offset(), tuple(t.shape))
-    per = _converted.get(t)
+    per = table.get(t)
     hit = per.get(key) if per else None
     if hit is not None and hit[0] == t._version:
         return hit[1]
     conv = convert(t.detach())
     per = dict(per or {})
     per[key] = (t._version, conv)
-    _converted.put(t, per)
+    table.put(t, per)
     return conv
 
 
@@ -337,13 +342,18 @@ def _param(t: torch.Tensor | None, kind: str):
     return _cached_conversion(t, kind, lambda src: layout.repack_lowrank(src, down=(kind == "down")))
 
 
-def _packed_fragments(t: torch.Tensor | None, down: bool, N: int, R: int):
+def _packed_fragments(t: torch.Tensor | None, down: bool, N: int, R: int, epilogue: bool = False):
     """ABI 21: the MFMA-fragment image of a low-rank factor in the kernel layout (``down``: rank-major ``[R][N]`` -> svdq_pack_lora_down; else ``[N][R]`` ->
     svdq_pack_lora_up), packed ONCE per storage and version (a ``set_lora`` writes a new tensor or bumps the version: re-packed) -- the rank 48 .. 160 kernels
-    otherwise re-pack the weight on every launch (190 pack launches per rank-128 FLUX step).  None where the library has no such image."""
+    otherwise re-pack the weight on every launch (190 pack launches per rank-128 FLUX step).  ``epilogue``: the consumer is the attention kernel's fused
+    quantiser, which at rank 16 / 32 reads the same image (one rank block, padded with zeros) in its own low-rank pass instead of the rank-major rows.
+    None where the library has no such image."""
     if t is None or not _Ops.cache_packed_lowrank or R % 16 or t.dtype not in _DT:
         return None
-    if down and not (48 <= R <= 160 and N % 256 == 0):
+    if down and epilogue and 0 < R <= 32:
+        if not (_Ops.attention_lowrank_image and N % 128 == 0):
+            return None
+    elif down and not (48 <= R <= 160 and N % 256 == 0):
         return None
     if not down and not (48 <= R <= 160 and N % 32 == 0):
         return None
@@ -356,7 +366,7 @@ def _packed_fragments(t: torch.Tensor | None, down: bool, N: int, R: int):
         _lib.check(fn(src.data_ptr(), out.data_ptr(), N, R, _DT[src.dtype], _stream()), "pack_lora_down" if down else "pack_lora_up")
         return out
 
-    return _cached_conversion(t, f"frag_{'down' if down else 'up'}", pack)
+    return _cached_conversion(t, f"frag_{'down' if down else 'up'}", pack, _epilogue_images if down and epilogue and R <= 32 else None)
 
 
 def _weight(wgt: torch.Tensor, K: int) -> torch.Tensor:
@@ -415,6 +425,8 @@ class _Ops:
 
     # False: the fused quantiser's low-rank down projection stays inside the attention epilogue at every rank (tests / A/B of the split path, rank 48 .. 160)
     attention_split_lowrank = True
+    # rank 16 / 32: the fused quantiser's low-rank pass reads the cached fragment image of its factor (False: the rank-major rows, as before; A/B and tests)
+    attention_lowrank_image = True
 
     @staticmethod
     def attention_workspace_status() -> None:
@@ -953,8 +965,8 @@ class _Ops:
                 a.qlora_act_format = _lib.LORA_ACT_Q32
             a.qsmooth, a.qlora_down, a.qR = _ptr(quant["smooth"]), _ptr(quant.get("lora_down")), int(quant.get("R", 0))
             a.qsmooth2, a.qlora_down2 = _ptr(quant.get("smooth2")), _ptr(quant.get("lora_down2"))
-            fq = _packed_fragments(quant.get("lora_down"), True, Kq, a.qR)
-            fq2 = _packed_fragments(quant.get("lora_down2"), True, Kq, a.qR)
+            fq = _packed_fragments(quant.get("lora_down"), True, Kq, a.qR, epilogue=True)
+            fq2 = _packed_fragments(quant.get("lora_down2"), True, Kq, a.qR, epilogue=True)
             if fq is not None and (quant.get("lora_down2") is None or fq2 is not None):
                 a.qlora_down_packed, a.qlora_down_packed2 = _ptr(fq), _ptr(fq2)
             a.qsplit_rows = int(quant.get("split_rows", 0))

@@ -72,6 +72,7 @@ struct AttnParams {
     int mask_j0, mask_j1;            // geometry 2 with a key mask: the main segment [mask_j0, mask_j1) of fully real tiles (even count) the assembly loop runs
     const uint16_t *qsmooth, *qlora_down, *qsmooth2, *qlora_down2;
     int qR, qsplit_rows;
+    const void *qimg, *qimg2; // rank <= 32: the fragment image of qlora_down(2) (svdq_pack_lora_down, [H * 8 units][64 lanes][8]) or NULL -- the row-per-lane loads
     void *qa16;        // split low-rank down (rank 48 .. 160, fp32): the normalised 16-bit output as MFMA operand fragments [L / 32][H * 8 units][64 lanes][8]
                        // (lowrank_split.h); the kernel then runs no low-rank pass -- lowrank_down_split_kernel contracts the image behind it
     // persistent schedule (svdq_attention_args.workspace): arrival counters + error word, then one slab per workgroup
@@ -151,10 +152,35 @@ template <int DT> __device__ __forceinline__ float sum2(unsigned packed, float l
     else return __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2, packed), __builtin_bit_cast(f16x2, 0x3c003c00u), l, false);
 }
 
-// Normalise one 32-row tile of a wave and store it: lane owns query row q0 + lr and channels 32*dt + 8c + 4h + e of o[dt].
-// Either the 16-bit output, or (p.qact) the output projection's quantised activation, or both.
+// The fused quantiser's per-head operands of a launch that carries the fragment image of its low-rank factor (p.qimg; rank <= 32): what a lane needs of them
+// does not depend on the row tile, so a wave requests them ONCE per task and every row tile it finishes reads the same registers.
+template <int DT> struct QuantOperands {
+    typename Half<DT>::V8 w[8]; // B fragment of MFMA step dt * 2 + qq: ranks lane & 31, k-slots 8 h + j (the image: one lane-contiguous 16-byte load each)
+    u16x4 sm[16];               // smooth of the lane's channels 32 dt + 8 c + 4 h + e: [dt * 4 + c]
+};
 template <int DT>
-__device__ __forceinline__ void finish_rows(const AttnParams &p, const v16f (&o)[4], float l_run, int q0, int head, int lane) {
+__device__ __forceinline__ void load_quant_operands(const AttnParams &p, int q0, int head, int lane, QuantOperands<DT> &qo) {
+    using V8 = typename Half<DT>::V8;
+    using T = typename Half<DT>::T;
+    const bool s2 = p.qsplit_rows > 0 && q0 >= p.qsplit_rows; // wave-uniform (the split is a multiple of 256 rows)
+    const V8 *img = (const V8 *)(s2 ? p.qimg2 : p.qimg) + (size_t)head * (8 * 64) + lane; // [K / 16 units][64 lanes][8]: unit = head * 8 + step
+    const T *smooth = (const T *)(s2 ? p.qsmooth2 : p.qsmooth) + head * ATT_D + (lane >> 5) * 4;
+#pragma unroll
+    for (int s = 0; s < 8; s++) qo.w[s] = img[s * 64];
+#pragma unroll
+    for (int i = 0; i < 16; i++) qo.sm[i] = *reinterpret_cast<const u16x4 *>(smooth + (i >> 2) * 32 + (i & 3) * 8);
+}
+// the two 16-bit values of a packed dword, widened (exact)
+template <int DT> __device__ __forceinline__ float unpack16(unsigned w, int hi) {
+    if constexpr (DT == SVDQ_BF16) return __builtin_bit_cast(float, hi ? (w & 0xffff0000u) : (w << 16));
+    else return (float)__builtin_bit_cast(_Float16, (unsigned short)(hi ? (w >> 16) : (w & 0xffffu)));
+}
+
+// Normalise one 32-row tile of a wave and store it: lane owns query row q0 + lr and channels 32*dt + 8c + 4h + e of o[dt].
+// Either the 16-bit output, or (p.qact) the output projection's quantised activation, or both.  `pre`: the quantiser's operands the caller requested
+// for this task (load_quant_operands; only looked at when p.qimg is set) -- NULL: requested here.
+template <int DT>
+__device__ __forceinline__ void finish_rows(const AttnParams &p, const v16f (&o)[4], float l_run, int q0, int head, int lane, const QuantOperands<DT> *pre = nullptr) {
     using V8 = typename Half<DT>::V8;
     const int lr = lane & 31, h = lane >> 5;
     const float inv = 1.0f / (l_run + __shfl_xor(l_run, 32));
@@ -165,58 +191,8 @@ __device__ __forceinline__ void finish_rows(const AttnParams &p, const v16f (&o)
         const bool s2 = p.qsplit_rows > 0 && q0 >= p.qsplit_rows; // wave-uniform
         const T *smooth = (const T *)(s2 ? p.qsmooth2 : p.qsmooth) + head * ATT_D;
         const int K = p.H * ATT_D, KP = p.H;
-        // lora_act[q][rank] += sum_d o16[q][d] * down[d][rank] over this head's 128 channels, 32 ranks per pass (rank 128 checkpoints and runtime LoRAs
-        // take 2 .. 8 passes; the body of a pass is the rank <= 32 code of rounds 2-4, unchanged: it sits at the register limit of the 4 x 64 kernels)
-        auto lowrank_pass = [&](int rank0) {
-            const T *ld = (const T *)(s2 ? p.qlora_down2 : p.qlora_down) + head * ATT_D; // rank-major [R][K]
-            v16f dl;
-#pragma unroll
-            for (int i = 0; i < 16; i++) dl[i] = 0.f;
-            const bool live = rank0 + lr < p.qR;
-#pragma unroll
-            for (int dt = 0; dt < 4; dt++)
-#pragma unroll
-                for (int qq = 0; qq < 2; qq++) {
-                    V8 wv, gv;
-                    if (live) {
-                        const T *src = ld + (size_t)(rank0 + lr) * K + dt * 32 + qq * 16 + h * 4;
-                        const u16x4 w0 = *reinterpret_cast<const u16x4 *>(src);
-                        const u16x4 w1 = *reinterpret_cast<const u16x4 *>(src + 8);
-#pragma unroll
-                        for (int j = 0; j < 4; j++) { wv[j] = hfrom<T>(w0[j]); wv[4 + j] = hfrom<T>(w1[j]); }
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 8; j++) wv[j] = (T)0.f;
-                    }
-#pragma unroll
-                    for (int j = 0; j < 8; j++) gv[j] = f2h<T>(o[dt][qq * 8 + j] * inv);
-                    dl = Half<DT>::mfma32(gv, wv, dl);
-                }
-            if (live) { // C layout: column (rank) = lane & 31, rows (i & 3) + 8 (i >> 2) + 4 h
-                const size_t at = (size_t)(q0 + h * 4) * p.qR + rank0 + lr;
-                const int mode = 1 | (p.qlora_q32 ? 2 : 0); // the H heads add to the same element
-#pragma unroll
-                for (int i = 0; i < 16; i++) lora_act_add(p.qlora_act, at + (size_t)((i & 3) + 8 * (i >> 2)) * p.qR, dl[i], mode);
-            }
-        };
-        if (p.qa16) {
-            // rank 48 .. 160: the 16-bit rows as the A-operand fragments of a contraction that runs behind this kernel -- the lane's 8 channels
-            // {16 qq + 8 (j >> 2) + 4 h + (j & 3)} of unit (head, dt, qq) are k-slots 8 h + j as they stand: 8 coalesced 16-byte stores per row tile
-            // instead of 2 .. 5 passes of 8 MFMAs + 16 atomic instructions that the H heads aim at the same elements
-            V8 *a16 = (V8 *)p.qa16 + ((size_t)(q0 >> 5) * (size_t)(p.H * 8) + (size_t)head * 8) * 64 + lane;
-#pragma unroll
-            for (int dt = 0; dt < 4; dt++)
-#pragma unroll
-                for (int qq = 0; qq < 2; qq++) {
-                    V8 gv;
-#pragma unroll
-                    for (int j = 0; j < 8; j++) gv[j] = f2h<T>(o[dt][qq * 8 + j] * inv);
-                    a16[(dt * 2 + qq) * 64] = gv;
-                }
-        } else {
-        if (p.qR > 0) lowrank_pass(0);                                     // (straight-line, as in rounds 2-4: the rank-32 step runs exactly this)
-        for (int rank0 = 32; rank0 < p.qR; rank0 += 32) lowrank_pass(rank0); // the slabs beyond rank 32
-        }
+        // codes, scales and their stores: `o16_at(dt, i)` = the rounded normalised o[dt][i], `smooth_at(dt, c)` = smooth of channels 32 dt + 8 c + 4 h + (0 .. 3)
+        auto quantise = [&](auto o16_at, auto smooth_at) {
         uint32_t rec[12];
         T sc16[2];
 #pragma unroll
@@ -228,10 +204,10 @@ __device__ __forceinline__ void finish_rows(const AttnParams &p, const v16f (&o)
 #pragma unroll
                 for (int c = 0; c < 4; c++) {
                     const int dt = 2 * g + t;
-                    const u16x4 sv = *reinterpret_cast<const u16x4 *>(smooth + dt * 32 + c * 8 + h * 4);
+                    const u16x4 sv = smooth_at(dt, c);
 #pragma unroll
                     for (int e = 0; e < 4; e++) {
-                        const float o16 = round16<T>(o[dt][c * 4 + e] * inv);
+                        const float o16 = o16_at(dt, c * 4 + e);
                         const float sm = h2f(hfrom<T>(sv[e]));
                         const float v = smooth_div16<T>(o16, __builtin_amdgcn_rcpf(sm));
                         xh[16 * t + c * 4 + e] = v;
@@ -264,6 +240,98 @@ __device__ __forceinline__ void finish_rows(const AttnParams &p, const v16f (&o)
         *reinterpret_cast<uint4 *>(dst + F6_PLANE) = make_uint4(rec[4], rec[5], rec[6], rec[7]);
         *reinterpret_cast<uint4 *>(dst + 2 * F6_PLANE) = make_uint4(rec[8], rec[9], rec[10], rec[11]);
         p.qscales[(((size_t)rt * KP + head) * 2 + h) * 32 + lr] = hbits(sc16[h]);
+        };
+        if (p.qimg) {
+            // ---- rank <= 32 with the fragment image: the operands come from registers requested once per task (ranks >= qR of the image are zeros, the `live`
+            //      predicate of the pass below), and the normalised rows are formed and rounded ONCE: the same packed 16-bit values are the A operand of the
+            //      low-rank MFMAs and the quantiser's input.  Same MFMA chain, same order, same atomics as lowrank_pass(0).
+            QuantOperands<DT> own;
+            if (!pre) load_quant_operands<DT>(p, q0, head, lane, own);
+            const QuantOperands<DT> &qo = pre ? *pre : own;
+            unsigned g16[4][8]; // g16[dt][i]: elements 2 i, 2 i + 1 of o[dt], normalised and rounded (pack2_scaled: the rounding of the 16-bit output path)
+#pragma unroll
+            for (int dt = 0; dt < 4; dt++)
+#pragma unroll
+                for (int i = 0; i < 8; i++) g16[dt][i] = pack2_scaled<DT>(o[dt][2 * i], o[dt][2 * i + 1], inv);
+            v16f dl;
+#pragma unroll
+            for (int i = 0; i < 16; i++) dl[i] = 0.f;
+#pragma unroll
+            for (int dt = 0; dt < 4; dt++)
+#pragma unroll
+                for (int qq = 0; qq < 2; qq++) {
+                    const V8 gv = __builtin_bit_cast(V8, v4i{(int)g16[dt][4 * qq], (int)g16[dt][4 * qq + 1], (int)g16[dt][4 * qq + 2], (int)g16[dt][4 * qq + 3]});
+                    dl = Half<DT>::mfma32(gv, qo.w[dt * 2 + qq], dl);
+                }
+            if (lr < p.qR) { // C layout: column (rank) = lane & 31, rows (i & 3) + 8 (i >> 2) + 4 h
+                const size_t at = (size_t)(q0 + h * 4) * p.qR + lr;
+                const int mode = 1 | (p.qlora_q32 ? 2 : 0); // the H heads add to the same element
+#pragma unroll
+                for (int i = 0; i < 16; i++) lora_act_add(p.qlora_act, at + (size_t)((i & 3) + 8 * (i >> 2)) * p.qR, dl[i], mode);
+            }
+            quantise([&](int dt, int i) { return unpack16<DT>(g16[dt][i >> 1], i & 1); }, [&](int dt, int c) { return qo.sm[dt * 4 + c]; });
+        } else {
+        // lora_act[q][rank] += sum_d o16[q][d] * down[d][rank] over this head's 128 channels, 32 ranks per pass (rank 128 checkpoints and runtime LoRAs
+        // take 2 .. 8 passes; the body of a pass is the rank <= 32 code of rounds 2-4, unchanged: it sits at the register limit of the 4 x 64 kernels)
+        auto lowrank_pass = [&](int rank0) {
+            const T *ld = (const T *)(s2 ? p.qlora_down2 : p.qlora_down) + head * ATT_D; // rank-major [R][K]
+            v16f dl;
+#pragma unroll
+            for (int i = 0; i < 16; i++) dl[i] = 0.f;
+            const bool live = rank0 + lr < p.qR;
+#pragma unroll
+            for (int dt = 0; dt < 4; dt++)
+#pragma unroll
+                for (int qq = 0; qq < 2; qq++) {
+                    V8 wv, gv;
+                    if (live) {
+                        const T *src = ld + (size_t)(rank0 + lr) * K + dt * 32 + qq * 16 + h * 4;
+                        const u16x4 w0 = *reinterpret_cast<const u16x4 *>(src);
+                        const u16x4 w1 = *reinterpret_cast<const u16x4 *>(src + 8);
+#pragma unroll
+                        for (int j = 0; j < 4; j++) { wv[j] = hfrom<T>(w0[j]); wv[4 + j] = hfrom<T>(w1[j]); }
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 8; j++) wv[j] = (T)0.f;
+                    }
+                    // the A operand is the 16-bit output itself, rounded as pack2_scaled rounds it.  (Written `f2h<T>(o * inv)` the fp16 build made v_mul_f32 +
+                    // v_cvt_pk_f16_f32 of it -- 4 packed conversions in front of every MFMA of this pass in the ISA listing: the fp32 product rounded a SECOND time,
+                    // one fp16 step from the value the quantiser below and a separate quantiser launch read on ~1e-4 of the elements, which put fp16 lora_act up to
+                    // 1.25x outside the quantiser rows' bound 2e-5 (|x'| @ |D|) + 1e-6 against the kernel's own output.  bf16: the same bits either way.)
+                    unsigned gp[4];
+#pragma unroll
+                    for (int j = 0; j < 4; j++) gp[j] = pack2_scaled<DT>(o[dt][qq * 8 + 2 * j], o[dt][qq * 8 + 2 * j + 1], inv);
+                    gv = __builtin_bit_cast(V8, v4i{(int)gp[0], (int)gp[1], (int)gp[2], (int)gp[3]});
+                    dl = Half<DT>::mfma32(gv, wv, dl);
+                }
+            if (live) { // C layout: column (rank) = lane & 31, rows (i & 3) + 8 (i >> 2) + 4 h
+                const size_t at = (size_t)(q0 + h * 4) * p.qR + rank0 + lr;
+                const int mode = 1 | (p.qlora_q32 ? 2 : 0); // the H heads add to the same element
+#pragma unroll
+                for (int i = 0; i < 16; i++) lora_act_add(p.qlora_act, at + (size_t)((i & 3) + 8 * (i >> 2)) * p.qR, dl[i], mode);
+            }
+        };
+        if (p.qa16) {
+            // rank 48 .. 160: the 16-bit rows as the A-operand fragments of a contraction that runs behind this kernel -- the lane's 8 channels
+            // {16 qq + 8 (j >> 2) + 4 h + (j & 3)} of unit (head, dt, qq) are k-slots 8 h + j as they stand: 8 coalesced 16-byte stores per row tile
+            // instead of 2 .. 5 passes of 8 MFMAs + 16 atomic instructions that the H heads aim at the same elements
+            V8 *a16 = (V8 *)p.qa16 + ((size_t)(q0 >> 5) * (size_t)(p.H * 8) + (size_t)head * 8) * 64 + lane;
+#pragma unroll
+            for (int dt = 0; dt < 4; dt++)
+#pragma unroll
+                for (int qq = 0; qq < 2; qq++) {
+                    V8 gv;
+#pragma unroll
+                    for (int j = 0; j < 8; j++) gv[j] = f2h<T>(o[dt][qq * 8 + j] * inv);
+                    a16[(dt * 2 + qq) * 64] = gv;
+                }
+        } else {
+        if (p.qR > 0) lowrank_pass(0);                                     // (straight-line, as in rounds 2-4: the rank-32 step runs exactly this)
+        for (int rank0 = 32; rank0 < p.qR; rank0 += 32) lowrank_pass(rank0); // the slabs beyond rank 32
+        }
+        quantise([&](int dt, int i) { return round16<T>(o[dt][i] * inv); },
+                 [&](int dt, int c) { return *reinterpret_cast<const u16x4 *>(smooth + dt * 32 + c * 8 + h * 4); });
+        } // no image
     }
     if (p.out) {
     uint16_t *orow = p.out + (size_t)(q0 + lr) * p.ldo + (size_t)head * p.o_hs + 8 * h;
@@ -825,6 +893,16 @@ __global__ __launch_bounds__(256, 1) void attention_kernel64(const AttnParams p)
             }
 #undef SVDQ_ATTN_LOOP_OPERANDS
         }
+        // The fused quantiser's operands, once per task: requested in front of the segment's last tile, whose 64 MFMAs cover the round trip -- score set A is
+        // dead behind the loop, its registers hold them (fragment image only; both row tiles read the same registers).  Plain grid without a mask only: the
+        // masked kernel keeps score set A and the start values for its extra tiles, the persistent one has no register to spare around its slab code (both
+        // already spill) -- there every row tile requests its own, the same coalesced loads.
+        constexpr bool EARLY = !MASK && !PERSIST;
+        const bool part = PERSIST && tl >= 0 && (j0 > 0 || j1 < ntiles); // a part of a split task: no epilogue here
+        QuantOperands<DT> qo;
+        if constexpr (EARLY) {
+            if (p.qimg) load_quant_operands<DT>(p, q0, head, lane, qo);
+        }
         last_tile(SB, 1); // a segment has an even number of tiles: its last one sits in score set B / buffer 1
         __syncthreads();  // the buffers are free for the next segment's prologue
         if constexpr (MASK) {
@@ -902,7 +980,7 @@ __global__ __launch_bounds__(256, 1) void attention_kernel64(const AttnParams p)
         float l_run[RT] = {l2[0] + l2[1], l2[2] + l2[3]};
 
         if constexpr (PERSIST) {
-            if (tl >= 0 && (j0 > 0 || j1 < ntiles)) { // a part of a split task: publish the un-normalised state, no epilogue here
+            if (part) { // publish the un-normalised state
                 typedef __attribute__((address_space(1))) int gint;
                 typedef __attribute__((address_space(1))) v4f gv4f;
                 typedef __attribute__((address_space(1))) v2f gv2f;
@@ -936,7 +1014,7 @@ __global__ __launch_bounds__(256, 1) void attention_kernel64(const AttnParams p)
             for (int dt = 0; dt < 4; dt++)
 #pragma unroll
                 for (int r = 0; r < 16; r++) o4[dt][r] = O[2 * rt + (dt >> 1)][16 * (dt & 1) + r];
-            finish_rows<DT>(p, o4, l_run[rt], q0 + 32 * rt, head, lane);
+            finish_rows<DT>(p, o4, l_run[rt], q0 + 32 * rt, head, lane, EARLY ? &qo : nullptr);
         }
     } // segments
     if constexpr (PERSIST) {
@@ -1181,6 +1259,13 @@ extern "C" int svdq_attention(const svdq_attention_args *a, void *stream) {
     p.qsmooth = (const uint16_t *)a->qsmooth; p.qlora_down = (const uint16_t *)a->qlora_down;
     p.qsmooth2 = (const uint16_t *)a->qsmooth2; p.qlora_down2 = (const uint16_t *)a->qlora_down2;
     p.qR = a->qR; p.qsplit_rows = a->qsmooth2 ? a->qsplit_rows : 0;
+    // rank <= 32 with the caller's fragment image(s) of the factor(s): the epilogue's low-rank pass reads them (one image per weight set the launch uses)
+    const bool qimage = a->qact && a->qR > 0 && a->qR <= 32 && a->qlora_down_packed && (!a->qsmooth2 || a->qlora_down_packed2);
+    if (qimage && (((uintptr_t)a->qlora_down_packed | (uintptr_t)(a->qsmooth2 ? a->qlora_down_packed2 : nullptr)) & 15)) {
+        set_error("svdq_attention: fused quantiser: qlora_down_packed(2) must be 16-byte aligned");
+        return SVDQ_E_INVALID;
+    }
+    p.qimg = qimage ? a->qlora_down_packed : nullptr; p.qimg2 = qimage && a->qsmooth2 ? a->qlora_down_packed2 : nullptr;
     p.zero_ptr = (v4i *)a->zero_ptr;
     p.zero_vec = a->zero_ptr ? a->zero_bytes / 16 : 0;
     p.ws_flags = nullptr;

@@ -2025,8 +2025,8 @@ extern "C" int svdq_gemm_schedule(int32_t M_pad, int32_t N, int32_t K, int32_t c
 
 extern "C" int64_t svdq_pack_lora_down_bytes(int32_t N, int32_t R2) { return lowrank_split_pack_bytes(N, R2, false); }
 extern "C" int svdq_pack_lora_down(const void *ld, void *out, int32_t N, int32_t R2, int32_t dtype, void *stream) {
-    if (!ld || !out || !lowrank_split_shape_ok(N, R2) || R2 % 16 || (dtype != SVDQ_BF16 && dtype != SVDQ_FP16)) {
-        set_error("svdq_pack_lora_down: needs ld, out, N %% 256 == 0, R2 a multiple of 16 in 48 .. 160 (N=%d R2=%d)", N, R2);
+    if (!pack_lora_down_args_ok(ld, out, N, R2, dtype)) {
+        set_error("svdq_pack_lora_down: needs ld, out, R2 a multiple of 16: 48 .. 160 with N %% 256 == 0, or 16 / 32 with N %% 128 == 0 (N=%d R2=%d)", N, R2);
         return SVDQ_E_INVALID;
     }
     if (dtype == SVDQ_BF16) launch_pack_lora_down<SVDQ_BF16>(ld, out, N, R2, (hipStream_t)stream);

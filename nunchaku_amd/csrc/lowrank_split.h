@@ -2,6 +2,7 @@
 // fused quantiser of the output projection).  Included by gemm_w4a4.hip and attention.hip; part of the hashed kernel sources (bench.kernel_sources_sha16).
 #pragma once
 #include "svdq_common.h"
+#include "lowrank_image_host.h"
 
 namespace svdq {
 
@@ -146,9 +147,7 @@ __global__ __launch_bounds__(256, 2) void lowrank_down_split_kernel(const typena
     }
 }
 
-// bytes the packed down projection(s) of a launch take ([N / 16 units][nb blocks][64 lanes][8] 16-bit per weight set)
-static inline long long lowrank_split_pack_bytes(int N, int R2, bool two_sets) { return (two_sets ? 2LL : 1LL) * (N / 16) * ((R2 + 31) / 32) * 1024; }
-static inline bool lowrank_split_shape_ok(int N, int R2) { return R2 > 32 && (R2 + 31) / 32 <= 5 && N % 256 == 0; }
+// (lowrank_split_pack_bytes, lowrank_split_shape_ok: lowrank_image_host.h)
 
 // pack the down projection(s) into `ldp` (lowrank_split_pack_bytes), then -- `producer()` enqueues the kernel that writes the act16 image -- contract:
 // out[M_pad][R2] += act16 . ld.  ld / ld2: rank-major [R2][N] 16-bit; rows >= split_row use ld2 (0x7fffffff: one set).  cus: compute units the grid is sized for.
