@@ -646,6 +646,40 @@ typedef struct svdq_cross_attention_args {
 int svdq_cross_attention(const svdq_cross_attention_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Batched attention at head dimension 64 (the self- and cross-attention of Stable Diffusion XL's transformer blocks; added WITHOUT a
+ * version bump: one new symbol and a new args struct, nothing existing changes, so SVDQ_ABI_VERSION stays 24.  reference:
+ * NunchakuSDXLFA2Processor, nunchaku/models/attention_processors/sdxl.py -- a chunk, three view / transpose copies and torch's SDPA).
+ * Per sample b < B, head h < H, query t < T and keys n < N:
+ *   out[b, t, h, :] = round16( softmax_n(scale * q[b, t, h, :] . k[b, n, h, :]) . v[b, n, h, :] )        head_dim = 64, no mask
+ * q and out are [B][T, H * 64], k and v are [B][N, H * 64]; each has a row stride (ldq / ldk / ldv / ldo) and a batch stride (q_bs / k_bs /
+ * v_bs / out_bs; ignored at B = 1), all in elements: the three column thirds of a packed [B, T, 3 * H * 64] QKV projection (N = T) and the
+ * [B, 77, H * 64] outputs of to_k / to_v are read in place, out is written token-major.  No transposed side input, no workspace, no
+ * atomics, no synchronisation: the call can be captured and two launches are bit-identical.
+ * The keys are walked in chunks of 64 from key 0 with an online softmax (exp2 with scale * log2(e); the probabilities are rounded to 16
+ * bits before they meet V, the row sum is taken over the rounded values, the normalisation follows the last MFMA, as in svdq_attention
+ * and svdq_cross_attention): a row's result depends on its own sample's and head's keys only.  Rows of k / v at or beyond N, rows of
+ * q / out at or beyond T and columns beyond H * 64 are neither read nor written.
+ * Validation (no launch), SVDQ_E_INVALID: NULL args or pointers, B / T / H / N < 1, B * H > 65535, T or N > 2^30, a row stride below
+ * H * 64 or not a multiple of 8, a batch stride (B > 1) below (rows - 1) * ld + H * 64 or not a multiple of 8, pointers not 16-byte
+ * aligned, unknown dtype, a scale that is not finite and positive, out overlapping an input.  SVDQ_E_UNSUPPORTED: head_dim != 64.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct svdq_attention_d64_args {
+    const void *q;   /* [B][T, H * 64] 16-bit, row stride ldq, batch stride q_bs */
+    const void *k;   /* [B][N, H * 64], row stride ldk, batch stride k_bs */
+    const void *v;   /* [B][N, H * 64], row stride ldv, batch stride v_bs */
+    void *out;       /* [B][T, H * 64], row stride ldo, batch stride out_bs */
+    int64_t q_bs, k_bs, v_bs, out_bs; /* in elements; ignored at B = 1 */
+    int32_t ldq, ldk, ldv, ldo;       /* in elements */
+    int32_t B, T, H, N;
+    int32_t head_dim; /* 64 */
+    int32_t dtype;
+    float scale;      /* 64^-0.5 in the reference */
+    int32_t reserved;
+} svdq_attention_d64_args;
+
+int svdq_attention_d64(const svdq_attention_d64_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * SANA block glue (the element-wise passes between the three layers of a SANA block; added WITHOUT a version bump: one new symbol and a
  * new args struct, nothing existing changes, so SVDQ_ABI_VERSION stays 24.  reference: SanaLinearTransformerBlock::forward,
  * src/SanaModel.cpp:234-322 -- a copy of timestep, one add of scale_shift_table, two LayerNorms and five mul_add_batch launches per block;

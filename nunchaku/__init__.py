@@ -7,7 +7,8 @@ positional signatures, reference-sized opaque buffers and checkpoint-layout para
 reference's own ``ops/*.py`` / ``models/linear.py`` callers run against it unchanged (tests/test_nunchaku_shim.py).
 ``from nunchaku import NunchakuT5EncoderModel`` is the 4-bit T5 text encoder of the FLUX pipelines (AWQ W4A16 group-128
 linears on ``ops.gemm_awq``); transformers is imported on first access of that name, so ``import nunchaku`` works without it.
-``from nunchaku import NunchakuSanaTransformer2DModel`` is SANA (``nunchaku_amd/models/transformer_sana.py``).  Z-Image is not part of this package.
+``from nunchaku import NunchakuSanaTransformer2DModel`` is SANA (``nunchaku_amd/models/transformer_sana.py``).
+``from nunchaku.models.unets.unet_sdxl import NunchakuSDXLUNet2DConditionModel`` is Stable Diffusion XL (``nunchaku_amd/models/sdxl.py``).  Z-Image is not part of this package.
 """
 from .models import (  # noqa: F401
     NunchakuFluxTransformer2dModel,

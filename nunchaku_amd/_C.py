@@ -1157,6 +1157,34 @@ class _Ops:
         _lib.check(lib.svdq_cross_attention(C.byref(a), _stream()), "cross_attention")
 
     @staticmethod
+    def attention_d64(q, k, v, out, scale):
+        """Extension (SDXL): ``out[b] = round16(softmax(scale * q[b] k[b]^T) v[b])`` per head at head_dim 64 (``svdq_attention_d64``).
+        ``q`` / ``out``: ``[B, T, H, D]`` views, ``k`` / ``v``: ``[B, N, H, D]`` views, each with unit channel stride, heads D elements apart and
+        its own row and batch stride (the column thirds of a packed QKV projection are read in place).  What the strides and addresses must
+        satisfy the library judges."""
+        lib = _lib.load()
+        for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+            if t is None or t.dim() != 4 or t.stride(3) != 1 or (t.shape[2] > 1 and t.stride(2) != t.shape[3]):
+                raise ValueError(f"attention_d64: {name} must be a [B, rows, H, D] view with unit channel stride and heads D elements apart")
+        if q.dtype not in _DT or k.dtype != q.dtype or v.dtype != q.dtype or out.dtype != q.dtype:
+            raise ValueError("attention_d64: q, k, v, out must share one 16-bit dtype (bfloat16 or float16)")
+        B, T, H, D = q.shape
+        N = k.shape[1]
+        if tuple(out.shape) != (B, T, H, D) or tuple(k.shape) != (B, N, H, D) or tuple(v.shape) != (B, N, H, D):
+            raise ValueError("attention_d64: expected q / out [B, T, H, D] and k / v [B, N, H, D]")
+        for t in (q, k, v, out):
+            if not t.is_cuda:
+                raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
+        a = _lib.AttentionD64Args()
+        a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+        # (the strides of dimensions of size 1 are arbitrary in torch: the library gets the natural ones)
+        a.ldq, a.ldk, a.ldv, a.ldo = (t.stride(1) if t.shape[1] > 1 else H * D for t in (q, k, v, out))
+        a.q_bs, a.k_bs, a.v_bs, a.out_bs = (t.stride(0) if B > 1 else 0 for t in (q, k, v, out))
+        a.B, a.T, a.H, a.N, a.head_dim = B, T, H, N, D
+        a.dtype, a.scale = _DT[q.dtype], float(scale)
+        _lib.check(lib.svdq_attention_d64(C.byref(a), _stream()), "attention_d64")
+
+    @staticmethod
     def sana_glue(res, a, timestep, gate_table, mod_table, out, out_mod, stats, T, C_feat, C_pad, lds, gate_row=-1, scale_row=0, shift_row=0, eps=1e-6):
         """Extension (SANA): the glue pass of a SANA block (``svdq_sana_glue``): the gated residual ``t`` of ``res`` and ``a``, written to ``out``,
         its LayerNorm statistics to ``stats`` and the LayerNorm modulated per sample with rows ``scale_row`` / ``shift_row`` of

@@ -167,6 +167,16 @@ class CrossAttentionArgs(C.Structure):
     ]
 
 
+class AttentionD64Args(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("out", C.c_void_p),
+        ("q_bs", C.c_int64), ("k_bs", C.c_int64), ("v_bs", C.c_int64), ("out_bs", C.c_int64),
+        ("ldq", C.c_int32), ("ldk", C.c_int32), ("ldv", C.c_int32), ("ldo", C.c_int32),
+        ("B", C.c_int32), ("T", C.c_int32), ("H", C.c_int32), ("N", C.c_int32),
+        ("head_dim", C.c_int32), ("dtype", C.c_int32), ("scale", C.c_float), ("reserved", C.c_int32),
+    ]
+
+
 class SanaGlueArgs(C.Structure):
     _fields_ = [
         ("res", C.c_void_p), ("a", C.c_void_p), ("timestep", C.c_void_p), ("gate_table", C.c_void_p), ("mod_table", C.c_void_p),
@@ -197,6 +207,7 @@ EXPORTS = {
     "svdq_dwconv3x3": (C.c_int, [C.POINTER(Dwconv3x3Args), C.c_void_p]),
     "svdq_cross_attention": (C.c_int, [C.POINTER(CrossAttentionArgs), C.c_void_p]),
     "svdq_sana_glue": (C.c_int, [C.POINTER(SanaGlueArgs), C.c_void_p]),
+    "svdq_attention_d64": (C.c_int, [C.POINTER(AttentionD64Args), C.c_void_p]),
     "svdq_gemm_workspace_bytes": (C.c_int64, []),
     "svdq_gemm_workspace_bytes_for": (C.c_int64, [C.POINTER(GemmArgs)]),
     "svdq_gemm_workspace_status": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -231,3 +231,45 @@ def cross_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: in
     ops.cross_attention(q3[..., :hd].unflatten(-1, (heads, head_dim)), k, v, out3.unflatten(-1, (heads, head_dim)),
                         key_offsets.contiguous(), key_counts.contiguous(), int(max_keys), head_dim ** -0.5 if scale is None else scale)
     return out
+
+
+def attention_d64(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float | None = None, out: torch.Tensor | None = None):
+    """Stable Diffusion XL's attention, one launch: per sample and head, ``round16(softmax(scale * Q K^T) V)`` at head dimension 64, no mask.
+
+    ``q``: ``[B, T, H*64]``, ``k`` / ``v``: ``[B, N, H*64]``, or all three 2-D (one sample).  Each may be a column slice of a wider buffer: the
+    thirds of a packed ``[B, T, 3*H*64]`` QKV projection and the outputs of ``to_k`` / ``to_v`` are read in place, without a ``chunk``, a
+    ``view`` / ``transpose`` copy or a transposed V.  ``scale`` defaults to ``64 ** -0.5``.  Other head sizes raise ``NotImplementedError``;
+    what the library rejects (strides, alignment, an ``out`` that overlaps an input) raises ``ValueError``.
+
+    Returns ``out`` in the leading shape of ``q`` with ``H*64`` columns, token-major (what ``to_out[0]``'s quantiser reads); a given ``out``
+    may be a column slice of a wider buffer.  No synchronisation and no allocation beyond ``out``."""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"attention_d64: {name} must be a tensor")
+        if t.dtype not in (torch.bfloat16, torch.float16):
+            raise TypeError(f"attention_d64: {name} must be bfloat16 or float16, got {t.dtype}")
+    if k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError(f"attention_d64: k ({k.dtype}) and v ({v.dtype}) must have q's dtype {q.dtype}")
+    if q.dim() not in (2, 3) or k.dim() != q.dim() or v.dim() != q.dim():
+        raise ValueError(f"attention_d64: q, k and v must all be [B, rows, H*64] or all [rows, H*64], got {tuple(q.shape)}, {tuple(k.shape)}, "
+                         f"{tuple(v.shape)}")
+    hd = q.shape[-1]
+    if heads < 1 or hd % heads:
+        raise ValueError(f"attention_d64: {hd} columns are not a multiple of heads={heads}")
+    head_dim = hd // heads
+    if head_dim != 64:
+        raise NotImplementedError(f"attention_d64: head_dim={head_dim}: 64 is implemented ({hd} columns, {heads} heads)")
+    if k.shape[-1] != hd or tuple(v.shape) != tuple(k.shape) or k.shape[:-2] != q.shape[:-2] or q.shape[-2] < 1 or k.shape[-2] < 1:
+        raise ValueError(f"attention_d64: expected q [B, T, {hd}] and k / v [B, N, {hd}] of one batch size with T, N >= 1, got {tuple(q.shape)}, "
+                         f"{tuple(k.shape)}, {tuple(v.shape)}")
+    if out is None:
+        out = torch.empty(*q.shape[:-1], hd, dtype=q.dtype, device=q.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != q.dtype or out.device != q.device or tuple(out.shape) != tuple(q.shape):
+        raise ValueError(f"attention_d64: out must be a {q.dtype} tensor of shape {tuple(q.shape)} on {q.device}, got "
+                         f"{getattr(out, 'dtype', None)} {tuple(getattr(out, 'shape', ()))}")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not t.is_cuda:
+            raise ValueError(f"attention_d64: {name} must be a GPU tensor (there is no CPU path)")
+    q4, k4, v4, o4 = ((t if t.dim() == 3 else t.unsqueeze(0)).unflatten(-1, (heads, 64)) for t in (q, k, v, out))
+    ops.attention_d64(q4, k4, v4, o4, 64 ** -0.5 if scale is None else scale)
+    return out
