@@ -734,6 +734,80 @@ typedef struct svdq_sana_glue_args {
 int svdq_sana_glue(const svdq_sana_glue_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Z-Image block glue, part 1: the sandwich norm (added WITHOUT a version bump: one new symbol and a new args struct, nothing existing
+ * changes, so SVDQ_ABI_VERSION stays 24.  reference: diffusers' ZImageTransformerBlock as nunchaku/models/transformers/transformer_zimage.py
+ * patches it -- four full-width RMSNorms around the two sub-layers, two per-sample modulations, two tanh-gated residuals, each a 16-bit torch
+ * operation).  One row pass closes a sub-layer and opens the next.  Rows are M = B * T tokens, row r belongs to sample b = r / T.
+ * round16 = round to nearest even to `dtype`; every operation between two roundings is ONE plain fp32 multiply or add whose fp32 result is
+ * then rounded to 16 bits (no fused multiply-add, no fp16 clipping):
+ *   rstd(h) = 1 / sqrt(sum_c(h[c]^2) / C + eps);      rms(h, w)[c] = round16(round16(h[c] * rstd(h)) * w[c])
+ *   y = res                                                                          (a NULL)
+ *   y = round16(res + rms(a, w_post))                                                (a given, gate NULL)
+ *   y = round16(res + round16(gate[b] * rms(a, w_post)))                             (a and gate given)
+ *   out[r] = y                                                                       (if out)
+ *   out_mod[r] = rms(y, w_pre)  |  round16(rms(y, w_pre) * scale[b])                 (if out_mod; scale NULL | given)
+ *   stats[r] = (rstd(a) or 0 without a, rstd(y))                                     (if stats)
+ * The sums of squares run in one fixed order (a lane adds its elements in index order, a 6-level butterfly folds the wave), so two calls
+ * are bit-identical; a term passes through at most 8 * ceil(C / 512) + 6 additions.  gate and scale are [B, C] with batch strides gate_bs /
+ * scale_bs (elements); they hold what the block applies, i.e. tanh(gate) and 1 + scale.  Every tensor of rows has its own row stride.
+ * C % 8 == 0, ceil(C / 512) in {1..8, 12, 16, 24, 32} (else SVDQ_E_UNSUPPORTED).  out may alias res when ld_out == ld_res; out_mod may alias
+ * nothing that is read.  One launch, no workspace, no LDS, no atomics: the call can be captured.
+ * Validation (no launch), SVDQ_E_INVALID: NULL args or res, none of out / out_mod / stats, gate without a, a without w_post, out_mod
+ * without w_pre, M or C < 1, C % 8, a row stride below C or not a multiple of 8, T < 1 or M % T, a batch stride below C or not a multiple
+ * of 8, pointers not 16-byte aligned (stats: 8-byte), unknown dtype, an eps that is negative or not finite.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct svdq_sandwich_norm_args {
+    const void *res;    /* [M, C] 16-bit, row stride ld_res */
+    const void *a;      /* [M, C], row stride ld_a: the sub-layer's output, or NULL */
+    const void *w_post; /* [C]: the RMSNorm weight behind the sub-layer (with a) */
+    const void *gate;   /* [B, C], batch stride gate_bs, or NULL */
+    const void *w_pre;  /* [C]: the RMSNorm weight in front of the next sub-layer (with out_mod) */
+    const void *scale;  /* [B, C], batch stride scale_bs, or NULL */
+    void *out;          /* [M, C], row stride ld_out, or NULL */
+    void *out_mod;      /* [M, C], row stride ld_mod, or NULL */
+    float *stats;       /* [M, 2] fp32 or NULL */
+    int64_t gate_bs, scale_bs;            /* in elements */
+    int32_t ld_res, ld_a, ld_out, ld_mod; /* in elements */
+    int32_t M, T, C, dtype;
+    float eps;
+    int32_t reserved;
+} svdq_sandwich_norm_args;
+
+int svdq_sandwich_norm(const svdq_sandwich_norm_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Z-Image block glue, part 2: per-head RMSNorm of Q and K, RoPE and V^T (added WITHOUT a version bump, as above.  reference:
+ * NunchakuZSingleStreamAttnProcessor, nunchaku/models/attention_processors/zimage.py:35-88 -- two RMSNorms over head_dim, a rotation
+ * through fp32 complex tensors, three unflatten / transpose copies into SDPA).  One sample per launch.  qkv is the packed
+ * [T, 3 * H * 128] output of the QKV projection (row stride ld): Q of head h at column h * 128, K at H * 128 + h * 128, V at
+ * 2 * H * 128 + h * 128.  The Q and K thirds are rewritten IN PLACE, per token t and head, on the 128 values x of Q and of K:
+ *   n = round16(round16(x * rstd) * w),  rstd = 1 / sqrt(sum(x^2) / 128 + eps),  w = norm_q | norm_k [128]         (w NULL: n = x)
+ *   x'[2i] = round16(n[2i] * c - n[2i+1] * s),  x'[2i+1] = round16(n[2i] * s + n[2i+1] * c),  (c, s) = freqs[t, i]   (freqs NULL: x' = n)
+ * with plain fp32 multiplies, adds and subtractions between the roundings (no fused multiply-add).  freqs is [T, 64, 2] fp32 (cos, sin):
+ * torch.view_as_real of the pipeline's complex freqs_cis.  V is not changed; with vt, vt[h * 128 + d, t] = V[t, h * 128 + d] for t < T
+ * and +0 for T <= t < L_pad (svdq_attention needs finite V^T under masked keys); nothing is written at or beyond column L_pad.
+ * rstd (optional): [T, 2 * H] fp32, column h for Q and H + h for K of head h (0 where there is no norm).  No atomics; two calls on the
+ * same input are bit-identical.
+ * Validation (no launch), SVDQ_E_INVALID: NULL args or qkv, T < 1, H < 1 or > 65535, ld < 3 * H * 128 or not a multiple of 8, with vt:
+ * L_pad < T or not a multiple of 128, ldvt < L_pad or not a multiple of 8; pointers not 16-byte aligned (rstd: 4-byte), unknown dtype, an
+ * eps that is negative or not finite.  head_dim != 128: SVDQ_E_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct svdq_qk_norm_rope_args {
+    void *qkv;          /* [T, 3 * H * 128] 16-bit, row stride ld */
+    const void *norm_q; /* [128] 16-bit or NULL */
+    const void *norm_k; /* [128] 16-bit or NULL */
+    const float *freqs; /* [T, 64, 2] fp32 or NULL */
+    void *vt;           /* [H * 128, ldvt] 16-bit or NULL */
+    float *rstd;        /* [T, 2 * H] fp32 or NULL */
+    int32_t ld, ldvt;   /* in elements */
+    int32_t T, L_pad, H, head_dim;
+    int32_t dtype;
+    float eps;
+} svdq_qk_norm_rope_args;
+
+int svdq_qk_norm_rope(const svdq_qk_norm_rope_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * AWQ W4A16 GEMV (reference: ops.gemv_awq, nunchaku/csrc/ops.h:123-145 -> src/kernels/awq/gemv_awq.cu:100-286;
  * module nunchaku/models/linear.py:277-414).  The AdaLayerNormZero modulation projections of every block.
  *   out[m, n] = round16( sum_k round16( round16(q[n,k]*scales[k/64,n] + zeros[k/64,n]) * x[m,k] ) ) (+ bias[n])

@@ -8,16 +8,18 @@ reference's own ``ops/*.py`` / ``models/linear.py`` callers run against it uncha
 ``from nunchaku import NunchakuT5EncoderModel`` is the 4-bit T5 text encoder of the FLUX pipelines (AWQ W4A16 group-128
 linears on ``ops.gemm_awq``); transformers is imported on first access of that name, so ``import nunchaku`` works without it.
 ``from nunchaku import NunchakuSanaTransformer2DModel`` is SANA (``nunchaku_amd/models/transformer_sana.py``).
-``from nunchaku.models.unets.unet_sdxl import NunchakuSDXLUNet2DConditionModel`` is Stable Diffusion XL (``nunchaku_amd/models/sdxl.py``).  Z-Image is not part of this package.
+``from nunchaku.models.unets.unet_sdxl import NunchakuSDXLUNet2DConditionModel`` is Stable Diffusion XL (``nunchaku_amd/models/sdxl.py``).
+``from nunchaku import NunchakuZImageTransformer2DModel`` is Z-Image (``nunchaku_amd/models/zimage.py``).
 """
 from .models import (  # noqa: F401
     NunchakuFluxTransformer2dModel,
     NunchakuFluxTransformer2DModelV2,
     NunchakuQwenImageTransformer2DModel,
     NunchakuSanaTransformer2DModel,
+    NunchakuZImageTransformer2DModel,
 )
 
-__all__ = ["NunchakuFluxTransformer2dModel", "NunchakuFluxTransformer2DModelV2", "NunchakuQwenImageTransformer2DModel", "NunchakuSanaTransformer2DModel"]  # (+ NunchakuT5EncoderModel, lazily)
+__all__ = ["NunchakuFluxTransformer2dModel", "NunchakuFluxTransformer2DModelV2", "NunchakuQwenImageTransformer2DModel", "NunchakuSanaTransformer2DModel", "NunchakuZImageTransformer2DModel"]  # (+ NunchakuT5EncoderModel, lazily)
 
 
 def __getattr__(name):

@@ -4,4 +4,5 @@ from .transformers import (  # noqa: F401
     NunchakuFluxTransformer2DModelV2,
     NunchakuQwenImageTransformer2DModel,
     NunchakuSanaTransformer2DModel,
+    NunchakuZImageTransformer2DModel,
 )

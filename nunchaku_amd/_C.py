@@ -1223,6 +1223,69 @@ class _Ops:
         args.dtype, args.eps = _DT[dtype], float(eps)
         _lib.check(lib.svdq_sana_glue(C.byref(args), _stream()), op)
 
+    @staticmethod
+    def sandwich_norm(res, a, w_post, gate, w_pre, scale, out, out_mod, stats, T, C_feat, lds, eps=1e-5):
+        """Extension (Z-Image): one pass of the sandwich norm (``svdq_sandwich_norm``): ``y = res + [gate[b] *] rms(a, w_post)`` to ``out``,
+        ``rms(y, w_pre) [* scale[b]]`` to ``out_mod``, ``(rstd(a), rstd(y))`` to ``stats``.  ``res`` / ``a`` / ``out`` / ``out_mod``: views of
+        token rows with unit column stride, the samples ``T`` rows apart; ``lds``: their four row strides in elements (0 for an absent tensor)
+        -- ``ops.elementwise.sandwich_norm`` checks the shapes and forms them; ``gate`` / ``scale``: ``[B, C_feat]`` with unit column stride;
+        the weights: contiguous ``[C_feat]``; ``stats``: float32 ``[B * T, 2]``.  What is None here and required there the library judges."""
+        op, lib, args = "sandwich_norm", _lib.load(), _lib.SandwichNormArgs()
+        if res is None or res.dtype not in _DT:
+            raise ValueError(f"{op}: res must be a 16-bit view of token rows")
+        dtype = res.dtype
+        M = res.numel() // res.shape[-1]
+        for name, t in (("res", res), ("a", a), ("out", out), ("out_mod", out_mod), ("gate", gate), ("scale", scale)):
+            if t is not None and (t.dtype != dtype or t.stride(-1) != 1):
+                raise ValueError(f"{op}: {name} must have unit column stride and the dtype of res")
+        if T < 1 or M % T:
+            raise ValueError(f"{op}: {M} rows are not whole samples of T={T} tokens")
+        B = M // T
+        for name, t in (("w_post", w_post), ("w_pre", w_pre)):
+            if t is not None and (t.dim() != 1 or t.shape[0] != C_feat or t.dtype != dtype or not t.is_contiguous()):
+                raise ValueError(f"{op}: {name} must be a contiguous [{C_feat}] tensor in the dtype of res")
+        for name, t in (("gate", gate), ("scale", scale)):
+            if t is not None and tuple(t.shape) != (B, C_feat):
+                raise ValueError(f"{op}: {name} must be [{B}, {C_feat}], got {tuple(t.shape)}")
+        _row_stats(op, stats, M)
+        args.res, args.a, args.out, args.out_mod = _ptr(res, True), _ptr(a, True), _ptr(out, True), _ptr(out_mod, True)
+        args.w_post, args.w_pre, args.gate, args.scale = _ptr(w_post), _ptr(w_pre), _ptr(gate, True), _ptr(scale, True)
+        args.stats = _ptr(stats, True)
+        args.ld_res, args.ld_a, args.ld_out, args.ld_mod = lds
+        # (the strides of dimensions of size 1 are arbitrary in torch: the library gets the natural ones)
+        args.gate_bs = 0 if gate is None else gate.stride(0) if B > 1 else C_feat
+        args.scale_bs = 0 if scale is None else scale.stride(0) if B > 1 else C_feat
+        args.M, args.T, args.C, args.dtype, args.eps = M, int(T), int(C_feat), _DT[dtype], float(eps)
+        _lib.check(lib.svdq_sandwich_norm(C.byref(args), _stream()), op)
+
+    @staticmethod
+    def qk_norm_rope(qkv, norm_q, norm_k, freqs, vt, rstd, T, L_pad, H, eps=1e-5):
+        """Extension (Z-Image): per-head RMSNorm and RoPE of the Q and K thirds of one sample's packed ``qkv`` ``[>= T, 3 * H * 128]`` (any row
+        stride) in place, V transposed into ``vt`` ``[H * 128, >= L_pad]`` with zeros in columns ``[T, L_pad)`` (``svdq_qk_norm_rope``).
+        ``norm_q`` / ``norm_k``: contiguous ``[128]`` or None; ``freqs``: contiguous float32 ``[T, 64, 2]`` or None; ``rstd``: contiguous float32
+        ``[T, 2 * H]`` or None.  What the sizes must satisfy the library judges."""
+        op, lib, args = "qk_norm_rope", _lib.load(), _lib.QkNormRopeArgs()
+        if qkv is None or qkv.dim() != 2 or qkv.dtype not in _DT or qkv.stride(1) != 1:
+            raise ValueError(f"{op}: qkv must be a 16-bit [rows, 3 * H * 128] view with unit column stride")
+        if qkv.shape[0] < T or qkv.shape[1] != 3 * H * 128:
+            raise ValueError(f"{op}: qkv {tuple(qkv.shape)} does not hold T={T} rows of 3 * {H} * 128 columns")
+        for name, t in (("norm_q", norm_q), ("norm_k", norm_k)):
+            if t is not None and (t.dtype != qkv.dtype or tuple(t.shape) != (128,) or not t.is_contiguous()):
+                raise ValueError(f"{op}: {name} must be a contiguous [128] tensor in the dtype of qkv")
+        if freqs is not None and (freqs.dtype != torch.float32 or tuple(freqs.shape) != (T, 64, 2) or not freqs.is_contiguous()):
+            raise ValueError(f"{op}: freqs must be a contiguous float32 [{T}, 64, 2] tensor (torch.view_as_real of freqs_cis)")
+        if vt is not None and (vt.dim() != 2 or vt.dtype != qkv.dtype or vt.shape[0] != H * 128 or vt.shape[1] < L_pad or vt.stride(1) != 1):
+            raise ValueError(f"{op}: vt must be a [{H * 128}, >= {L_pad}] view in the dtype of qkv with unit column stride")
+        if rstd is not None and (rstd.dtype != torch.float32 or tuple(rstd.shape) != (T, 2 * H) or not rstd.is_contiguous()):
+            raise ValueError(f"{op}: rstd must be a contiguous float32 [{T}, {2 * H}] tensor")
+        args.qkv, args.norm_q, args.norm_k, args.freqs = _ptr(qkv, True), _ptr(norm_q), _ptr(norm_k), _ptr(freqs)
+        args.vt, args.rstd = _ptr(vt, True), _ptr(rstd)
+        args.ld = qkv.stride(0) if qkv.shape[0] > 1 else max(qkv.stride(0), qkv.shape[1])
+        args.ldvt = 0 if vt is None else vt.stride(0) if vt.shape[0] > 1 else max(vt.stride(0), vt.shape[1])
+        args.T, args.L_pad, args.H, args.head_dim = int(T), int(L_pad), int(H), 128
+        args.dtype, args.eps = _DT[qkv.dtype], float(eps)
+        _lib.check(lib.svdq_qk_norm_rope(C.byref(args), _stream()), op)
+
 
 class _Utils:
     """reference: csrc/pybind.cpp:118-123 -- logging / sm_75 toggles; no-ops here."""

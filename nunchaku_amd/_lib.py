@@ -189,6 +189,26 @@ class SanaGlueArgs(C.Structure):
     ]
 
 
+class SandwichNormArgs(C.Structure):
+    _fields_ = [
+        ("res", C.c_void_p), ("a", C.c_void_p), ("w_post", C.c_void_p), ("gate", C.c_void_p), ("w_pre", C.c_void_p), ("scale", C.c_void_p),
+        ("out", C.c_void_p), ("out_mod", C.c_void_p), ("stats", C.c_void_p),
+        ("gate_bs", C.c_int64), ("scale_bs", C.c_int64),
+        ("ld_res", C.c_int32), ("ld_a", C.c_int32), ("ld_out", C.c_int32), ("ld_mod", C.c_int32),
+        ("M", C.c_int32), ("T", C.c_int32), ("C", C.c_int32), ("dtype", C.c_int32),
+        ("eps", C.c_float), ("reserved", C.c_int32),
+    ]
+
+
+class QkNormRopeArgs(C.Structure):
+    _fields_ = [
+        ("qkv", C.c_void_p), ("norm_q", C.c_void_p), ("norm_k", C.c_void_p), ("freqs", C.c_void_p), ("vt", C.c_void_p), ("rstd", C.c_void_p),
+        ("ld", C.c_int32), ("ldvt", C.c_int32),
+        ("T", C.c_int32), ("L_pad", C.c_int32), ("H", C.c_int32), ("head_dim", C.c_int32),
+        ("dtype", C.c_int32), ("eps", C.c_float),
+    ]
+
+
 EXPORTS = {
     "svdq_quantize_w4a4_act_fuse_lora": (C.c_int, [C.POINTER(QuantizeArgs), C.c_void_p]),
     "svdq_gemm_w4a4": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
@@ -208,6 +228,8 @@ EXPORTS = {
     "svdq_cross_attention": (C.c_int, [C.POINTER(CrossAttentionArgs), C.c_void_p]),
     "svdq_sana_glue": (C.c_int, [C.POINTER(SanaGlueArgs), C.c_void_p]),
     "svdq_attention_d64": (C.c_int, [C.POINTER(AttentionD64Args), C.c_void_p]),
+    "svdq_sandwich_norm": (C.c_int, [C.POINTER(SandwichNormArgs), C.c_void_p]),
+    "svdq_qk_norm_rope": (C.c_int, [C.POINTER(QkNormRopeArgs), C.c_void_p]),
     "svdq_gemm_workspace_bytes": (C.c_int64, []),
     "svdq_gemm_workspace_bytes_for": (C.c_int64, [C.POINTER(GemmArgs)]),
     "svdq_gemm_workspace_status": (C.c_int, [C.c_void_p, C.c_void_p]),

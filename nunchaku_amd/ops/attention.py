@@ -273,3 +273,49 @@ def attention_d64(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
     q4, k4, v4, o4 = ((t if t.dim() == 3 else t.unsqueeze(0)).unflatten(-1, (heads, 64)) for t in (q, k, v, out))
     ops.attention_d64(q4, k4, v4, o4, 64 ** -0.5 if scale is None else scale)
     return out
+
+
+def qk_norm_rope(qkv: torch.Tensor, heads: int, tokens: int | None = None, *, norm_q: torch.Tensor | None = None, norm_k: torch.Tensor | None = None,
+                 freqs_cis: torch.Tensor | None = None, vt: torch.Tensor | None = None, eps: float = 1e-5, want_rstd: bool = False):
+    """Z-Image's step between the QKV projection and the attention, for ONE sample, in one launch (``svdq_qk_norm_rope``): per token and head
+    the RMSNorm of Q and of K over the 128 values of the head (``norm_q`` / ``norm_k``: the ``[128]`` weights, None for no normalisation), then
+    the rotation of the pairs ``(2i, 2i + 1)`` by ``freqs_cis[t, i]`` (None: no rotation), one 16-bit rounding per torch operation of the
+    reference processor.  ``qkv``: ``[L, 3 * H * 128]`` with any row stride, whose first ``tokens`` rows (default: all) are real; its Q and K
+    thirds are rewritten IN PLACE.  ``freqs_cis``: complex64 ``[tokens, 64]`` as the pipeline makes it, or its float32 ``[tokens, 64, 2]``
+    ``torch.view_as_real``.  ``vt``: a ``[H * 128, >= L]`` buffer that gets V transposed in columns ``[0, tokens)`` and zeros in
+    ``[tokens, L)`` (``L`` a multiple of 128: what ``attention_packed(qkv, vt[:, :L], heads, kv_valid=(tokens,))`` then reads), None for none.
+    Returns ``qkv``, or ``(qkv, rstd)`` with ``want_rstd``: the float32 ``[tokens, 2 * H]`` reciprocal RMS values (Q heads, then K heads)."""
+    op = "qk_norm_rope"
+    if not isinstance(qkv, torch.Tensor) or qkv.dim() != 2:
+        raise ValueError(f"{op}: qkv must be one sample's [L, 3 * H * 128] tensor")
+    if qkv.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"{op}: qkv must be bfloat16 or float16, got {qkv.dtype}")
+    L, width = qkv.shape
+    if heads < 1 or width != 3 * heads * 128:
+        raise NotImplementedError(f"{op}: head_dim 128 is implemented: {width} columns are not 3 * heads={heads} * 128")
+    T = L if tokens is None else int(tokens)
+    if not 1 <= T <= L:
+        raise ValueError(f"{op}: tokens={T} must be within the {L} rows of qkv")
+    for name, t in (("norm_q", norm_q), ("norm_k", norm_k)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != qkv.dtype or tuple(t.shape) != (128,)):
+            raise ValueError(f"{op}: {name} must be a {qkv.dtype} [128] tensor")
+    freqs = None
+    if freqs_cis is not None:
+        if not isinstance(freqs_cis, torch.Tensor):
+            raise TypeError(f"{op}: freqs_cis must be a tensor")
+        freqs = torch.view_as_real(freqs_cis) if freqs_cis.is_complex() else freqs_cis
+        if freqs.dtype != torch.float32 or tuple(freqs.shape) != (T, 64, 2):
+            raise ValueError(f"{op}: freqs_cis must be complex64 [{T}, 64] or float32 [{T}, 64, 2], got {freqs_cis.dtype} {tuple(freqs_cis.shape)}")
+        freqs = freqs.contiguous()
+    if vt is not None:
+        if not isinstance(vt, torch.Tensor) or vt.dtype != qkv.dtype or vt.dim() != 2 or vt.shape[0] != heads * 128 or vt.shape[1] < L:
+            raise ValueError(f"{op}: vt must be a {qkv.dtype} [{heads * 128}, >= {L}] tensor")
+        if L % 128:
+            raise ValueError(f"{op}: with vt the rows of qkv are the padded length of the attention: {L} is not a multiple of 128")
+    for name, t in (("qkv", qkv), ("norm_q", norm_q), ("norm_k", norm_k), ("freqs_cis", freqs), ("vt", vt)):
+        if t is not None and not t.is_cuda:
+            raise ValueError(f"{op}: {name} must be a GPU tensor (there is no CPU path)")
+    rstd = torch.empty(T, 2 * heads, dtype=torch.float32, device=qkv.device) if want_rstd else None
+    ops.qk_norm_rope(qkv, None if norm_q is None else norm_q.contiguous(), None if norm_k is None else norm_k.contiguous(), freqs, vt, rstd,
+                     T, L, heads, eps=eps)
+    return (qkv, rstd) if want_rstd else qkv

@@ -275,3 +275,76 @@ def sana_glue(res: torch.Tensor, a: torch.Tensor | None = None, *, timestep: tor
                   T, C, C_pad, gate_row=-1 if gate_row is None else int(gate_row), scale_row=int(scale_row or 0), shift_row=int(shift_row or 0),
                   eps=eps, lds=lds)
     return out, out_mod, stats
+
+
+def sandwich_norm(res: torch.Tensor, a: torch.Tensor | None = None, *, w_post: torch.Tensor | None = None, gate: torch.Tensor | None = None,
+                  w_pre: torch.Tensor | None = None, scale: torch.Tensor | None = None, out: torch.Tensor | bool | None = None,
+                  out_mod: torch.Tensor | bool | None = None, want_stats: bool = False, eps: float = 1e-5):
+    """One pass of Z-Image's sandwich norm (``svdq_sandwich_norm``): it closes a sub-layer and opens the next.  With
+    ``rms(h, w) = (h * rstd(h)) * w`` (diffusers' ``RMSNorm``; one 16-bit rounding per operation throughout, fp32 in between)::
+
+        y = res  |  res + rms(a, w_post)  |  res + gate[b] * rms(a, w_post)            (no a | no gate | gate)
+        out = y;   out_mod = rms(y, w_pre)  |  rms(y, w_pre) * scale[b]                  (no scale | scale)
+
+    ``res`` / ``a``: ``[B, T, C]`` with unit stride on the last axis and the samples T rows apart (a column slice of a wider buffer will do);
+    ``gate`` / ``scale``: ``[B, C]`` -- what the block applies: ``tanh(gate)`` and ``1 + scale``; the weights: ``[C]``.  ``out`` / ``out_mod``: a
+    tensor to write into (``out`` may be ``res``), True to allocate one, None / False for none; ``out`` defaults to "when ``a`` is given",
+    ``out_mod`` to "when ``w_pre`` is given".  Returns ``(out, out_mod, stats)`` with None for what was not asked for; ``stats`` is the float32
+    ``[B * T, 2]`` ``(rstd(a) or 0, rstd(y))``."""
+    op = "sandwich_norm"
+    if not isinstance(res, torch.Tensor) or res.dim() != 3:
+        raise ValueError(f"{op}: res must be a [B, T, C] tensor")
+    if res.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"{op}: res must be bfloat16 or float16, got {res.dtype}")
+    B, T, C = res.shape
+    if C < 8 or C % 8 or B < 1 or T < 1:
+        raise ValueError(f"{op}: need C={C} a multiple of 8 and at least one row, got res {tuple(res.shape)}")
+    if out is None:
+        out = a is not None
+    if out_mod is None:
+        out_mod = w_pre is not None
+    out = torch.empty(B, T, C, dtype=res.dtype, device=res.device) if out is True else None if out is False else out
+    out_mod = torch.empty(B, T, C, dtype=res.dtype, device=res.device) if out_mod is True else None if out_mod is False else out_mod
+    if out is None and out_mod is None and not want_stats:
+        raise ValueError(f"{op}: nothing to do: none of out, out_mod and stats is asked for")
+    if gate is not None and a is None:
+        raise ValueError(f"{op}: a gate needs a")
+    if a is not None and w_post is None:
+        raise ValueError(f"{op}: a needs w_post")
+    if out_mod is not None and w_pre is None:
+        raise ValueError(f"{op}: out_mod needs w_pre")
+    if scale is not None and out_mod is None:
+        raise ValueError(f"{op}: scale needs out_mod")
+    if not (eps >= 0.0) or eps == float("inf"):
+        raise ValueError(f"{op}: eps={eps} must be finite and not negative")
+
+    def row_stride(name, t):
+        """the row stride of a [B, T, C] view whose samples lie T rows apart (0 for None)"""
+        if t is None:
+            return 0
+        if not isinstance(t, torch.Tensor) or t.dtype != res.dtype:
+            raise TypeError(f"{op}: {name} must be a {res.dtype} tensor like res")
+        if t.device != res.device:
+            raise ValueError(f"{op}: {name} must live on res's device {res.device}, got {t.device}")
+        if tuple(t.shape) != (B, T, C):
+            raise ValueError(f"{op}: {name} must be [{B}, {T}, {C}], got {tuple(t.shape)}")
+        s0, s1, s2 = t.stride()
+        if s2 != 1 or (B > 1 and T > 1 and s0 != T * s1):
+            raise ValueError(f"{op}: {name} must have unit stride on its last axis and hold its samples T rows apart")
+        # (the strides of dimensions of size 1 are arbitrary in torch: the library gets the natural ones)
+        return s1 if T > 1 else s0 if B > 1 else C
+
+    lds = (row_stride("res", res), row_stride("a", a), row_stride("out", out), row_stride("out_mod", out_mod))
+    for name, t in (("w_post", w_post), ("w_pre", w_pre)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != res.dtype or tuple(t.shape) != (C,) or not t.is_contiguous()):
+            raise ValueError(f"{op}: {name} must be a contiguous {res.dtype} [{C}] tensor")
+    for name, t in (("gate", gate), ("scale", scale)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != res.dtype or tuple(t.shape) != (B, C) or t.stride(1) != 1):
+            raise ValueError(f"{op}: {name} must be a {res.dtype} [{B}, {C}] tensor with unit stride on its last axis")
+    for name, t in (("res", res), ("a", a), ("w_post", w_post), ("gate", gate), ("w_pre", w_pre), ("scale", scale), ("out", out), ("out_mod", out_mod)):
+        if t is not None and not t.is_cuda:
+            raise ValueError(f"{op}: {name} must be a GPU tensor (there is no CPU path)")
+    stats = torch.empty(B * T, 2, dtype=torch.float32, device=res.device) if want_stats else None
+    ops.sandwich_norm(res, a, w_post if a is not None else None, gate, w_pre if out_mod is not None else None, scale, out, out_mod, stats, T, C,
+                      lds=lds, eps=eps)
+    return out, out_mod, stats
