@@ -28,13 +28,13 @@
 // workgroup order: deterministic) and runs the epilogue.  Logical workgroup g = (blockIdx % 8) * G/8 + blockIdx / 8: the
 // workgroups of one XCD take neighbouring tasks, i.e. the same few heads, and walk their keys together.
 #include "svdq_common.h"
+#include "attn_frag.h"
 #include "lowrank_split.h"
 #include <type_traits>
 
-// tools/ablate/build_attn.py builds timing variants of geometry 2's tile loop (the generator under other options) by redefining these
-#ifndef SVDQ_ATTN_LOOP_INC_BF16
-#define SVDQ_ATTN_LOOP_INC_BF16 "attention_loop64_bf16.inc"
-#define SVDQ_ATTN_LOOP_INC_FP16 "attention_loop64_fp16.inc"
+// tools/ablate/build_attn.py builds timing variants of geometry 2's tile loop (the generator under other options) by redefining this
+#ifndef SVDQ_ATTN_LOOP_INC
+#define SVDQ_ATTN_LOOP_INC "attention_loop64.inc"
 #endif
 // clock / phase stamps of the tools-built probe library (tools/ablate/attn_probe_hooks.inc); nothing in the product build
 #ifdef SVDQ_PROBE
@@ -120,14 +120,6 @@ struct AttnSchedule {
     }
 };
 
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-// two floats -> one dword of two RNE-rounded 16-bit values (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32)
-template <int DT> __device__ __forceinline__ unsigned pack2(float a, float b) {
-    if constexpr (DT == SVDQ_BF16) return __builtin_bit_cast(unsigned, __builtin_convertvector((v2f){a, b}, bf16x2));
-    else return __builtin_bit_cast(unsigned, __builtin_convertvector((v2f){a, b}, f16x2));
-}
 // (a * s, b * s) -> one dword of two 16-bit values, rounded as finish_rows' fused quantiser rounds the same products.  fp16: the backend folds a SCALAR
 // `(_Float16)(x * s)` into v_fma_mixlo/hi_f16 -- ONE rounding of the exact product -- while the packed conversion of two fp32 products rounds twice
 // (fp32, then fp16) and lands one fp16 step away on ~1e-4 of the values.  Until round 6 the 16-bit output path took the packed form and the fused
@@ -647,7 +639,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attention_kernel(const AttnPa
 // and the instruction stream itself overlaps what the two co-resident waves of a SIMD used to overlap by chance:
 //   iteration j:   P(j) = exp2(S'(j)) -> 16-bit fragments   beside the 32 MFMAs of  S'(j+1) = K(j+1) Q'^T - mc
 //                  row maxima of S'(j+1)                     beside the 32 MFMAs of  O += V^T(j) P(j)
-// The tile loop is generated assembly with explicit registers (tools/gen_attn_loop.py -> attention_loop64_*.inc; DESIGN.md 6b:
+// The tile loop is generated assembly with explicit registers (tools/gen_attn_loop.py -> attention_loop64.inc; DESIGN.md 6b:
 // what an instruction beside an MFMA costs was measured, the iteration is packed to it slot by slot, and the hazards a compiler
 // would cover are covered by construction); the segment's first and last tile, the schedule, the slabs and the epilogue are C++.
 // Scores are RELATIVE and in log2 units: Q is multiplied by scale * log2(e) when it is loaded (16-bit rounding of the product: the
@@ -883,12 +875,14 @@ __global__ __launch_bounds__(256, 1) void attention_kernel64(const AttnParams p)
               "v178", "v179", "v180", "v181", "v182", "v183",                                                                        \
               "v246", "v247", "v252", "v253", "v254", "v255"
             if constexpr (DT == SVDQ_BF16) {
+#include "asm_tokens_bf16.h"
                 asm volatile(
-#include SVDQ_ATTN_LOOP_INC_BF16
+#include SVDQ_ATTN_LOOP_INC
                     SVDQ_ATTN_LOOP_OPERANDS);
             } else {
+#include "asm_tokens_fp16.h"
                 asm volatile(
-#include SVDQ_ATTN_LOOP_INC_FP16
+#include SVDQ_ATTN_LOOP_INC
                     SVDQ_ATTN_LOOP_OPERANDS);
             }
 #undef SVDQ_ATTN_LOOP_OPERANDS

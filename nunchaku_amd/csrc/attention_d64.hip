@@ -11,9 +11,9 @@
 // buffer c & 1, the registers are written to buffer (c + 1) & 1 (last read in iteration c - 1, which every wave left through the previous
 // barrier), one barrier.
 //
-// Fragments and arithmetic are cross_attention.hip's at D = 64 (S^T = K Q^T, O^T = V^T P^T on the 32x32x16 MFMA, a lane owning a query row;
-// four K-steps of Q stay in registers for the whole walk; online softmax over chunks of 64 keys from key 0: exp2 with scale * log2(e),
-// P rounded to 16 bits before it meets V, the row sum over the rounded values, the normalisation after the last MFMA).
+// Fragments and arithmetic are attn_frag.h's, as in cross_attention.hip, at D = 64 (S^T = K Q^T, O^T = V^T P^T on the 32x32x16 MFMA, a lane
+// owning a query row; four K-steps of Q stay in registers for the whole walk; online softmax over chunks of 64 keys from key 0: exp2 with
+// scale * log2(e); attn_frag.h states the softmax contract).
 // LDS images: a K row and a V^T row are both 128 bytes = 8 pieces of 16 bytes; two rows cover the 64 banks once, so piece p of row r lives at
 // column p ^ ((r >> 1) & 7): the sixteen rows of a ds_read_b128 lane group fall on sixteen distinct 16-byte slots.
 // V is transposed on its way to LDS: a thread loads 2 channels (one dword) of 8 keys, in the key order the S accumulator delivers
@@ -23,6 +23,7 @@
 // and their scores -inf, probability exactly 0.  Rows at or beyond T: loads clamped to row T - 1, stores skipped.  Every offset is formed
 // in 64 bits.  No atomics, no workspace; every output element is produced by one lane in a fixed order: two launches are bit-equal.
 #include "svdq_common.h"
+#include "attn_frag.h"
 
 namespace svdq {
 
@@ -40,16 +41,6 @@ constexpr int AD_ROWS = AD_NW * 32; // query rows per tile
 constexpr int AD_CHUNK = 64;        // keys per online-softmax step and per LDS stage
 constexpr int AD_D = 64;
 constexpr int AD_STAGE = 2 * AD_CHUNK * AD_D * 2; // bytes of one stage: K [64 keys][128 B], then V^T [64 channels][128 B]
-
-template <int DT> __device__ __forceinline__ unsigned ad_pack2(float a, float b) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    if constexpr (DT == SVDQ_BF16) return __builtin_bit_cast(unsigned, __builtin_convertvector((f2){a, b}, b2));
-    else return __builtin_bit_cast(unsigned, __builtin_convertvector((f2){a, b}, h2));
-}
-template <int DT> __device__ __forceinline__ float ad_lo(unsigned pk) { return h2f(hfrom<typename Half<DT>::T>((unsigned short)(pk & 0xffffu))); }
-template <int DT> __device__ __forceinline__ float ad_hi(unsigned pk) { return h2f(hfrom<typename Half<DT>::T>((unsigned short)(pk >> 16))); }
 
 template <int DT>
 __global__ __launch_bounds__(AD_NW * 64) void attention_d64_kernel(const AttnD64Params p) {
@@ -101,12 +92,7 @@ __global__ __launch_bounds__(AD_NW * 64) void attention_d64_kernel(const AttnD64
         *(lds_v4i *)(L8 + (base + kw0)) = kreg[0];
         *(lds_v4i *)(L8 + (base + kw1)) = kreg[1];
         v4i lo, hi; // channel 2 cp: the low halves of the 8 keys; channel 2 cp + 1: the high halves
-#pragma unroll
-        for (int w = 0; w < 4; w++) {
-            const unsigned a = vreg[2 * w], bb = vreg[2 * w + 1];
-            lo[w] = (int)((a & 0xffffu) | (bb << 16));
-            hi[w] = (int)((a >> 16) | (bb & 0xffff0000u));
-        }
+        transpose8x2_pieces(vreg, lo, hi);
         *(lds_v4i *)(L8 + (base + vw)) = lo;
         *(lds_v4i *)(L8 + (base + vw + RB)) = hi;
     };
@@ -166,22 +152,11 @@ __global__ __launch_bounds__(AD_NW * 64) void attention_d64_kernel(const AttnD64
 #pragma unroll
                 for (int kt = 0; kt < 2; kt++)
 #pragma unroll
-                    for (int r = 0; r < 16; r++) {
-                        const int key = AD_CHUNK * ch + 32 * kt + 8 * (r >> 2) + 4 * h + (r & 3);
-                        s[kt][r] = key < N ? s[kt][r] : -INFINITY;
-                    }
+                    for (int r = 0; r < 16; r++) s[kt][r] = AD_CHUNK * ch + 32 * kt + score_key(r, h) < N ? s[kt][r] : -INFINITY;
             }
             // ---- online softmax: lane holds 32 of the 64 scores of query row lr, lane ^ 32 the others ----
-            float mloc = s[0][0];
-#pragma unroll
-            for (int kt = 0; kt < 2; kt++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) mloc = fmaxf(mloc, s[kt][r]);
-            mloc = fmaxf(mloc, __shfl_xor(mloc, 32));
-            const float m_new = fmaxf(m_run, mloc);
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c); // 0 on the first chunk (m_run = -inf), 1 while the maximum stands
-            m_run = m_new;
-            const float nmc = -(m_new * c);
+            const SoftmaxScale sc = online_softmax_scale(m_run, row_max<2>(s), c);
+            m_run = sc.m;
             V8 pf[4];
             float lc = 0.f;
 #pragma unroll
@@ -190,19 +165,16 @@ __global__ __launch_bounds__(AD_NW * 64) void attention_d64_kernel(const AttnD64
                 unsigned w[4];
 #pragma unroll
                 for (int i = 0; i < 4; i++) {
-                    const float e0 = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][r0 + 2 * i], c, nmc));
-                    const float e1 = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][r0 + 2 * i + 1], c, nmc));
-                    w[i] = ad_pack2<DT>(e0, e1);
-                    lc += ad_lo<DT>(w[i]);
-                    lc += ad_hi<DT>(w[i]);
+                    w[i] = prob_pair<DT>(s[kt][r0 + 2 * i], s[kt][r0 + 2 * i + 1], c, sc.nmc);
+                    lc = add_rounded<DT>(lc, w[i]);
                 }
                 pf[ks] = __builtin_bit_cast(V8, v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]});
             }
-            l = l * alpha + lc;
+            l = l * sc.alpha + lc;
             // ---- O^T = alpha O^T + V^T P^T ----
 #pragma unroll
             for (int dt = 0; dt < NDT; dt++) {
-                o[dt] = o[dt] * alpha;
+                o[dt] = o[dt] * sc.alpha;
 #pragma unroll
                 for (int ks = 0; ks < 4; ks++) {
                     const v4i vv = *(const lds_v4i *)(L8 + (base + va[ks] + dt * 32 * RB));
@@ -215,27 +187,15 @@ __global__ __launch_bounds__(AD_NW * 64) void attention_d64_kernel(const AttnD64
     }
     if (!active) return;
     l += __shfl_xor(l, 32);
-    // ---- round16(o / l).  Lane (lr, h) holds channels 32 dt + 8 g + 4 h + e; a v_permlane32_swap per dword pair gives every lane 8 consecutive
-    //      channels 32 dt + 16 j2 + 8 h .. +7: 16-byte stores ----
+    // ---- round16(o / l): 16-byte stores ----
     const float inv = 1.0f / l;
     uint16_t *orow = p.out + (size_t)b * (size_t)p.out_bs + (size_t)(live ? row : p.T - 1) * p.ldo + (size_t)head * D + 8 * h;
 #pragma unroll
     for (int dt = 0; dt < NDT; dt++)
 #pragma unroll
         for (int j2 = 0; j2 < 2; j2++) {
-            unsigned x[2], y[2];
-#pragma unroll
-            for (int d2 = 0; d2 < 2; d2++) {
-                float t[4];
-#pragma unroll
-                for (int i = 0; i < 4; i++) t[i] = o[dt][8 * j2 + 4 * (i >> 1) + 2 * d2 + (i & 1)] * inv;
-                x[d2] = ad_pack2<DT>(t[0], t[1]);
-                y[d2] = ad_pack2<DT>(t[2], t[3]);
-                const auto sw = __builtin_amdgcn_permlane32_swap(x[d2], y[d2], false, false);
-                x[d2] = sw[0];
-                y[d2] = sw[1];
-            }
-            if (live) *reinterpret_cast<v4i *>(orow + 32 * dt + 16 * j2) = v4i{(int)x[0], (int)x[1], (int)y[0], (int)y[1]};
+            const v4i w = o_tile_piece<DT>(o[dt], j2, inv);
+            if (live) *reinterpret_cast<v4i *>(orow + 32 * dt + 16 * j2) = w;
         }
 }
 

@@ -9,13 +9,13 @@
 // Shape of the problem: thousands of queries per sample against at most a few hundred keys of that sample.  A workgroup (8 waves) belongs
 // to one (sample, head): it stages that pair's K and V into LDS ONCE (RESIDENT, not streamed: see DESIGN 6m), passes the only barrier and
 // walks 256-row query tiles, a wave owning 32 rows.  300 keys are ten 32-key accumulator tiles -- too many to keep every score of a row
-// live as ip_attention.hip does -- so a wave walks the resident keys in CHUNKS of 64 with an online softmax (attention.hip's: running
-// maximum m, running sum l over the ROUNDED probabilities, O rescaled by exp2((m_old - m_new) c), normalisation after the last MFMA: a row
-// dominated by one key returns that key's V row exactly).  Chunks start at the sample's first key: a row's arithmetic depends on its own
-// sample's keys only, not on where they lie in the buffer or on what other samples hold.
+// live as ip_attention.hip does -- so a wave walks the resident keys in CHUNKS of 64 with an online softmax (attn_frag.h states its
+// contract).  Chunks start at the sample's first key: a row's arithmetic depends on its own sample's keys
+// only, not on where they lie in the buffer or on what other samples hold.
 //
-// Fragments are ip_attention.hip's (S^T = K Q^T, O^T = V^T P^T on the 32x32x16 MFMA; V transposed while staging in the key order the
-// accumulator delivers, so P^T goes from the S accumulator to the PV MFMA without a cross-lane exchange).  What the head dimension changes:
+// Fragments are attn_frag.h's, shared with ip_attention.hip (S^T = K Q^T, O^T = V^T P^T on the 32x32x16 MFMA; V transposed while staging in
+// the key order the accumulator delivers, so P^T goes from the S accumulator to the PV MFMA without a cross-lane exchange).  What the head
+// dimension changes:
 //   * K-steps of QK^T: KS = ceil(D / 16) = 5 / 7 / 8.  D = 72 is four and a half: the 16-byte piece of channels 72..79 is ZERO in LDS (K) and
 //     in registers (Q) -- neither is loaded: those columns belong to the next head (or lie beyond H * D), and 0 * Inf would be NaN.
 //   * K rows in LDS are 2 KS pieces = 160 / 224 / 256 bytes.  160 and 224 bytes step 8 consecutive rows over 8 distinct 32-byte bank groups:
@@ -28,7 +28,7 @@
 // A sample without keys: its rows are written as zeros (flash-attention does the same).  Rows at or beyond T: loads clamped to row T - 1,
 // stores skipped.  No atomics, no workspace; every output element is produced by one lane in a fixed order: two launches are bit-equal.
 #include "svdq_common.h"
-#include <atomic>
+#include "attn_frag.h"
 
 namespace svdq {
 
@@ -50,16 +50,6 @@ constexpr int XA_MAX_KEYS = 320;    // D = 128: 320 * (256 + 256) bytes = 160 Ki
 
 constexpr int xa_krow_bytes(int d) { return (d + 15) / 16 * 32; }
 constexpr int xa_lds_bytes(int d, int kcap) { return kcap * (xa_krow_bytes(d) + 2 * d); }
-
-template <int DT> __device__ __forceinline__ unsigned xa_pack2(float a, float b) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    if constexpr (DT == SVDQ_BF16) return __builtin_bit_cast(unsigned, __builtin_convertvector((f2){a, b}, b2));
-    else return __builtin_bit_cast(unsigned, __builtin_convertvector((f2){a, b}, h2));
-}
-template <int DT> __device__ __forceinline__ float xa_lo(unsigned pk) { return h2f(hfrom<typename Half<DT>::T>((unsigned short)(pk & 0xffffu))); }
-template <int DT> __device__ __forceinline__ float xa_hi(unsigned pk) { return h2f(hfrom<typename Half<DT>::T>((unsigned short)(pk >> 16))); }
 
 template <int DT, int D>
 __global__ __launch_bounds__(XA_NW * 64, 2) void cross_attention_kernel(const XAttnParams p) {
@@ -129,12 +119,7 @@ __global__ __launch_bounds__(XA_NW * 64, 2) void cross_attention_kernel(const XA
             }
 #pragma unroll
             for (int e = 0; e < 8; e++) { // channel 8 cb + e: the e-th 16-bit value of every key row
-                v4i col;
-#pragma unroll
-                for (int w = 0; w < 4; w++) {
-                    const unsigned a = (unsigned)rows[2 * w][e >> 1], bb = (unsigned)rows[2 * w + 1][e >> 1];
-                    col[w] = (int)((e & 1) ? ((a >> 16) | (bb & 0xffff0000u)) : ((a & 0xffffu) | (bb << 16)));
-                }
+                const v4i col = transpose8x8_piece(rows, e);
                 const int d = 8 * cb + e;
                 *(lds_v4i *)(L8 + (VBASE + d * RB + ((j ^ (d & 7)) << 4))) = col;
             }
@@ -198,22 +183,11 @@ __global__ __launch_bounds__(XA_NW * 64, 2) void cross_attention_kernel(const XA
 #pragma unroll
                 for (int kt = 0; kt < 2; kt++)
 #pragma unroll
-                    for (int r = 0; r < 16; r++) {
-                        const int key = XA_CHUNK * ch + 32 * kt + 8 * (r >> 2) + 4 * h + (r & 3);
-                        s[kt][r] = key < n ? s[kt][r] : -INFINITY;
-                    }
+                    for (int r = 0; r < 16; r++) s[kt][r] = XA_CHUNK * ch + 32 * kt + score_key(r, h) < n ? s[kt][r] : -INFINITY;
             }
             // ---- online softmax: lane holds 32 of the 64 scores of query row lr, lane ^ 32 the others ----
-            float mloc = s[0][0];
-#pragma unroll
-            for (int kt = 0; kt < 2; kt++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) mloc = fmaxf(mloc, s[kt][r]);
-            mloc = fmaxf(mloc, __shfl_xor(mloc, 32));
-            const float m_new = fmaxf(m_run, mloc);
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c); // 0 on the first chunk (m_run = -inf), 1 while the maximum stands
-            m_run = m_new;
-            const float nmc = -(m_new * c);
+            const SoftmaxScale sc = online_softmax_scale(m_run, row_max<2>(s), c);
+            m_run = sc.m;
             V8 pf[4];
             float lc = 0.f;
 #pragma unroll
@@ -222,19 +196,16 @@ __global__ __launch_bounds__(XA_NW * 64, 2) void cross_attention_kernel(const XA
                 unsigned w[4];
 #pragma unroll
                 for (int i = 0; i < 4; i++) {
-                    const float e0 = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][r0 + 2 * i], c, nmc));
-                    const float e1 = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][r0 + 2 * i + 1], c, nmc));
-                    w[i] = xa_pack2<DT>(e0, e1);
-                    lc += xa_lo<DT>(w[i]);
-                    lc += xa_hi<DT>(w[i]);
+                    w[i] = prob_pair<DT>(s[kt][r0 + 2 * i], s[kt][r0 + 2 * i + 1], c, sc.nmc);
+                    lc = add_rounded<DT>(lc, w[i]);
                 }
                 pf[ks] = __builtin_bit_cast(V8, v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]});
             }
-            l = l * alpha + lc;
+            l = l * sc.alpha + lc;
             // ---- O^T = alpha O^T + V^T P^T ----
 #pragma unroll
             for (int dt = 0; dt < NDT; dt++) {
-                o[dt] = o[dt] * alpha;
+                o[dt] = o[dt] * sc.alpha;
 #pragma unroll
                 for (int ks = 0; ks < 4; ks++) {
                     const v4i vw = *(const lds_v4i *)(L8 + (va[dt] + (((8 * ch + 2 * ks + h) ^ vsw[dt]) << 4)));
@@ -243,8 +214,7 @@ __global__ __launch_bounds__(XA_NW * 64, 2) void cross_attention_kernel(const XA
             }
         }
         l += __shfl_xor(l, 32);
-        // ---- round16(o / l).  Lane (lr, h) holds channels 32 dt + 8 g + 4 h + e; a v_permlane32_swap per dword pair gives every lane 8 consecutive
-        //      channels 32 dt + 16 j2 + 8 h .. +7: 16-byte stores, cut at D (beyond it lies the next head, which another workgroup owns) ----
+        // ---- round16(o / l): 16-byte stores, cut at D (beyond it lies the next head, which another workgroup owns) ----
         const float inv = 1.0f / l;
         uint16_t *orow = p.out + (qbase + row) * p.ldo + (size_t)head * D + 8 * h;
 #pragma unroll
@@ -252,19 +222,8 @@ __global__ __launch_bounds__(XA_NW * 64, 2) void cross_attention_kernel(const XA
 #pragma unroll
             for (int j2 = 0; j2 < 2; j2++) {
                 if (32 * dt + 16 * j2 >= D) continue; // (compile time: no lane of this pair has a channel)
-                unsigned x[2], y[2];
-#pragma unroll
-                for (int d2 = 0; d2 < 2; d2++) {
-                    float t[4];
-#pragma unroll
-                    for (int i = 0; i < 4; i++) t[i] = o[dt][8 * j2 + 4 * (i >> 1) + 2 * d2 + (i & 1)] * inv;
-                    x[d2] = xa_pack2<DT>(t[0], t[1]);
-                    y[d2] = xa_pack2<DT>(t[2], t[3]);
-                    const auto sw = __builtin_amdgcn_permlane32_swap(x[d2], y[d2], false, false);
-                    x[d2] = sw[0];
-                    y[d2] = sw[1];
-                }
-                if (live && 32 * dt + 16 * j2 + 8 * h < D) *reinterpret_cast<v4i *>(orow + 32 * dt + 16 * j2) = v4i{(int)x[0], (int)x[1], (int)y[0], (int)y[1]};
+                const v4i w = o_tile_piece<DT>(o[dt], j2, inv);
+                if (live && 32 * dt + 16 * j2 + 8 * h < D) *reinterpret_cast<v4i *>(orow + 32 * dt + 16 * j2) = w;
             }
     }
 }
@@ -272,16 +231,9 @@ __global__ __launch_bounds__(XA_NW * 64, 2) void cross_attention_kernel(const XA
 template <int DT, int D> static hipError_t launch_xa(const XAttnParams &p, dim3 grid, hipStream_t st) {
     const int bytes = xa_lds_bytes(D, p.kcap);
     if (bytes > 64 * 1024) { // beyond the default limit of dynamic LDS: raised once per device and instantiation, to what XA_MAX_KEYS needs
-        static std::atomic<unsigned long long> raised{0}; // (callers may launch from several threads)
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
+        static std::atomic<unsigned long long> raised{0};
+        const hipError_t e = raise_dynamic_lds(reinterpret_cast<const void *>(&cross_attention_kernel<DT, D>), xa_lds_bytes(D, XA_MAX_KEYS), raised);
         if (e != hipSuccess) return e;
-        if (dev >= 64 || !(raised.load() >> dev & 1)) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(&cross_attention_kernel<DT, D>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    xa_lds_bytes(D, XA_MAX_KEYS));
-            if (e != hipSuccess) return e;
-            if (dev < 64) raised.fetch_or(1ull << dev);
-        }
     }
     hipLaunchKernelGGL((cross_attention_kernel<DT, D>), grid, dim3(XA_NW * 64), bytes, st, p);
     return hipSuccess;

@@ -8,9 +8,10 @@
 // for the whole life of a workgroup; a workgroup (8 waves) belongs to one head and walks 256-row query tiles of it, a wave owning 32 rows.
 // All scores of a row are live at once (NKT = ceil(N / 32) accumulator tiles of the 32x32x16 MFMA): plain max / exp2 / sum, no online
 // softmax, no rescaling of O.  P is rounded to 16 bits before the PV MFMA and the row sum is taken over the ROUNDED probabilities, the
-// normalisation follows the MFMA (attention.hip's conventions: a row dominated by one key returns that key's V row exactly).
+// normalisation follows the MFMA (the softmax contract stated in attn_frag.h, without the running state).
 //
-// Fragments (the S^T = K Q^T / O^T = V^T P^T formulation of attention.hip, whose operand layouts are the verified ones):
+// Fragments (the S^T = K Q^T / O^T = V^T P^T formulation of attention.hip, whose operand layouts are the verified ones; the code that
+// depends on them alone is in attn_frag.h, shared with cross_attention.hip and attention_d64.hip):
 //   * S^T[key][q]: A = K rows from LDS (lane: key = 32 kt + lr, d = 16 ds + 8 h .. +7), B = Q from registers (lane: q = lr, same d).
 //     The accumulator gives lane (lr, h) the scores of query lr for the keys  32 kt + 8 (r / 4) + 4 h + r % 4.
 //   * O^T[d][q]: B = P^T straight from those accumulator registers: the 8 registers r0 .. r0+7 (r0 = 8 (ks & 1)) of tile kt = ks / 2 are the
@@ -25,6 +26,7 @@
 //   * rows at or beyond T: the loads are clamped to row T - 1, the stores are skipped.
 // No atomics, no workspace; every output element is produced by one lane in a fixed order: two launches are bit-equal.
 #include "svdq_common.h"
+#include "attn_frag.h"
 
 namespace svdq {
 
@@ -43,17 +45,6 @@ constexpr int IPA_ROWS = IPA_NW * 32; // query rows per tile
 
 constexpr int ipa_pow2_pieces(int nkt) { return nkt <= 1 ? 4 : nkt <= 2 ? 8 : nkt <= 4 ? 16 : 32; } // 16-byte pieces per V^T row (a power of two)
 constexpr int ipa_lds_bytes(int nkt) { return nkt * 32 * 256 + 128 * ipa_pow2_pieces(nkt) * 16; }
-
-template <int DT> __device__ __forceinline__ unsigned ipa_pack2(float a, float b) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    if constexpr (DT == SVDQ_BF16) return __builtin_bit_cast(unsigned, __builtin_convertvector((f2){a, b}, b2));
-    else return __builtin_bit_cast(unsigned, __builtin_convertvector((f2){a, b}, h2));
-}
-// the two 16-bit values of a dword, as floats
-template <int DT> __device__ __forceinline__ float ipa_lo(unsigned pk) { return h2f(hfrom<typename Half<DT>::T>((unsigned short)(pk & 0xffffu))); }
-template <int DT> __device__ __forceinline__ float ipa_hi(unsigned pk) { return h2f(hfrom<typename Half<DT>::T>((unsigned short)(pk >> 16))); }
 
 template <int DT, int NKT>
 __global__ __launch_bounds__(IPA_NW * 64, NKT <= 4 ? 4 : 2) void ip_attention_kernel(const IpAttnParams p) {
@@ -102,12 +93,7 @@ __global__ __launch_bounds__(IPA_NW * 64, NKT <= 4 ? 4 : 2) void ip_attention_ke
             }
 #pragma unroll
             for (int e = 0; e < 8; e++) { // channel 8 cb + e: the e-th 16-bit value of every key row
-                v4i col;
-#pragma unroll
-                for (int w = 0; w < 4; w++) {
-                    const unsigned a = (unsigned)rows[2 * w][e >> 1], b = (unsigned)rows[2 * w + 1][e >> 1];
-                    col[w] = (int)((e & 1) ? ((a >> 16) | (b & 0xffff0000u)) : ((a & 0xffffu) | (b << 16)));
-                }
+                const v4i col = transpose8x8_piece(rows, e);
                 const int d = 8 * cb + e;
                 *(lds_v4i *)(L8 + (KBYTES + d * RB + ((j ^ ((d >> SW_SHIFT) & SW_MASK)) << 4))) = col;
             }
@@ -149,18 +135,10 @@ __global__ __launch_bounds__(IPA_NW * 64, NKT <= 4 ? 4 : 2) void ip_attention_ke
         // ---- keys at or beyond N (only the last tile can hold any) ----
         if (N < NKT * 32) {
 #pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int key = 32 * (NKT - 1) + 8 * (r >> 2) + 4 * h + (r & 3);
-                s[NKT - 1][r] = key < N ? s[NKT - 1][r] : -INFINITY;
-            }
+            for (int r = 0; r < 16; r++) s[NKT - 1][r] = 32 * (NKT - 1) + score_key(r, h) < N ? s[NKT - 1][r] : -INFINITY;
         }
         // ---- softmax in one pass: lane holds half of the scores of query row lr, lane ^ 32 the other half ----
-        float m = s[0][0];
-#pragma unroll
-        for (int kt = 0; kt < NKT; kt++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) m = fmaxf(m, s[kt][r]);
-        m = fmaxf(m, __shfl_xor(m, 32));
+        const float m = row_max<NKT>(s);
         const float nmc = -(m * c);
         V8 pf[2 * NKT];
         float l = 0.f;
@@ -170,11 +148,8 @@ __global__ __launch_bounds__(IPA_NW * 64, NKT <= 4 ? 4 : 2) void ip_attention_ke
             unsigned w[4];
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const float e0 = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][r0 + 2 * i], c, nmc));
-                const float e1 = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][r0 + 2 * i + 1], c, nmc));
-                w[i] = ipa_pack2<DT>(e0, e1);
-                l += ipa_lo<DT>(w[i]);
-                l += ipa_hi<DT>(w[i]);
+                w[i] = prob_pair<DT>(s[kt][r0 + 2 * i], s[kt][r0 + 2 * i + 1], c, nmc);
+                l = add_rounded<DT>(l, w[i]);
             }
             pf[ks] = __builtin_bit_cast(V8, v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]});
         }
@@ -194,7 +169,8 @@ __global__ __launch_bounds__(IPA_NW * 64, NKT <= 4 ? 4 : 2) void ip_attention_ke
         // ---- round16(out_scale * round16(o / l)): both products are formed in fp32 and then rounded (the reference multiplies a 16-bit tensor by
         //      a Python float: an fp32 product, rounded once); the empty asm statements keep the fp16 build from folding product and conversion
         //      into one mixed-precision FMA, which would round the exact product instead.  Lane (lr, h) holds channels 32 dt + 8 g + 4 h + e;
-        //      a v_permlane32_swap per dword pair gives every lane 8 consecutive channels: 16-byte stores ----
+        //      a v_permlane32_swap per dword pair gives every lane 8 consecutive channels: 16-byte stores (attn_frag.h's o_tile_piece with the
+        //      second rounding inside; its own copy: see there) ----
         const float inv = 1.0f / l;
         uint16_t *orow = p.out + (size_t)row * p.ldo + (size_t)head * 128 + 8 * h;
 #pragma unroll
@@ -213,8 +189,8 @@ __global__ __launch_bounds__(IPA_NW * 64, NKT <= 4 ? 4 : 2) void ip_attention_ke
                         asm volatile("" : "+v"(u));
                         t[i] = u;
                     }
-                    x[d2] = ipa_pack2<DT>(t[0], t[1]);
-                    y[d2] = ipa_pack2<DT>(t[2], t[3]);
+                    x[d2] = pack2<DT>(t[0], t[1]);
+                    y[d2] = pack2<DT>(t[2], t[3]);
                     const auto sw = __builtin_amdgcn_permlane32_swap(x[d2], y[d2], false, false);
                     x[d2] = sw[0];
                     y[d2] = sw[1];
@@ -226,16 +202,10 @@ __global__ __launch_bounds__(IPA_NW * 64, NKT <= 4 ? 4 : 2) void ip_attention_ke
 
 template <int DT, int NKT> static hipError_t launch_ip_nkt(const IpAttnParams &p, dim3 grid, hipStream_t st) {
     constexpr int bytes = ipa_lds_bytes(NKT);
-    if (bytes > 64 * 1024) { // beyond the default limit of dynamic LDS: raised once per device and instantiation (setting it twice is harmless)
-        static unsigned long long raised = 0;
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
+    if (bytes > 64 * 1024) { // beyond the default limit of dynamic LDS: raised once per device and instantiation
+        static std::atomic<unsigned long long> raised{0};
+        const hipError_t e = raise_dynamic_lds(reinterpret_cast<const void *>(&ip_attention_kernel<DT, NKT>), bytes, raised);
         if (e != hipSuccess) return e;
-        if (dev >= 64 || !(raised >> dev & 1)) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ip_attention_kernel<DT, NKT>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            if (e != hipSuccess) return e;
-            if (dev < 64) raised |= 1ull << dev;
-        }
     }
     hipLaunchKernelGGL((ip_attention_kernel<DT, NKT>), grid, dim3(IPA_NW * 64), bytes, st, p);
     return hipSuccess;

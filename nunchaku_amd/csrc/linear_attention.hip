@@ -26,6 +26,7 @@
 // No atomics: every partial and every sum is produced by one thread in a fixed order, two launches are bit-equal.  At most three launches
 // (two when only vk is asked for), no allocation, no synchronisation.
 #include "svdq_common.h"
+#include "attn_frag.h"
 
 namespace svdq {
 
@@ -52,15 +53,6 @@ __device__ __forceinline__ int la_relu2(int x) {
     const unsigned m = ((unsigned)x >> 15) & 0x00010001u;
     return x & ~(int)((m << 16) - m);
 }
-template <int DT> __device__ __forceinline__ unsigned la_pack2(float a, float b) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    if constexpr (DT == SVDQ_BF16) return __builtin_bit_cast(unsigned, __builtin_convertvector((f2){a, b}, b2));
-    else return __builtin_bit_cast(unsigned, __builtin_convertvector((f2){a, b}, h2));
-}
-template <int DT> __device__ __forceinline__ float la_lo(unsigned pk) { return h2f(hfrom<typename Half<DT>::T>((unsigned short)(pk & 0xffffu))); }
-template <int DT> __device__ __forceinline__ float la_hi(unsigned pk) { return h2f(hfrom<typename Half<DT>::T>((unsigned short)(pk >> 16))); }
 
 template <int DT>
 __global__ __launch_bounds__(256) void la_reduce_kernel(const LaParams p) {
@@ -166,8 +158,8 @@ __global__ __launch_bounds__(256) void la_apply_kernel(const LaParams p) {
             const v4i w = *reinterpret_cast<const v4i *>(mine + 16 * k);
 #pragma unroll
             for (int d = 0; d < 4; d++) {
-                qf[8 * k + 2 * d] = fmaxf(la_lo<DT>((unsigned)w[d]), 0.f);
-                qf[8 * k + 2 * d + 1] = fmaxf(la_hi<DT>((unsigned)w[d]), 0.f);
+                qf[8 * k + 2 * d] = fmaxf(pk_lo<DT>((unsigned)w[d]), 0.f);
+                qf[8 * k + 2 * d + 1] = fmaxf(pk_hi<DT>((unsigned)w[d]), 0.f);
             }
         }
         f32x2_t acc[17]; // (i = 2 n, 2 n + 1); acc[16] = (the denominator's sum, padding)
@@ -190,7 +182,7 @@ __global__ __launch_bounds__(256) void la_apply_kernel(const LaParams p) {
         for (int k = 0; k < 4; k++) {
             v4i w;
 #pragma unroll
-            for (int d = 0; d < 4; d++) w[d] = (int)la_pack2<DT>(acc[4 * k + d][0] * inv, acc[4 * k + d][1] * inv);
+            for (int d = 0; d < 4; d++) w[d] = (int)pack2<DT>(acc[4 * k + d][0] * inv, acc[4 * k + d][1] * inv);
             *reinterpret_cast<v4i *>(mine + 16 * k) = w; // over the thread's own Q row
         }
     }

@@ -1,9 +1,10 @@
 """The generated kernel sources in the tree are what their generators emit, and the attention iteration plan is complete.
 
-CPU-only: no GPU, no compiler.  (tools/gen_gemm_loop2.py -> gemm_loop2.inc, gemm_loop2_w4.inc: the GEMM main loops, and
-tools/gen_gemm_loop3.py -> gemm_loop3.inc, gemm_epi3.inc: loop and plain epilogue of the 128 x 64 wave tile kernel, each one file for
-bf16 and fp16 through the token splices of tools/asm_tokens.py;
-tools/gen_attn_loop.py -> attention_loop64_{bf16,fp16}.inc: the tile loop of the 4 x 64 attention kernel with its slot placement.)"""
+CPU-only: no GPU, no compiler.  (tools/gen_gemm_loop2.py -> gemm_loop2.inc, gemm_loop2_w4.inc: the GEMM main loops,
+tools/gen_gemm_loop3.py -> gemm_loop3.inc, gemm_epi3.inc: loop and plain epilogue of the 128 x 64 wave tile kernel, and
+tools/gen_attn_loop.py -> attention_loop64.inc: the tile loop of the 4 x 64 attention kernel with its slot placement; each one file for
+bf16 and fp16 through the token splices of tools/asm_tokens.py.  The attention plan and hazard walks read the committed file, expanded
+with each dtype's tokens: the text they reason about is the text the compiler gets.)"""
 import os
 import re
 import sys
@@ -113,21 +114,34 @@ def test_a_declared_fp16_only_line_is_a_comment_for_bf16(tmp_path):
 def test_attention_loops_in_tree_match_their_generator(tmp_path):
     import gen_attn_loop as GA
 
-    for dt in ("bf16", "fp16"):
-        out = tmp_path / f"attention_loop64_{dt}.inc"
-        GA.emit(str(out), dt)
-        assert out.read_text() == open(os.path.join(CSRC, out.name)).read(), f"{out.name} is stale: run python tools/gen_attn_loop.py"
+    out = tmp_path / "attention_loop64.inc"
+    GA.emit(str(out))
+    assert out.read_text() == open(os.path.join(CSRC, out.name)).read(), f"{out.name} is stale: run python tools/gen_attn_loop.py"
+
+
+def _attention_loop_in_tree(dt):
+    """the asm lines the compiler gets for dtype `dt` from the committed attention_loop64.inc; they are the generator's for that dtype"""
+    import asm_tokens
+    import gen_attn_loop as GA
+
+    lines = asm_tokens.expand(open(os.path.join(CSRC, "attention_loop64.inc")).read().splitlines(), dt)
+    assert lines == GA.build(dt)[0], dt
+    return lines
 
 
 def test_attention_loop_plan_is_complete_and_ordered():
     """Every operation of an iteration exactly once; a fragment is read before the MFMA that consumes it and its ring register is not
     re-read into while it is still needed; a P fragment is finished before its first PV MFMA; the row maxima of S'(j+1) come behind
     its last MFMA with the 11 wait states of the MFMA -> VALU hazard to spare; the counted LDS waits are right; the assembly text
-    only touches the registers of the documented plan."""
+    only touches the registers of the documented plan; the packed conversions, the v_dot2c row sums and their packed 1.0 are the dtype's."""
+    import asm_tokens
     import gen_attn_loop as GA
 
-    for kw in ({}, {"lead": 2}, {"lead": 6, "budget": 6}, {"dma0": 9, "rm_from": 40}):
-        lines, bodies = GA.build("bf16", **kw)
+    # the product options: the committed file; the other placements: the generator's lines -- each for both dtypes
+    for dt, kw in ((dt, kw) for dt in asm_tokens.DTYPES for kw in ({}, {"lead": 2}, {"lead": 6, "budget": 6}, {"dma0": 9, "rm_from": 40})):
+        lines, bodies = GA.build(dt, **kw)
+        if not kw:
+            lines = _attention_loop_in_tree(dt)
         for body in bodies:
             plan = body.plan
             seq = []  # program order: (slot, op)
@@ -187,6 +201,10 @@ def test_attention_loop_plan_is_complete_and_ordered():
         assert max(vregs) <= 255
         aregs = {r for a, b in re.findall(r"a\[(\d+):(\d+)\]", text) for r in range(int(a), int(b) + 1)} | {int(x) for x in re.findall(r"\ba(\d+)\b", text)}
         assert max(aregs) <= 191
+        ops = [ln.split()[0] for ln in lines if ln and not ln.startswith((";", "."))]
+        for name, n in (("MFMA_K16", 2 * 64), ("CVT_PK", 2 * 32), ("DOT2C", 2 * 32)):   # per body: 32 QK + 32 PV; 8 fragments x 4 dwords; each dword summed once
+            assert ops.count(asm_tokens.tok(dt, name)) == n, (name, dt, kw)
+        assert sum(ln.startswith(asm_tokens.tok(dt, "DOT2C") + " ") and f", {asm_tokens.tok(dt, 'ONE_PK')}, " in ln for ln in lines) == 2 * 32
 
 
 def _regs(tok):
@@ -209,111 +227,102 @@ def test_attention_loop_hazards_are_covered_by_construction():
     between an M0 write and the LDS-DMA that uses it; >= 1 between a v_exp_f32 and the instruction that reads its result; an MFMA result in
     VGPRs is not read by a VALU instruction before 12 wait states or two further MFMAs have passed; an AGPR tile an MFMA wrote is not
     read by v_accvgpr_read before 18 wait states; every ds_read result is covered by a counted s_waitcnt before its first reader."""
-    import gen_attn_loop as GA
-
     for dt in ("bf16", "fp16"):
-        lines, _ = GA.build(dt)
-        last_valu, last_exp, last_mfma_v, last_mfma_a, last_m0 = {}, {}, {}, {}, None  # register -> (wait-state clock, mfma count) of its last writer
-        pending_ds = {}  # VGPR -> index of the ds_read that will write it (cleared by a wait that covers it)
-        ds_order = []
-        clock, mfmas = 0, 0
-        for ln in lines:
-            if not ln or ln.startswith((";", ".")) or ln.endswith(":"):
-                continue
-            op, _, rest = ln.partition(" ")
-            toks = [t.strip() for t in rest.split(",")] if rest else []
-            if op == "s_nop":
-                clock += int(toks[0]) + 1
-                continue
-            if op == "s_waitcnt":
-                m = re.search(r"lgkmcnt\((\d+)\)", rest)
-                if m:
-                    keep = int(m.group(1))
-                    done = ds_order[: len(ds_order) - keep] if keep else ds_order[:]
-                    for regs in done:
-                        for r in regs:
-                            pending_ds.pop(r, None)
-                    ds_order = ds_order[len(ds_order) - keep:] if keep else []
-                clock += 1
-                continue
-            if op.startswith("s_") and op not in ("s_add_u32", "s_mov_b32"):
-                clock += 1
-                if op in ("s_barrier", "s_branch") or op.startswith("s_cbranch"):
-                    clock += 4
-                continue
-            dst = _regs(toks[0]) if toks else []
-            srcs = [r for t in toks[1:] for r in _regs(t.split(" ")[0])]
-            if op.startswith("v_permlane32_swap"):
-                srcs = srcs + dst  # reads and writes both operands
-            if op in ("v_fmac_f32",) or op.startswith("v_dot2c") or op.startswith("v_mfma") and False:
-                srcs = srcs + dst
-            # ---- checks on the readers
-            for r in srcs:
-                assert r not in pending_ds, f"{ln}: reads {r} before the ds_read that loads it is waited for"
-            if op.startswith("v_permlane32_swap"):
-                for r in srcs:
-                    if r in last_valu:
-                        assert clock - last_valu[r] >= 2, f"{ln}: {r} written {clock - last_valu[r]} wait states earlier"
-            if op.startswith("global_load_lds"):
-                assert last_m0 is not None and clock - last_m0 >= 1, ln
-            is_mfma = op.startswith("v_mfma")
-            is_valu = op.startswith("v_") and not is_mfma
-            if is_valu:
-                for r in srcs:
-                    if r in last_exp:
-                        assert clock - last_exp[r] >= 1, f"{ln}: reads the v_exp result {r} in the next issue slot"
-                    if r[0] == "v" and r in last_mfma_v:
-                        c0, m0_ = last_mfma_v[r]
-                        assert clock - c0 >= 12 or mfmas - m0_ >= 2, f"{ln}: reads the MFMA result {r} too early"
-            if op == "v_accvgpr_read_b32":
-                for r in srcs:
-                    if r in last_mfma_a:
-                        assert clock - last_mfma_a[r][0] >= 18 or mfmas - last_mfma_a[r][1] >= 3, f"{ln}: reads {r} too early behind the MFMA that wrote it"
-            # ---- bookkeeping on the writers
+        _walk_attention_loop_hazards(_attention_loop_in_tree(dt))
+
+
+def _walk_attention_loop_hazards(lines):
+    last_valu, last_exp, last_mfma_v, last_mfma_a, last_m0 = {}, {}, {}, {}, None  # register -> (wait-state clock, mfma count) of its last writer
+    pending_ds = {}  # VGPR -> index of the ds_read that will write it (cleared by a wait that covers it)
+    ds_order = []
+    clock, mfmas = 0, 0
+    for ln in lines:
+        if not ln or ln.startswith((";", ".")) or ln.endswith(":"):
+            continue
+        op, _, rest = ln.partition(" ")
+        toks = [t.strip() for t in rest.split(",")] if rest else []
+        if op == "s_nop":
+            clock += int(toks[0]) + 1
+            continue
+        if op == "s_waitcnt":
+            m = re.search(r"lgkmcnt\((\d+)\)", rest)
+            if m:
+                keep = int(m.group(1))
+                done = ds_order[: len(ds_order) - keep] if keep else ds_order[:]
+                for regs in done:
+                    for r in regs:
+                        pending_ds.pop(r, None)
+                ds_order = ds_order[len(ds_order) - keep:] if keep else []
             clock += 1
-            if op == "s_add_u32" and toks and toks[0] == "m0":
-                last_m0 = clock
-                continue
-            if op.startswith("ds_read"):
-                ds_order.append(dst)
+            continue
+        if op.startswith("s_") and op not in ("s_add_u32", "s_mov_b32"):
+            clock += 1
+            if op in ("s_barrier", "s_branch") or op.startswith("s_cbranch"):
+                clock += 4
+            continue
+        dst = _regs(toks[0]) if toks else []
+        srcs = [r for t in toks[1:] for r in _regs(t.split(" ")[0])]
+        if op.startswith("v_permlane32_swap"):
+            srcs = srcs + dst  # reads and writes both operands
+        if op in ("v_fmac_f32",) or op.startswith("v_dot2c") or op.startswith("v_mfma") and False:
+            srcs = srcs + dst
+        # ---- checks on the readers
+        for r in srcs:
+            assert r not in pending_ds, f"{ln}: reads {r} before the ds_read that loads it is waited for"
+        if op.startswith("v_permlane32_swap"):
+            for r in srcs:
+                if r in last_valu:
+                    assert clock - last_valu[r] >= 2, f"{ln}: {r} written {clock - last_valu[r]} wait states earlier"
+        if op.startswith("global_load_lds"):
+            assert last_m0 is not None and clock - last_m0 >= 1, ln
+        is_mfma = op.startswith("v_mfma")
+        is_valu = op.startswith("v_") and not is_mfma
+        if is_valu:
+            for r in srcs:
+                if r in last_exp:
+                    assert clock - last_exp[r] >= 1, f"{ln}: reads the v_exp result {r} in the next issue slot"
+                if r[0] == "v" and r in last_mfma_v:
+                    c0, m0_ = last_mfma_v[r]
+                    assert clock - c0 >= 12 or mfmas - m0_ >= 2, f"{ln}: reads the MFMA result {r} too early"
+        if op == "v_accvgpr_read_b32":
+            for r in srcs:
+                if r in last_mfma_a:
+                    assert clock - last_mfma_a[r][0] >= 18 or mfmas - last_mfma_a[r][1] >= 3, f"{ln}: reads {r} too early behind the MFMA that wrote it"
+        # ---- bookkeeping on the writers
+        clock += 1
+        if op == "s_add_u32" and toks and toks[0] == "m0":
+            last_m0 = clock
+            continue
+        if op.startswith("ds_read"):
+            ds_order.append(dst)
+            for r in dst:
+                pending_ds[r] = True
+            continue
+        if is_mfma:
+            mfmas += 1
+            for r in dst:
+                (last_mfma_v if r[0] == "v" else last_mfma_a)[r] = (clock, mfmas)
+                last_valu.pop(r, None)
+            continue
+        if is_valu:
+            for r in dst + (srcs if op.startswith("v_permlane32_swap") else []):
+                last_valu[r] = clock
+                last_exp.pop(r, None)
+                last_mfma_v.pop(r, None)
+            if op.startswith("v_exp_f32"):
                 for r in dst:
-                    pending_ds[r] = True
-                continue
-            if is_mfma:
-                mfmas += 1
-                for r in dst:
-                    (last_mfma_v if r[0] == "v" else last_mfma_a)[r] = (clock, mfmas)
-                    last_valu.pop(r, None)
-                continue
-            if is_valu:
-                for r in dst + (srcs if op.startswith("v_permlane32_swap") else []):
-                    last_valu[r] = clock
-                    last_exp.pop(r, None)
-                    last_mfma_v.pop(r, None)
-                if op.startswith("v_exp_f32"):
-                    for r in dst:
-                        last_exp[r] = clock
+                    last_exp[r] = clock
 
 
 def test_the_hazard_walk_notices_missing_wait_states():
-    """The checker above is not vacuous: strip the generator's own wait states / counted waits and it objects."""
-    import gen_attn_loop as GA
-
-    orig = GA.build
-    try:
+    """The checker above is not vacuous: strip the loop's own wait states / counted waits and it objects, for either dtype."""
+    for dt in ("bf16", "fp16"):
         for strip in ("s_nop 1", "s_nop 0", "s_waitcnt lgkmcnt(1)"):
-            def stripped(dt, _strip=strip, **kw):
-                lines, bodies = orig(dt, **kw)
-                return [ln for ln in lines if ln != _strip], bodies
-
-            GA.build = stripped
             try:
-                test_attention_loop_hazards_are_covered_by_construction()
+                _walk_attention_loop_hazards([ln for ln in _attention_loop_in_tree(dt) if ln != strip])
             except AssertionError:
                 continue
-            raise AssertionError(f"removing every '{strip}' went unnoticed")
-    finally:
-        GA.build = orig
+            raise AssertionError(f"removing every '{strip}' from the {dt} loop went unnoticed")
 
 
 def test_gemm_loop_lds_dma_discipline():

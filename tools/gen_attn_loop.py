@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """The tile loop of the 4-wave x 64-row attention kernel (attention.hip, geometry 2) as assembly with explicit registers.
 
-    python tools/gen_attn_loop.py        # writes nunchaku_amd/csrc/attention_loop64_{bf16,fp16}.inc
+    python tools/gen_attn_loop.py        # writes nunchaku_amd/csrc/attention_loop64.inc
+
+The file serves bf16 and fp16: the dtype-dependent mnemonics and constants (MFMA, packed conversion, v_dot2c and its packed 1.0) are
+macro splices (tools/asm_tokens.py).
 
 Why assembly (profiles/r3_attention_geometry2.txt): one wave per SIMD owns the whole 512-register file and nothing
 but its own instruction stream fills the shadow of an MFMA.  The C++ version of this loop (slots separated by sched_barrier) runs
@@ -30,6 +33,8 @@ Register plan (the C++ side pins its asm operands to the same registers, attenti
   s47 j_end     s48 bytes between two K tiles     s49..s67 scratch (s[64:65] / s[66:67]: sources of the DMA pieces)
 """
 import os
+
+import asm_tokens
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ATT_TILE = 16384
@@ -70,7 +75,7 @@ class Body:
 
     def __init__(self, dt, buf, tag, lead=4, budget=5.0, rm_from=36, dma0=1, drop=0):
         self.dt, self.buf, self.tag = dt, buf, tag
-        self.mfma = "v_mfma_f32_32x32x16_bf16" if dt == "bf16" else "v_mfma_f32_32x32x16_f16"
+        self.mfma = asm_tokens.tok(dt, "MFMA_K16")
         self.lines = []
         self.reads = []      # fragment ids in issue order
         self.lead, self.budget, self.rm_from, self.dma0 = lead, budget, rm_from, dma0
@@ -116,7 +121,7 @@ class Body:
         bank = ETMP
         dst = PF(rt, ks) + (d if d < 2 else 2 + (d - 2))
         src = bank + (2 * d if d < 2 else 4 + 2 * (d - 2))
-        self.e(f"{'v_cvt_pk_bf16_f32' if self.dt == 'bf16' else 'v_cvt_pk_f16_f32'} {vr(dst)}, {vr(src)}, {vr(src + 1)}")
+        self.e(f"{asm_tokens.tok(self.dt, 'CVT_PK')} {vr(dst)}, {vr(src)}, {vr(src + 1)}")
 
     def op_swap(self, rt, ks, d2):
         # hazard: a VALU write of either operand needs 2 wait states before v_permlane32_swap reads it
@@ -124,8 +129,7 @@ class Body:
         self.e(f"v_permlane32_swap_b32 {vr(PF(rt, ks) + d2)}, {vr(PF(rt, ks) + 2 + d2)}")
 
     def op_dot8(self, ks):
-        one = "0x3f803f80" if self.dt == "bf16" else "0x3c003c00"
-        dot = "v_dot2c_f32_bf16" if self.dt == "bf16" else "v_dot2c_f32_f16"
+        one, dot = asm_tokens.tok(self.dt, "ONE_PK"), asm_tokens.tok(self.dt, "DOT2C")
         for rt in range(2):
             for w, acc in ((0, L2 + 2 * rt), (1, L2 + 2 * rt + 1), (2, L2 + 2 * rt), (3, L2 + 2 * rt + 1)):
                 self.e(f"{dot} {vr(acc)}, {one}, {vr(PF(rt, ks) + w)}")
@@ -323,17 +327,10 @@ def build(dt, **kw):
     return out, (b0, b1)
 
 
-def emit(path, dt, **kw):
-    lines, _ = build(dt, **kw)
-    with open(path, "w") as f:
-        f.write("// GENERATED by tools/gen_attn_loop.py -- do not edit.\n")
-        for ln in lines:
-            f.write('"' + ln + '\\n"\n')
-    return len(lines)
+def emit(path, **kw):
+    return asm_tokens.write_neutral(path, "tools/gen_attn_loop.py", {dt: build(dt, **kw)[0] for dt in asm_tokens.DTYPES})
 
 
 if __name__ == "__main__":
-    csrc = os.path.join(ROOT, "nunchaku_amd", "csrc")
-    n = emit(os.path.join(csrc, "attention_loop64_bf16.inc"), "bf16")
-    emit(os.path.join(csrc, "attention_loop64_fp16.inc"), "fp16")
-    print(f"wrote attention_loop64_{{bf16,fp16}}.inc ({n} lines each)")
+    n = emit(os.path.join(ROOT, "nunchaku_amd", "csrc", "attention_loop64.inc"))
+    print(f"wrote attention_loop64.inc ({n} lines)")

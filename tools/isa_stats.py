@@ -7,6 +7,11 @@ bound of what one tile executes) and, inside that, of the address range that hol
 per-epilogue budgets so that an edit that fattens an epilogue is caught on CPU.
 
     python tools/isa_stats.py [path/to/libsvdq_amd.so]
+    python tools/isa_stats.py [path/to/libsvdq_amd.so] --diff OTHER.so [name-substring ...]
+
+--diff: for a change that intends none in the code the GPU runs.  Every kernel whose name contains one of the substrings (all kernels without one) is
+compared between the two libraries: its instruction lines (without the address / encoding / branch-target comment, so code that merely moved compares
+equal) and its resource record (kernel_resources()).  Prints "identical" or the first differing line per kernel; exit status 1 on any difference.
 """
 import collections
 import os
@@ -116,7 +121,31 @@ def gemm_stats(funcs):
     return out
 
 
+def diff(lib, other, patterns):
+    """number of kernels that differ between the two libraries (or exist in one only), each reported on one line"""
+    code = [{k: [ln.split("//")[0].rstrip() for ln in v] for k, v in disassemble(x).items()} for x in (lib, other)]
+    res = [kernel_resources(x, "") for x in (lib, other)]
+    bad = 0
+    for name in sorted(n for n in set(res[0]) | set(res[1]) if any(p in n for p in patterns or [""])):
+        a, b = ((c.get(name), r.get(name)) for c, r in zip(code, res))
+        if a == b:
+            print(f"identical ({len(a[0])} instructions)  {name}")
+            continue
+        bad += 1
+        if a[0] is None or b[0] is None:
+            print(f"ONLY IN {lib if b[0] is None else other}  {name}")
+        elif a[0] != b[0]:
+            k = next((i for i, (x, y) in enumerate(zip(a[0], b[0])) if x != y), min(len(a[0]), len(b[0])))
+            print(f"DIFFERS at instruction {k}: {a[0][k:k + 1]} / {b[0][k:k + 1]}  {name}")
+        else:
+            print(f"DIFFERS in resources: {a[1]} / {b[1]}  {name}")
+    return bad
+
+
 def main():
+    if "--diff" in sys.argv:
+        k = sys.argv.index("--diff")
+        sys.exit(1 if diff(sys.argv[1] if k > 1 else os.path.join(ROOT, "nunchaku_amd", "csrc", "libsvdq_amd.so"), sys.argv[k + 1], sys.argv[k + 2:]) else 0)
     lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "nunchaku_amd", "csrc", "libsvdq_amd.so")
     st = gemm_stats(disassemble(lib))
     for (dt, fuse, nw, laq, carry), r in sorted(st.items()):
