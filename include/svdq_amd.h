@@ -808,6 +808,49 @@ typedef struct svdq_qk_norm_rope_args {
 int svdq_qk_norm_rope(const svdq_qk_norm_rope_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Folded identity cross-attention (PuLID for FLUX; added WITHOUT a version bump: one new symbol and a new args struct, nothing existing
+ * changes, so SVDQ_ABI_VERSION stays 24.  reference: PerceiverAttentionCA, nunchaku/models/pulid/encoders_transformer.py:62-128 -- two
+ * LayerNorms, to_q, to_kv, a 16-bit softmax and to_out in torch ops, called from FluxModel.cpp's residual_callback).  K and V depend on the
+ * identity embeddings only, so to_q and to_out are folded into them once per embeddings tensor (nunchaku_amd/models/pulid.py): an attention
+ * whose H heads share one query, the hidden row itself, over J = H * 32 folded keys a_fold and values b_fold, summed over the heads.
+ * Per row t < T, head h < H, key n < N of the head (column j = 32 h + n; columns with n >= N take no part) and channel c < C:
+ *   acc[t, j] = sum_c x[t, c] * a_fold[j, c]                         fp32, on the 16-bit matrix core, in a fixed order
+ *   s[t, j]   = rstd_t * (acc[t, j] - mean_t * colsum[j]) + cbias[j]  (mean_t, rstd_t) = stats[t]; one fp32 rounding per operation
+ *   P[t, j]   = round16( e_j / sum_n e_n ),  e_j = exp(s[t, j] - max_n s[t, n])    over the head's N keys, fp32; P = +0 for n >= N
+ *   o[t, c]   = sum_j P[t, j] * b_fold[j, c]                         fp32, on the 16-bit matrix core
+ *   out[t, c] = round16( out_scale * round16(o[t, c]) )              svdq_ip_attention's output rule: out_scale multiplies in fp32
+ * This is the reference's softmax(weight.float()).type(dtype) with the LayerNorm of the query inside the score epilogue.  exp is formed from
+ * plain fp32 operations (range reduction by ln 2 in two pieces, a degree-7 polynomial; exp of less than -80 is +0) and the sum runs in a fixed
+ * order (nunchaku_amd/csrc/pulid_ca.hip), so the two epilogues can be restated bit for bit from acc and o (tests/pulid_ref.py).
+ * probs [T, H * 32] is a 16-bit workspace that receives P (contents are a result: callers may read it).  acc / o_acc (optional, fp32,
+ * contiguous [T, H * 32] / [T, C]) receive the two accumulators as the epilogues saw them.  Two kernel launches, no atomics, no allocation, no
+ * synchronisation: the call can be captured, two calls are bit-identical, and a row's result depends on neither T nor the row's position.
+ * Rows of a_fold / b_fold with n >= N, rows of x / stats at or beyond T and columns at or beyond C are never read; nothing is written
+ * outside out[:T, :C], probs, acc and o_acc.
+ * Validation (no launch), SVDQ_E_INVALID: NULL args or a missing pointer, T / C / H / N < 1, a row stride below C or not a multiple of 8,
+ * pointers not 16-byte aligned (stats: 8-byte), unknown dtype, an out_scale that is not finite, more tiles than the grid holds.
+ * SVDQ_E_UNSUPPORTED: C not a multiple of 128, H not a multiple of 4, H * 32 > 512, N > 32.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct svdq_pulid_ca_args {
+    const void *x;       /* [T, C] 16-bit, row stride ldx */
+    const float *stats;  /* [T, 2] fp32: (mean, rstd) of every row of x, eps = 1e-5 */
+    const void *a_fold;  /* [H * 32, C] 16-bit, contiguous: key-major folded keys */
+    const float *colsum; /* [H * 32] fp32: the sum over c of the 16-bit a_fold[j, c] */
+    const float *cbias;  /* [H * 32] fp32 */
+    const void *b_fold;  /* [H * 32, C] 16-bit, contiguous: folded values */
+    void *probs;         /* [T, H * 32] 16-bit, contiguous: workspace, receives P */
+    void *out;           /* [T, C] 16-bit, row stride ldo */
+    float *acc;          /* [T, H * 32] fp32 or NULL */
+    float *o_acc;        /* [T, C] fp32 or NULL */
+    int32_t ldx, ldo;    /* in elements */
+    int32_t T, C, H, N;
+    int32_t dtype;
+    float out_scale;     /* fp32 */
+} svdq_pulid_ca_args;
+
+int svdq_pulid_ca(const svdq_pulid_ca_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * AWQ W4A16 GEMV (reference: ops.gemv_awq, nunchaku/csrc/ops.h:123-145 -> src/kernels/awq/gemv_awq.cu:100-286;
  * module nunchaku/models/linear.py:277-414).  The AdaLayerNormZero modulation projections of every block.
  *   out[m, n] = round16( sum_k round16( round16(q[n,k]*scales[k/64,n] + zeros[k/64,n]) * x[m,k] ) ) (+ bias[n])

@@ -1027,6 +1027,44 @@ class _Ops:
         _lib.check(lib.svdq_ip_attention(C.byref(a), _stream()), "ip_attention")
 
     @staticmethod
+    def pulid_ca(x, stats, a_fold, colsum, cbias, b_fold, probs, out, n_tokens, out_scale=1.0, acc=None, o_acc=None):
+        """Extension (PuLID): the folded identity cross-attention (``svdq_pulid_ca``):
+        ``out = round16(out_scale * round16(sum_h softmax_n(rstd (x . a_fold - mean colsum) + cbias) . b_fold))``.
+        ``x`` / ``out``: ``[T, C]`` row views with any row stride; ``stats``: float32 ``[T, 2]`` (mean, rstd); ``a_fold`` / ``b_fold``:
+        contiguous ``[H * 32, C]``; ``colsum`` / ``cbias``: float32 ``[H * 32]``; ``probs``: contiguous 16-bit ``[T, H * 32]`` (receives the
+        probabilities); ``n_tokens``: identity tokens per head, 1 .. 32.  ``acc`` / ``o_acc``: optional contiguous float32
+        ``[T, H * 32]`` / ``[T, C]``, receive the two accumulators."""
+        lib = _lib.load()
+        for name, t in (("x", x), ("out", out)):
+            if t is None or t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"pulid_ca: {name} must be a [T, C] view with unit column stride")
+        T, Cw = x.shape
+        if a_fold is None or a_fold.dim() != 2 or a_fold.shape[1] != Cw or a_fold.shape[0] % 32 or not a_fold.is_contiguous():
+            raise ValueError("pulid_ca: a_fold must be a contiguous [H * 32, C] tensor")
+        J = a_fold.shape[0]
+        if b_fold is None or tuple(b_fold.shape) != (J, Cw) or not b_fold.is_contiguous() or tuple(out.shape) != (T, Cw):
+            raise ValueError("pulid_ca: expected x / out [T, C] and contiguous a_fold / b_fold [H * 32, C]")
+        if x.dtype not in _DT or any(t.dtype != x.dtype for t in (a_fold, b_fold, probs, out)):
+            raise ValueError("pulid_ca: x, a_fold, b_fold, probs and out must share one 16-bit dtype")
+        if tuple(probs.shape) != (T, J) or not probs.is_contiguous():
+            raise ValueError("pulid_ca: probs must be a contiguous [T, H * 32] tensor")
+        for name, t, shape in (("stats", stats, (T, 2)), ("colsum", colsum, (J,)), ("cbias", cbias, (J,)), ("acc", acc, (T, J)), ("o_acc", o_acc, (T, Cw))):
+            if t is None and name in ("acc", "o_acc"):
+                continue
+            if t is None or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"pulid_ca: {name} must be a contiguous float32 tensor of shape {list(shape)}")
+        for t in (x, stats, a_fold, colsum, cbias, b_fold, probs, out, acc, o_acc):
+            if t is not None and not t.is_cuda:
+                raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
+        a = _lib.PulidCaArgs()
+        a.x, a.stats, a.a_fold, a.colsum, a.cbias = x.data_ptr(), stats.data_ptr(), a_fold.data_ptr(), colsum.data_ptr(), cbias.data_ptr()
+        a.b_fold, a.probs, a.out = b_fold.data_ptr(), probs.data_ptr(), out.data_ptr()
+        a.acc, a.o_acc = (None if acc is None else acc.data_ptr()), (None if o_acc is None else o_acc.data_ptr())
+        a.ldx, a.ldo = (x.stride(0), out.stride(0)) if T > 1 else (Cw, Cw)  # (the stride of a one-row view means nothing)
+        a.T, a.C, a.H, a.N, a.dtype, a.out_scale = T, Cw, J // 32, int(n_tokens), _DT[x.dtype], float(out_scale)
+        _lib.check(lib.svdq_pulid_ca(C.byref(a), _stream()), "pulid_ca")
+
+    @staticmethod
     def linear_attention(q, kv, out, vk=None, eps=1e-6):
         """Extension (SANA): ReLU linear attention per batch element and head, head_dim 32 (``svdq_linear_attention``):
         ``vk = [V | 1]^T relu(K)`` over the tokens in fp32, ``out = round16(relu(Q) vk[:32]^T / (relu(Q) . vk[32] + eps))``.

@@ -209,6 +209,16 @@ class QkNormRopeArgs(C.Structure):
     ]
 
 
+class PulidCaArgs(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("stats", C.c_void_p), ("a_fold", C.c_void_p), ("colsum", C.c_void_p), ("cbias", C.c_void_p),
+        ("b_fold", C.c_void_p), ("probs", C.c_void_p), ("out", C.c_void_p), ("acc", C.c_void_p), ("o_acc", C.c_void_p),
+        ("ldx", C.c_int32), ("ldo", C.c_int32),
+        ("T", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("N", C.c_int32),
+        ("dtype", C.c_int32), ("out_scale", C.c_float),
+    ]
+
+
 EXPORTS = {
     "svdq_quantize_w4a4_act_fuse_lora": (C.c_int, [C.POINTER(QuantizeArgs), C.c_void_p]),
     "svdq_gemm_w4a4": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
@@ -230,6 +240,7 @@ EXPORTS = {
     "svdq_attention_d64": (C.c_int, [C.POINTER(AttentionD64Args), C.c_void_p]),
     "svdq_sandwich_norm": (C.c_int, [C.POINTER(SandwichNormArgs), C.c_void_p]),
     "svdq_qk_norm_rope": (C.c_int, [C.POINTER(QkNormRopeArgs), C.c_void_p]),
+    "svdq_pulid_ca": (C.c_int, [C.POINTER(PulidCaArgs), C.c_void_p]),
     "svdq_gemm_workspace_bytes": (C.c_int64, []),
     "svdq_gemm_workspace_bytes_for": (C.c_int64, [C.POINTER(GemmArgs)]),
     "svdq_gemm_workspace_status": (C.c_int, [C.c_void_p, C.c_void_p]),

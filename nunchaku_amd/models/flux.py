@@ -431,7 +431,7 @@ class FluxEngineMixin:
 
     def engine_forward(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids,
                        guidance=None, controlnet_block_samples=None, controlnet_single_block_samples=None, controlnet_blocks_repeat=False,
-                       *, ip_hidden_states=None):
+                       *, ip_hidden_states=None, id_embeddings=None, id_weight=1.0):
         """hidden_states [1, T_img, 64]; encoder_hidden_states [1, T_txt, 4096]; pooled [1, 768];
         timestep/guidance [1]; img_ids [T_img, 3]; txt_ids [T_txt, 3]  ->  [1, T_img, 64]
         (transformer_flux_v2.py:430-561; batch 1 -- the fused QKV epilogue takes one rotary table).
@@ -441,8 +441,13 @@ class FluxEngineMixin:
         ``ip_hidden_states``: the image embeddings of an attached IP-Adapter (``models/ip_adapter.py``) -- a tensor whose last axis is the
         adapter's ``cross_dim`` and whose other axes are all image-prompt tokens, or the pipeline's list (element 0); None: the stored
         ``image_embeds``.  Ignored without an adapter; an adapter without any embeddings raises ``ValueError``.
+        ``id_embeddings`` / ``id_weight``: PuLID (``models/pulid.py``; needs ``attach_pulid``) -- the identity embeddings ``[1, N, kv_dim]``
+        (N <= 32 on the fused arm) and the strength, a Python float: behind every second joint and every fourth single block the image
+        stream gets ``id_weight * pulid_ca[k](id_embeddings, hidden)``.  Batch 1 only; refused with a cache active or an offloaded model.
         The step is its stages run back to back (``_prologue``, ``_run_joint``, ``_join``, ``_run_single``, ``_tail``);
         :meth:`engine_forward_cached` is the same stages with the First-Block-Cache decision in between."""
+        if id_embeddings is not None:
+            self._pulid_check(hidden_states)
         if hidden_states.shape[0] > 1:
             # The fused QKV epilogue takes ONE rotary table and the operand buffers of a launch belong to one sample
             # (reference: rotary_emb.shape[0] * shape[1] == M assert, launch_impl.cuh:353; SURVEY.md section 8e): a batch
@@ -460,7 +465,8 @@ class FluxEngineMixin:
                                            ip_hidden_states=per_ip(i))
                               for i in range(hidden_states.shape[0])], dim=0)
         st = self._prologue(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance,
-                            controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat, ip_hidden_states=ip_hidden_states)
+                            controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat, ip_hidden_states=ip_hidden_states,
+                            id_embeddings=id_embeddings, id_weight=id_weight)
         # every modulation projection depends on the timestep embedding only: one batched GEMV launch for the whole step
         self._launch_mods(st, range(len(self.blocks)), range(len(self.single_blocks)))
         self._run_joint(st, 0, len(self.blocks))
@@ -470,7 +476,7 @@ class FluxEngineMixin:
 
     def _prologue(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance=None,
                   controlnet_block_samples=None, controlnet_single_block_samples=None, controlnet_blocks_repeat=False, *,
-                  ip_hidden_states=None) -> "_Step":
+                  ip_hidden_states=None, id_embeddings=None, id_weight=1.0) -> "_Step":
         """Embedders, rotary tables, padding of the two streams and their first LayerNorm statistics; with an IP-Adapter attached, the
         image-prompt K / V of every joint block (projected once per embeddings tensor: ``IPAdapter.kv``)."""
         dt = self.dtype_
@@ -527,6 +533,7 @@ class FluxEngineMixin:
         st.cn_joint, st.cn_single, st.cn_repeat = controlnet_block_samples, controlnet_single_block_samples, controlnet_blocks_repeat
         st.fused = self.fused_norm and hidden.shape[0] == 1
         st.ip = None if adapter is None else (ip_kv, adapter.ip_adapter_scale)
+        st.pulid = None if id_embeddings is None else (self.pulid_ca, id_embeddings, float(id_weight), self.pulid_fused and st.fused)
         st.stats = ((residual_gate_stats(hidden)[1], None), (residual_gate_stats(enc)[1], None)) if st.fused else None
         return st
 
@@ -556,6 +563,8 @@ class FluxEngineMixin:
                 st.hidden, h_stats = blocks.add_control(st.hidden, st.cn_joint, i, nj, st.cn_repeat, want_stats=st.fused)
                 if st.fused:
                     st.stats = ((h_stats, st.stats[0][1]), st.stats[1])
+            if st.pulid is not None and i % 2 == 0:
+                self._pulid_add(st, i // 2)
             if st.ip is not None:
                 self._ip_add(st, i, ip_q)
 
@@ -604,6 +613,56 @@ class FluxEngineMixin:
         if st.fused:  # (fused blocks around a torch-op adapter step: attention impl "sdpa" or a head dim other than 128)
             st.stats = ((residual_gate_stats(st.hidden)[1], st.stats[0][1]), st.stats[1])
 
+    # True: the PuLID step runs the folded kernel (svdq_pulid_ca) and one residual pass; False: the reference's torch-op sequence
+    pulid_fused = True
+
+    def _pulid_check(self, hidden_states) -> None:
+        """the refusals of a step with ``id_embeddings`` (before anything is launched)"""
+        from ..caching import teacache
+
+        if getattr(self, "pulid_ca", None) is None or len(self.pulid_ca) == 0:
+            raise ValueError("id_embeddings were passed but no PuLID modules are attached: call models.pulid.attach_pulid(transformer, source) first")
+        if hidden_states.shape[0] != 1:
+            raise ValueError(f"PuLID supports batch 1 only (got {hidden_states.shape[0]}): run the samples one by one")
+        if getattr(self, "_is_cached", False) and getattr(self, "residual_diff_threshold_multi", -1.0) >= 0.0:
+            raise NotImplementedError("PuLID with First-Block Cache active is not supported: a skipped block's identity residual would be "
+                                      "dropped (switch the cache off: residual_diff_threshold_multi < 0)")
+        if any(hasattr(self, name) for name in teacache.STATE):
+            raise NotImplementedError("PuLID inside a TeaCache context is not supported")
+        if getattr(self, "offload", False):
+            raise NotImplementedError("PuLID does not support an offloaded model")
+        want = (len(self.blocks) + 1) // 2 + (len(self.single_blocks) + 3) // 4
+        if len(self.pulid_ca) != want:
+            raise ValueError(f"{len(self.pulid_ca)} PuLID modules are attached, the transformer needs {want}")
+
+    def _pulid_add(self, st: "_Step", k: int) -> None:
+        """``image rows += id_weight * pulid_ca[k](id_embeddings, image rows)`` (reference: FluxModel.cpp ``residual_callback``, behind the
+        ControlNet add).  Fused arm: ``svdq_pulid_ca`` on the un-normalised rows (its own eps = 1e-5 statistics: one stats-only pass), then
+        ONE ``svdq_residual_gate_stats`` pass that adds the result in place and renews the statistics the next block's quantisers read --
+        in the joined stream the image rows' slice of them, as ``add_control`` does there.  Padded image rows take part like any row."""
+        mods, emb, weight, fused = st.pulid
+        t_pad = st.p_txt if st.joined else 0
+        img = st.hidden[:, t_pad:]
+        if fused:
+            o = mods[k].forward_fused(emb, img, out_scale=weight)
+            _, h_stats = residual_gate_stats(img, o)
+            if st.joined:
+                st.stats[0][t_pad:] = h_stats
+            else:
+                st.stats = ((h_stats, st.stats[0][1]), st.stats[1])
+            return
+        new = img + weight * mods[k](emb if emb.dim() == 3 else emb[None], img)
+        if st.joined:
+            st.hidden = torch.cat([st.hidden[:, :t_pad], new], dim=1)
+        else:
+            st.hidden = new
+        if st.fused:  # (fused blocks around a torch-op PuLID step)
+            h_stats = residual_gate_stats(new)[1]
+            if st.joined:
+                st.stats[0][t_pad:] = h_stats
+            else:
+                st.stats = ((h_stats, st.stats[0][1]), st.stats[1])
+
     def _join(self, st: "_Step") -> None:
         """[text | image] for the single blocks; the statistics in the same row order."""
         st.hidden = torch.cat([st.enc, st.hidden], dim=1)
@@ -620,6 +679,8 @@ class FluxEngineMixin:
                 _, i_stats = blocks.add_control(st.hidden[:, t_pad:], st.cn_single, i, ns, st.cn_repeat, want_stats=st.fused)
                 if st.fused:
                     st.stats[0][t_pad:] = i_stats
+            if st.pulid is not None and i % 4 == 0:
+                self._pulid_add(st, (len(self.blocks) + 1) // 2 + i // 4)
 
     def _tail(self, st: "_Step") -> torch.Tensor:
         """The real image rows through AdaLayerNormContinuous and the output projection."""
@@ -821,7 +882,7 @@ class _Step:
     ``[text | image]`` stream once ``joined``), the LayerNorm statistics that travel with them on the fused path, and the step's constants."""
 
     __slots__ = ("hidden", "enc", "stats", "temb_act", "rot", "kv_valid", "t_txt", "t_img", "p_txt", "fused", "mods", "joined",
-                 "cn_joint", "cn_single", "cn_repeat", "ip")
+                 "cn_joint", "cn_single", "cn_repeat", "ip", "pulid")
 
 
 class FluxTransformerAMD(nn.Module, FluxEngineMixin):

@@ -118,6 +118,30 @@ def ip_attention(qkv_or_q: torch.Tensor, k_ip: torch.Tensor, v_ip: torch.Tensor,
     return out
 
 
+def pulid_ca(x: torch.Tensor, fold, out_scale: float = 1.0, stats: torch.Tensor | None = None, out: torch.Tensor | None = None,
+             return_probs: bool = False, acc: torch.Tensor | None = None, o_acc: torch.Tensor | None = None):
+    """PuLID's identity cross-attention with ``to_q`` and ``to_out`` folded into the keys and values (``svdq_pulid_ca``):
+    ``round16(out_scale * round16(sum_h softmax(rstd (x . a_fold_h - mean colsum_h) + cbias_h) . b_fold_h))``.
+    ``x``: ``[T, C]`` or ``[1, T, C]`` with any row stride -- the UN-normalised image stream; ``fold``: the record of
+    ``models.pulid.PerceiverAttentionCA.fold`` (``a_fold``, ``b_fold`` ``[H * 32, C]``, ``colsum``, ``cbias`` ``[H * 32]`` float32, ``tokens``);
+    ``stats``: float32 ``[T, 2]`` (mean, rstd) of the rows of ``x`` for eps = 1e-5 -- None: one stats-only ``residual_gate_stats`` launch
+    computes them.  ``out_scale`` (``id_weight``, a Python float) multiplies in fp32.  Returns ``out`` in the shape of ``x``; with
+    ``return_probs`` also the 16-bit probabilities ``[T, H * 32]`` (the call's workspace).  ``acc`` / ``o_acc``: float32 ``[T, H * 32]`` /
+    ``[T, C]`` tensors that receive the two accumulators (tests)."""
+    x2 = x if x.dim() == 2 else x.reshape(-1, x.shape[-1])
+    T, C = x2.shape
+    if stats is None:
+        from .elementwise import residual_gate_stats
+
+        stats = residual_gate_stats(x2, eps=1e-5)[1]
+    if out is None:
+        out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    probs = torch.empty(T, fold.a_fold.shape[0], dtype=x.dtype, device=x.device)
+    ops.pulid_ca(x2, stats, fold.a_fold, fold.colsum, fold.cbias, fold.b_fold, probs, out if out.dim() == 2 else out.view(-1, C),
+                 fold.tokens, out_scale=out_scale, acc=acc, o_acc=o_acc)
+    return (out, probs) if return_probs else out
+
+
 def linear_attention(qkv: torch.Tensor, heads: int, out: torch.Tensor | None = None, tokens: int | None = None, return_vk: bool = False,
                      eps: float = 1e-6):
     """SANA's ReLU linear attention over the packed output of the QKV projection, read in place (no copies): per batch element and head
