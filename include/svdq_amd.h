@@ -275,6 +275,12 @@ int64_t svdq_gemm_workspace_bytes_for(const svdq_gemm_args *args);
 #define SVDQ_PLAN_SPLIT_DOWN 5
 #define SVDQ_PLAN_WAVE_TILE_128 6
 int svdq_gemm_last_plan(int32_t *out8);
+/* Host only, launches nothing (the GEMM's svdq_attention_plan): validates `args` exactly as svdq_gemm_w4a4 does (same return codes and messages), then writes the
+ * eight words svdq_gemm_last_plan would report after that launch on a device of `cus` compute units (1 .. 256; 0 = the current device's count, 256 where there
+ * is none).  Reads the shapes, ranks, fuse, geometry, lora_act_format, workspace_bytes and which pointers are NULL / 16-byte aligned; dereferences none of them.
+ * Launch and query run the same function (plan_gemm, csrc/gemm_w4a4.hip), so a test can pin the dispatch without a GPU (tests/test_gemm_plan.py).  One new
+ * symbol, nothing existing changes, so SVDQ_ABI_VERSION stays 24. */
+int svdq_gemm_plan(const svdq_gemm_args *args, int32_t cus, int32_t out8[8]);
 /* Synchronises `stream`, then returns SVDQ_E_HIP (and clears the flag) if a launch that used `workspace` timed out
  * waiting for partial tiles -- see svdq_gemm_args.workspace; SVDQ_OK otherwise.  Test / debugging aid. */
 int svdq_gemm_workspace_status(void *workspace, void *stream);

@@ -245,6 +245,7 @@ EXPORTS = {
     "svdq_gemm_workspace_bytes_for": (C.c_int64, [C.POINTER(GemmArgs)]),
     "svdq_gemm_workspace_status": (C.c_int, [C.c_void_p, C.c_void_p]),
     "svdq_gemm_last_plan": (C.c_int, [C.POINTER(C.c_int32)]),
+    "svdq_gemm_plan": (C.c_int, [C.POINTER(GemmArgs), C.c_int32, C.POINTER(C.c_int32)]),
     "svdq_attention_workspace_bytes": (C.c_int64, []),
     "svdq_attention_workspace_bytes_for": (C.c_int64, [C.POINTER(AttentionArgs)]),
     "svdq_attention_workspace_status": (C.c_int, [C.c_void_p, C.c_void_p]),

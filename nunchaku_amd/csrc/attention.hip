@@ -1102,10 +1102,8 @@ static int attention_cus() {
     }
     return cus;
 }
-static int attention_groups_for(int L, int H, int cus);
-// Persistent or plain grid?  Whole rounds of tasks need no split (and no partial traffic); otherwise deal the KV tiles of
+// Persistent or plain grid (a launch without a workspace: plain)?  Whole rounds of tasks need no split (and no partial traffic); otherwise deal the KV tiles of
 // all tasks evenly to min(CUs, tiles/2) workgroups, a multiple of 8 (XCD-aware numbering).  0 = plain grid.
-static int attention_groups(const AttnParams &p) { return p.ws_flags ? attention_groups_for(p.L, p.H, attention_cus()) : 0; }
 static int attention_groups_for(int L, int H, int cus) {
     if (L % 256) return 0;
     const long long tasks = (long long)H * (L / 256), half = tasks * (L / ATT_KB) / 2;
@@ -1120,18 +1118,21 @@ static int attention_groups_for(int L, int H, int cus) {
 using namespace svdq;
 
 // header + two slabs per workgroup of the persistent schedule: the one a contributor publishes, and (geometry 2) the stash an owner parks its own part in
-extern "C" int64_t svdq_attention_workspace_bytes(void) { return ATT_WS_HEADER + 2 * (int64_t)attention_cus() * ATT_SLAB_FLOATS * 4; }
+static int64_t attention_workspace_base(int cus) { return ATT_WS_HEADER + 2 * (int64_t)cus * ATT_SLAB_FLOATS * 4; }
+extern "C" int64_t svdq_attention_workspace_bytes(void) { return attention_workspace_base(attention_cus()); }
 // the fused quantiser's low-rank down projection can run split (lowrank_split.h): fp32 accumulators, rank 48 .. 160, K = H * 128 a multiple of 256
 static bool attention_split_shape_ok(const svdq_attention_args *a) {
     return a->qact && a->qlora_act && a->qlora_down && a->qlora_act_format == SVDQ_LORA_ACT_F32 && a->L > 0 && a->L % 256 == 0 && a->H > 0 &&
            lowrank_split_shape_ok(a->H * ATT_D, a->qR);
 }
+// ... and what it adds to the workspace: the packed down projection(s), then the 16-bit output image (0: no split for these arguments)
+static int64_t attention_split_bytes(const svdq_attention_args *a) {
+    return attention_split_shape_ok(a) ? lowrank_split_pack_bytes(a->H * ATT_D, a->qR, a->qsmooth2 != nullptr) + (int64_t)a->L * a->H * ATT_D * 2 : 0;
+}
 // ABI 20: the workspace size with which THIS launch takes every fast path: svdq_attention_workspace_bytes(), plus -- fused quantiser of rank 48 .. 160 -- the
 // packed down projection(s) and the 16-bit output image (L * H * 128 * 2 bytes) of the split low-rank down projection.  A smaller workspace is never an error.
 extern "C" int64_t svdq_attention_workspace_bytes_for(const svdq_attention_args *a) {
-    const int64_t base = svdq_attention_workspace_bytes();
-    if (!a || !attention_split_shape_ok(a)) return base;
-    return base + lowrank_split_pack_bytes(a->H * ATT_D, a->qR, a->qsmooth2 != nullptr) + (int64_t)a->L * a->H * ATT_D * 2;
+    return attention_workspace_base(attention_cus()) + (a ? attention_split_bytes(a) : 0);
 }
 
 extern "C" int svdq_attention_workspace_status(void *workspace, void *stream) {
@@ -1181,18 +1182,44 @@ extern "C" int svdq_attention_schedule(int32_t L, int32_t H, int32_t cus, int32_
     return n;
 }
 
+// What a launch takes -- the one place that decides it; svdq_attention, svdq_attention_plan and svdq_attention_last_plan read it.  Pure: `with_ws` = the caller's
+// workspace holds the persistent schedule's part (svdq_attention_workspace_bytes), `cus` = the compute units that schedule is sized for.
+struct AttnPlan {
+    int geometry, nw;  // workgroup geometry 1 (nw = 8 | 4 waves x 32 rows) | 2 (4 waves x 64 rows)
+    int groups;        // workgroups of the persistent schedule (0 = plain grid)
+    bool mask2;        // the key mask runs on geometry 2 ...
+    int j0, j1;        // ... whose assembly loop walks the main segment [j0, j1) of fully real 64-key tiles
+    bool split;        // the fused quantiser's low-rank down projection runs split (svdq_attention_workspace_bytes_for)
+};
+static AttnPlan attention_plan(const svdq_attention_args *a, bool with_ws, int cus) {
+    AttnPlan pl = {};
+    pl.nw = a->L % 256 == 0 ? 8 : 4;
+    // automatic: geometry 2 on the plain grid when Q comes prescaled, the length allows it and there is no key mask (the mask lives in
+    // geometry 1).  Same box, 24 heads x 4608 tokens: 216 us against 274 for geometry 1 on its better schedule; geometry 2's own
+    // persistent schedule 236.  With a raw Q geometry 2 has to scale the 16-bit values itself (a second rounding, ~2.5x the error against
+    // fp32): only on explicit request.  An explicit geometry takes the workspace if given.
+    // (round 4: a masked launch takes geometry 2 as well -- plain grid, the padded / odd tiles as C++ "extra" tiles behind the assembly loop,
+    //  attention_kernel64<.., MASK> -- when the same conditions hold and some run of fully real tiles has at least two)
+    pl.mask2 = attention_masked_geometry2(a, pl.j0, pl.j1);
+    pl.geometry = a->kv_len0 > 0 ? (pl.mask2 ? 2 : 1) : a->geometry ? a->geometry : (a->L % 256 == 0 && a->q_prescaled ? 2 : 1);
+    pl.groups = !with_ws || (pl.geometry == 2 && (a->geometry == 0 || pl.mask2)) ? 0 : attention_groups_for(a->L, a->H, cus);
+    // behind the persistent schedule's part of the workspace (ABI 20): the split low-rank down projection of the fused quantiser
+    const int64_t split_bytes = with_ws ? attention_split_bytes(a) : 0;
+    pl.split = split_bytes > 0 && a->workspace_bytes >= attention_workspace_base(cus) + split_bytes;
+    return pl;
+}
+
 // Which kernel a launch with these arguments would take (host only, nothing is launched): out[0] = workgroup geometry (1 / 2), out[1] = 1 when the
 // key mask runs on geometry 2, out[2], out[3] = the main segment [j0, j1) of fully real 64-key tiles its assembly loop walks (the other tiles that
 // hold a real key are C++ "extra" tiles).  Pointers are not looked at.
 extern "C" int svdq_attention_plan(const svdq_attention_args *a, int32_t *out) {
     if (!a || !out) { set_error("svdq_attention_plan: args and out are required"); return SVDQ_E_INVALID; }
     if (a->L <= 0 || a->L % 128) { set_error("svdq_attention_plan: L=%d must be a positive multiple of 128", a->L); return SVDQ_E_INVALID; }
-    int j0 = 0, j1 = 0;
-    const bool mask2 = attention_masked_geometry2(a, j0, j1);
-    out[0] = a->kv_len0 > 0 ? (mask2 ? 2 : 1) : a->geometry ? a->geometry : (a->L % 256 == 0 && a->q_prescaled ? 2 : 1);
-    out[1] = mask2 ? 1 : 0;
-    out[2] = j0;
-    out[3] = j1;
+    const AttnPlan pl = attention_plan(a, false, 0); // (the schedule and the split are not among the four words: no workspace, no device)
+    out[0] = pl.geometry;
+    out[1] = pl.mask2 ? 1 : 0;
+    out[2] = pl.j0;
+    out[3] = pl.j1;
     return SVDQ_OK;
 }
 
@@ -1262,52 +1289,35 @@ extern "C" int svdq_attention(const svdq_attention_args *a, void *stream) {
     p.qimg = qimage ? a->qlora_down_packed : nullptr; p.qimg2 = qimage && a->qsmooth2 ? a->qlora_down_packed2 : nullptr;
     p.zero_ptr = (v4i *)a->zero_ptr;
     p.zero_vec = a->zero_ptr ? a->zero_bytes / 16 : 0;
-    p.ws_flags = nullptr;
-    p.ws_slabs = nullptr;
-    p.qa16 = nullptr;
-    void *split_pack = nullptr;
     SVDQ_ATTN_PROBE_FILL(p);
-    if (a->workspace) {
-        if (((uintptr_t)a->workspace & 15) || a->workspace_bytes < 0) { set_error("svdq_attention: workspace must be 16-byte aligned"); return SVDQ_E_INVALID; }
-        if (a->workspace_bytes >= svdq_attention_workspace_bytes()) { // a smaller one is ignored (plain grid), as in svdq_gemm_w4a4
-            p.ws_flags = (int *)a->workspace;
-            p.ws_slabs = (float *)((uint8_t *)a->workspace + ATT_WS_HEADER);
-        }
-        // ... and behind the persistent schedule's part (ABI 20, svdq_attention_workspace_bytes_for): the split low-rank down projection of the fused quantiser
-        if (attention_split_shape_ok(a) && a->workspace_bytes >= svdq_attention_workspace_bytes_for(a)) {
-            split_pack = (uint8_t *)a->workspace + svdq_attention_workspace_bytes();
-            p.qa16 = (uint8_t *)split_pack + lowrank_split_pack_bytes(a->H * ATT_D, a->qR, a->qsmooth2 != nullptr);
-        }
-    }
+    if (a->workspace && (((uintptr_t)a->workspace & 15) || a->workspace_bytes < 0)) { set_error("svdq_attention: workspace must be 16-byte aligned"); return SVDQ_E_INVALID; }
     hipStream_t st = (hipStream_t)stream;
     if (a->reserved != 0) { set_error("svdq_attention: reserved must be 0 (timing ablations live in tools/ablate, not in this library)"); return SVDQ_E_INVALID; }
     if (a->geometry < 0 || a->geometry > 2 || (a->geometry == 2 && a->L % 256)) {
         set_error("svdq_attention: geometry=%d (0 = automatic, 1 = 8 waves x 32 rows, 2 = 4 waves x 64 rows: needs L %% 256 == 0)", a->geometry);
         return SVDQ_E_INVALID;
     }
-    const int nw = a->L % 256 == 0 ? 8 : 4;
-    // automatic: geometry 2 on the plain grid when Q comes prescaled, the length allows it and there is no key mask (the mask lives in
-    // geometry 1).  Same box, 24 heads x 4608 tokens: 216 us against 274 for geometry 1 on its better schedule; geometry 2's own
-    // persistent schedule 236.  With a raw Q geometry 2 has to scale the 16-bit values itself (a second rounding, ~2.5x the error against
-    // fp32): only on explicit request.  An explicit geometry takes the workspace if given.
-    // (round 4: a masked launch takes geometry 2 as well -- plain grid, the padded / odd tiles as C++ "extra" tiles behind the assembly loop,
-    //  attention_kernel64<.., MASK> -- when the same conditions hold and some run of fully real tiles has at least two)
-    const bool mask2 = attention_masked_geometry2(a, p.mask_j0, p.mask_j1);
-    const int geometry = a->kv_len0 > 0 ? (mask2 ? 2 : 1) : a->geometry ? a->geometry : (a->L % 256 == 0 && a->q_prescaled ? 2 : 1);
-    const int groups = geometry == 2 && (a->geometry == 0 || mask2) ? 0 : attention_groups(p);
-    g_attn_last_plan[0] = geometry; g_attn_last_plan[1] = groups; g_attn_last_plan[2] = mask2 ? 1 : 0; g_attn_last_plan[3] = p.qa16 ? 1 : 0;
+    const int cus = attention_cus();
+    const bool with_ws = a->workspace && a->workspace_bytes >= attention_workspace_base(cus); // a smaller one is ignored (plain grid), as in svdq_gemm_w4a4
+    const AttnPlan pl = attention_plan(a, with_ws, cus);
+    p.mask_j0 = pl.j0; p.mask_j1 = pl.j1;
+    p.ws_flags = with_ws ? (int *)a->workspace : nullptr;
+    p.ws_slabs = with_ws ? (float *)((uint8_t *)a->workspace + ATT_WS_HEADER) : nullptr;
+    void *split_pack = pl.split ? (uint8_t *)a->workspace + attention_workspace_base(cus) : nullptr;
+    p.qa16 = pl.split ? (uint8_t *)split_pack + lowrank_split_pack_bytes(a->H * ATT_D, a->qR, a->qsmooth2 != nullptr) : nullptr;
+    g_attn_last_plan[0] = pl.geometry; g_attn_last_plan[1] = pl.groups; g_attn_last_plan[2] = pl.mask2 ? 1 : 0; g_attn_last_plan[3] = pl.split ? 1 : 0;
     const int prof = prof_begin(2, 4.0 * a->L * (double)a->L * a->H * ATT_D, st);
     auto launch = [&]() {
-    if (geometry == 2 && a->L % 256 == 0) { if (a->dtype == SVDQ_FP16) launch_attention64<SVDQ_FP16>(p, groups, st); else launch_attention64<SVDQ_BF16>(p, groups, st); }
-    else if (groups > 0) { if (a->dtype == SVDQ_FP16) launch_attention_persistent<SVDQ_FP16>(p, groups, st); else launch_attention_persistent<SVDQ_BF16>(p, groups, st); }
-    else if (a->dtype == SVDQ_FP16) { if (nw == 8) launch_attention<SVDQ_FP16, 8>(p, st); else launch_attention<SVDQ_FP16, 4>(p, st); }
-    else if (nw == 8) launch_attention<SVDQ_BF16, 8>(p, st);
+    if (pl.geometry == 2 && a->L % 256 == 0) { if (a->dtype == SVDQ_FP16) launch_attention64<SVDQ_FP16>(p, pl.groups, st); else launch_attention64<SVDQ_BF16>(p, pl.groups, st); }
+    else if (pl.groups > 0) { if (a->dtype == SVDQ_FP16) launch_attention_persistent<SVDQ_FP16>(p, pl.groups, st); else launch_attention_persistent<SVDQ_BF16>(p, pl.groups, st); }
+    else if (a->dtype == SVDQ_FP16) { if (pl.nw == 8) launch_attention<SVDQ_FP16, 8>(p, st); else launch_attention<SVDQ_FP16, 4>(p, st); }
+    else if (pl.nw == 8) launch_attention<SVDQ_BF16, 8>(p, st);
     else launch_attention<SVDQ_BF16, 4>(p, st);
     };
-    if (p.qa16) { // pack the down projection(s), the attention kernel (its epilogue stores the 16-bit fragments), the contraction into qlora_act
+    if (pl.split) { // pack the down projection(s), the attention kernel (its epilogue stores the 16-bit fragments), the contraction into qlora_act
         const int split_row = a->qsmooth2 ? a->qsplit_rows : 0x7fffffff;
-        if (a->dtype == SVDQ_FP16) launch_lowrank_down_split<SVDQ_FP16>(p.qa16, a->qlora_down, a->qlora_down2, split_row, a->L, a->H * ATT_D, a->qR, (float *)a->qlora_act, split_pack, attention_cus(), st, launch, a->qlora_down_packed, a->qlora_down_packed2);
-        else launch_lowrank_down_split<SVDQ_BF16>(p.qa16, a->qlora_down, a->qlora_down2, split_row, a->L, a->H * ATT_D, a->qR, (float *)a->qlora_act, split_pack, attention_cus(), st, launch, a->qlora_down_packed, a->qlora_down_packed2);
+        if (a->dtype == SVDQ_FP16) launch_lowrank_down_split<SVDQ_FP16>(p.qa16, a->qlora_down, a->qlora_down2, split_row, a->L, a->H * ATT_D, a->qR, (float *)a->qlora_act, split_pack, cus, st, launch, a->qlora_down_packed, a->qlora_down_packed2);
+        else launch_lowrank_down_split<SVDQ_BF16>(p.qa16, a->qlora_down, a->qlora_down2, split_row, a->L, a->H * ATT_D, a->qR, (float *)a->qlora_act, split_pack, cus, st, launch, a->qlora_down_packed, a->qlora_down_packed2);
     } else launch();
     prof_end(prof, st);
     return hip_check(hipGetLastError(), "svdq_attention launch");

@@ -1691,17 +1691,35 @@ __global__ __launch_bounds__(256, 1) void gemm_w4a4_wt128_kernel(const GemmParam
 #undef SVDQ_EPI3_ACC_IO
 #undef SVDQ_EPI3_EP_IN
 
-// What the last svdq_gemm_w4a4 call of this thread launched (svdq_gemm_last_plan): tile rows (256 | 128), kernel variant, grid, stream-K groups, row-run length,
-// whether the low-rank operands were packed.  Filled by the dispatch code itself -- tests read it to assert that no rank, shape or format fell back to a slower
-// kernel than the one documented for it (include/svdq_amd.h).
+// ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+// Host side.  plan_gemm() is the ONE place that decides a launch: kernel, schedule, packed images, workspace layout (DESIGN.md "GEMM dispatch").  It is pure --
+// no HIP call, no state, no allocation -- so svdq_gemm_plan answers on a machine without a GPU what svdq_gemm_w4a4 would launch.  launch_gemm() issues what a
+// plan says and decides nothing; svdq_gemm_last_plan, svdq_gemm_workspace_bytes_for and the schedule replay read the same code.
+// ---------------------------------------------------------------------------------------------------------------------------------------------------------------
 enum { PLAN_PLAIN = 0, PLAN_CARRY = 1, PLAN_ALL_RANK = 2, PLAN_HYBRID_CARRY = 3, PLAN_SOLO_CARRY = 4, PLAN_SPLIT_DOWN = 5, PLAN_WAVE_TILE_128 = 6 };
-static thread_local int32_t g_last_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-static void record_plan(int tile_rows, int variant, int grid, const GemmParams &p) {
-    g_last_plan[0] = tile_rows; g_last_plan[1] = variant; g_last_plan[2] = grid; g_last_plan[3] = p.sk_gs; g_last_plan[4] = p.rowrun;
-    g_last_plan[5] = (p.la_packed != nullptr && (variant == PLAN_ALL_RANK || variant == PLAN_SOLO_CARRY || variant == PLAN_SPLIT_DOWN)) ? 1 : 0;
-    g_last_plan[6] = (p.lu_packed != nullptr && (variant == PLAN_SOLO_CARRY || (variant == PLAN_ALL_RANK && tile_rows == 128))) ? 1 : 0;
-    g_last_plan[7] = p.dynamic;
-}
+enum { FAMILY_WAVE_TILE, FAMILY_8WAVE, FAMILY_4WAVE }; // gemm_w4a4_wt128_kernel | gemm_w4a4_kernel on 256 x 128 tiles (NW = 8) | on 128 x 128 tiles (NW = 4)
+struct GemmPlan {
+    int dtype, fuse;                   // the caller's: with the family and the switches they name the instantiation
+    int family;
+    bool laq, carry, rall, hyb, split; // template switches of gemm_w4a4_kernel
+    int variant, tile_rows;            // PLAN_*; 256 | 128
+    int cus, tiles, slots;             // what the schedule is sized for (tiles, slots: SVDQ_PROBE_GRID's view of it)
+    int grid, sk_gs, rowrun, dynamic, stagger, solo_carry; // GemmParams' fields of these names
+    int stage_lora, stage_lu_all;      // low-rank staging in LDS (GemmParams)
+    bool la_packed, lu_packed;         // lora_act_in / lora_up run as packed fragment images ...
+    bool lu_pre;                       // ... lora_up's being the caller's (svdq_gemm_args.lora_up_packed): no pack launch
+    int split_R2;                      // the split low-rank down projection runs, with this next-layer rank (0 = no; the GEMM kernel then sees R2 = 0)
+    long long la_off, lu_off, act16_off; // workspace layout: byte offsets of the lora_act_in, lora_up and 16-bit output images (the split's packed
+                                       //  down projections share lora_up's tail: the all-rank kernel on 256 x 128 tiles stages lora_up in LDS)
+    // the pack launches that precede the kernel
+    bool pack_la() const { return la_packed; }
+    bool pack_lu() const { return lu_packed && !lu_pre; }
+    // svdq_gemm_last_plan's words (include/svdq_amd.h) -- tests read them to assert that no rank, shape or format fell back to a slower kernel than documented
+    void words(int32_t *out8) const {
+        out8[0] = tile_rows; out8[1] = variant; out8[2] = grid; out8[3] = sk_gs; out8[4] = rowrun; out8[5] = la_packed; out8[6] = lu_packed; out8[7] = dynamic;
+    }
+};
+static thread_local int32_t g_last_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // what this thread's last svdq_gemm_w4a4 launched: launch_gemm copies it from the plan it consumed
 
 // compute units the persistent grids are sized for (a multiple of 8: the XCD-aware numbering deals workgroups to the 8
 // XCDs; at most 256: the stream-K header holds 1023 arrival counters for up to 2 x 256 workgroups)
@@ -1717,9 +1735,9 @@ static int device_cus() {
     return cus;
 }
 // one size for both geometries: 2 slabs per workgroup slot, 256 x 128 tiles on `cus` slots == 128 x 128 tiles on 2 * cus
-static long long workspace_slab_bytes() { return SK_HEADER_BYTES + 2LL * device_cus() * 256 * BN * 4; }
+static long long workspace_slab_bytes(int cus) { return SK_HEADER_BYTES + 2LL * cus * 256 * BN * 4; }
 // ... + the packed lora_act_in image of the all-rank kernels (LA_PACK_BYTES) behind the slabs
-static long long workspace_bytes_needed() { return workspace_slab_bytes() + LA_PACK_BYTES + LU_PACK_BYTES; }
+static long long workspace_bytes_needed(int cus) { return workspace_slab_bytes(cus) + LA_PACK_BYTES + LU_PACK_BYTES; }
 // ... + (ABI 20) the 16-bit image of a GELU_QUANT launch's output for the split low-rank down projection, behind everything else: M_pad * N * 2 bytes.
 // What the arguments alone decide (the workspace size is checked by the caller): GELU_QUANT, fp32 accumulators, own rank on the all-rank path (48 .. 160,
 // 16-byte aligned operands, image within its tail), next rank 48 .. 160 whose packed down projection(s) fit the lora_up tail.
@@ -1730,7 +1748,11 @@ static bool split_down_shape_ok(const svdq_gemm_args *a) {
 }
 // the library's own choice (geometry 0): every next-layer rank beyond the carry's 32, from a full round of 256 x 128 tiles (same box, profiles/r5_split_down_ab.txt:
 // next rank 48: 271 -> 258 us, 64: 296 -> 256 us against the hybrid carry; 128: 354 -> 277 us against the solo carry, 443 with per-tile atomics)
-static bool split_down_auto(const svdq_gemm_args *a) { return a->R2 > 32 && (long long)(a->M_pad / 128) * (a->N / BN) >= 2LL * device_cus(); }
+static bool split_down_auto(const svdq_gemm_args *a, int cus) { return a->R2 > 32 && (long long)(a->M_pad / 128) * (a->N / BN) >= 2LL * cus; }
+// the launch wants the split (geometry 7 asks for it at any size and from next-layer rank 48: tests, A/B); it runs where the workspace also holds the image
+static bool split_down_wanted(const svdq_gemm_args *a, int cus) {
+    return split_down_shape_ok(a) && (a->geometry == 7 || (a->geometry == 0 && split_down_auto(a, cus)));
+}
 
 // Stream-K heuristic.  The remainder R = tiles % slots of the last round leaves CUs idle for a whole tile time;
 // splitting those tiles along K costs every split ~2 x 128 KiB of fp32 partial traffic plus a prologue
@@ -1761,186 +1783,239 @@ static int persistent_grid(int tiles, int sk_gs, int slots) {
     if (sk_gs > 0) return tiles < slots ? max(tiles, sk_gs) : slots;
     return whole_rounds_grid(tiles, slots);
 }
+// Row runs (GELU_QUANT on 256 x 128 tiles with a next-layer low-rank branch of rank <= 32 and no K split): worth it from two tiles per
+// workgroup (profiles/r4_gemm_rowrun.txt: the per-tile atomics of the low-rank down projection cost 12 % of the fc1 launch)
+static bool rowrun_applies(int M_pad, int N, int R2, int sk_gs, int slots) {
+    return R2 > 0 && sk_gs == 0 && (M_pad / 256) * (N / BN) >= 2 * slots; // (callers: R2 <= 32, or the hybrid carry kernel beyond)
+}
+// grid of the row-run schedule (GemmSchedule::init_runs) and its run length: one workgroup per run of `*rl` column tiles of a tile row; a multiple of 8: the
+// XCD-aware numbering keeps consecutive runs on one XCD
+static int rowrun_grid(int TM, int TN, int slots, int *rl) {
+    *rl = GemmSchedule::run_length(TM, TN, slots);
+    return (TM * ((TN + *rl - 1) / *rl) + 7) / 8 * 8;
+}
 
-// Geometry of a launch (svdq_gemm_args.geometry; 0 = this heuristic).
+// Geometry the library chooses itself (svdq_gemm_args.geometry 0, and the explicit geometries 6, 7, 8 where their kernel cannot serve the launch).
 // Measured rule (profiles/r3_gemm_geometry.txt): a tile costs the same CU-cycles in both geometries (the SIMDs are
 // throughput-bound in the loop AND in the epilogues: co-residency hides no work), so the 128 x 128 queue wins exactly where
 // the 256 x 128 schedule cannot use the chip evenly: whole rounds that leave >= 10 % of the CUs out (1296 tiles = 6 rounds
 // on 216 of 256 CUs), provided the queue has >= 2 tiles per workgroup to balance with.  Long K stays on geometry 1 (stream-K).
-static int pick_geometry(const svdq_gemm_args *a, bool with_ws) {
-    if (a->geometry != 0 && a->geometry != 8) return a->geometry; // (8: the 128 x 64 wave tile where it serves the launch, this rule otherwise)
+static int auto_geometry(const svdq_gemm_args *a, bool with_ws, int cus) {
     if (!with_ws) return 1;
     // rank 48 .. 160: both geometries have all-rank kernels (256 x 128: lora_up of a tile staged in LDS + packed lora_act_in; 128 x 128: both operands packed), so
     // the choice below is the rank-32 one -- except for a grouped launch from rank 96, whose second lora_up only the 256 x 128 kernel serves without the plain
     // kernels' row-per-lane loads (16-18 k cycles per 128 x 128 tile at rank 128, profiles/r5_gemm_phase_trace.txt)
     if (a->wgt2 && a->R >= 96 && a->R <= Geo<8>::STG_LU_ALL_MAX_R && a->lora_act_format == SVDQ_LORA_ACT_F32 && (long long)a->M_pad * a->R * 2 <= LA_PACK_BYTES) return 1;
-    const int cus = device_cus();
     const int tiles1 = (a->M_pad / 256) * (a->N / BN), tiles2 = 2 * tiles1;
     if (tiles1 <= cus || streamk_groups_for(tiles1, a->K / 128, cus) > 0) return 1;
     const int rounds1 = (tiles1 + cus - 1) / cus;
     const double use1 = (double)tiles1 / ((double)rounds1 * cus);
     return (use1 < 0.9 && tiles2 >= 4 * cus) ? 2 : 1;
 }
-
-// Row runs (GELU_QUANT on 256 x 128 tiles with a next-layer low-rank branch of rank <= 32 and no K split): worth it from two tiles per
-// workgroup (profiles/r4_gemm_rowrun.txt: the per-tile atomics of the low-rank down projection cost 12 % of the fc1 launch)
-static bool rowrun_applies(int M_pad, int N, int R2, int sk_gs, int slots) {
-    return R2 > 0 && sk_gs == 0 && (M_pad / 256) * (N / BN) >= 2 * slots; // (callers: R2 <= 32, or the hybrid carry kernel beyond)
-}
-
-template <int DT, int FUSE, int NW, bool LAQ>
-static void launch_one_laq(GemmParams &p, bool with_ws, hipStream_t st) {
-    using G_ = Geo<NW>;
-    const int tiles = (p.M_pad / G_::BM) * (p.N / BN), slots = device_cus() * G_::WG_PER_CU;
-    p.sk_gs = with_ws ? streamk_groups_for(tiles, p.K / 128, slots) : 0;
-    // dynamic tile queues (128 x 128 geometry): when every slot has more than one tile to do and the remainder is not
-    // better served by a K split (long K: few, long tiles -- a queue cannot balance 1.7 tiles per workgroup)
-    p.dynamic = NW == 4 && p.dynamic && with_ws && tiles > slots && p.sk_gs == 0;
-    int g = persistent_grid(tiles, p.sk_gs, slots);
-    if (p.dynamic) g = slots; // every CU hosts two workgroups; the queue balances them
-    p.rowrun = 0;
-    // the low-rank-down carry (and, from two tiles per workgroup, the row-run schedule that makes it pay): GELU_QUANT on 256 x 128 tiles with an fp32
-    // next-layer low-rank branch of rank <= 32
-    // ... next-layer ranks 48 .. 128: the carry lives behind the ring of ONE 128 x 128 workgroup per CU (svdq_gemm_w4a4 picks that geometry: solo_carry)
-    if constexpr (NW == 4 && FUSE == SVDQ_FUSE_GELU_QUANT && !LAQ) {
-        if (p.solo_carry) {
-            const int TM = p.M_pad / G_::BM, TN = p.N / BN, cus = device_cus();
-            p.sk_gs = 0; p.dynamic = 0; p.stagger = 0;
-            p.rowrun = GemmSchedule::run_length(TM, TN, cus);
-            const int g4 = (TM * ((TN + p.rowrun - 1) / p.rowrun) + 7) / 8 * 8;
-            dim3 grid(SVDQ_PROBE_GRID(g4, tiles, cus)), block(G_::THREADS);
-            if (p.lu_packed && p.la_packed) { // both low-rank operands as MFMA fragments (the grouped launch's second lora_up is not packed: see svdq_gemm_w4a4)
-                float16_scales sc;
-                for (int i = 0; i < MAX_LORA_TILES; i++) sc.v[i] = p.lora_scales[i];
-                const int units = p.R / 16;
-                hipLaunchKernelGGL((pack_lora_act_kernel<DT>), dim3(p.M_pad / 32, (units + 3) / 4), dim3(256), 0, st, (const float *)p.lora_act_in,
-                                   (typename Half<DT>::V8 *)p.la_packed, p.R, units, sc);
-                if (!p.lu_pre)
-                    hipLaunchKernelGGL((pack_lora_up_kernel<DT>), dim3(p.N / 32, (units + 3) / 4), dim3(256), 0, st, (const typename Half<DT>::T *)p.lora_up,
-                                       (typename Half<DT>::V8 *)p.lu_packed, p.R, units);
-            }
-            record_plan(G_::BM, PLAN_SOLO_CARRY, (int)grid.x, p);
-            hipLaunchKernelGGL((gemm_w4a4_kernel<DT, FUSE, NW, LAQ, true>), grid, block, 0, st, p);
-            return;
-        }
-    }
-    if constexpr (NW == 4 && !LAQ) {
-        if (p.lu_packed && p.la_packed) { // rank 48 .. 160 on 128 x 128 tiles: both low-rank operands packed, then the all-rank kernel of this geometry
-            float16_scales sc;
-            for (int i = 0; i < MAX_LORA_TILES; i++) sc.v[i] = p.lora_scales[i];
-            const int units = p.R / 16;
-            hipLaunchKernelGGL((pack_lora_act_kernel<DT>), dim3(p.M_pad / 32, (units + 3) / 4), dim3(256), 0, st, (const float *)p.lora_act_in,
-                               (typename Half<DT>::V8 *)p.la_packed, p.R, units, sc);
-            if (!p.lu_pre)
-                hipLaunchKernelGGL((pack_lora_up_kernel<DT>), dim3(p.N / 32, (units + 3) / 4), dim3(256), 0, st, (const typename Half<DT>::T *)p.lora_up,
-                                   (typename Half<DT>::V8 *)p.lu_packed, p.R, units);
-            dim3 grid(SVDQ_PROBE_GRID(g, tiles, slots)), block(G_::THREADS);
-            record_plan(G_::BM, PLAN_ALL_RANK, (int)grid.x, p);
-            hipLaunchKernelGGL((gemm_w4a4_kernel<DT, FUSE, NW, LAQ, false, true>), grid, block, 0, st, p);
-            return;
-        }
-    }
-    if constexpr (NW == 8 && FUSE == SVDQ_FUSE_GELU_QUANT && LAQ) {
-        // SVDQ_LORA_ACT_Q32_RUNS (ABI 22): the row-run schedule with its fp32 carry, the run's sum converted to fixed point at the flush -- no atomics in a tile
-        if (p.lora_fixed == SVDQ_LORA_ACT_Q32_RUNS && p.R2 > 0 && p.R2 <= 32 && rowrun_applies(p.M_pad, p.N, p.R2, p.sk_gs, slots)) {
-            const int TM = p.M_pad / G_::BM, TN = p.N / BN;
-            p.rowrun = GemmSchedule::run_length(TM, TN, slots);
-            g = (TM * ((TN + p.rowrun - 1) / p.rowrun) + 7) / 8 * 8;
-            dim3 grid(SVDQ_PROBE_GRID(g, tiles, slots)), block(G_::THREADS);
-            record_plan(G_::BM, PLAN_CARRY, (int)grid.x, p);
-            hipLaunchKernelGGL((gemm_w4a4_kernel<DT, FUSE, NW, LAQ, true>), grid, block, 0, st, p);
-            return;
-        }
-    }
-    constexpr bool CAN_CARRY = NW == 8 && FUSE == SVDQ_FUSE_GELU_QUANT && !LAQ;
-    if constexpr (CAN_CARRY) {
-        if (p.R2 > 32 && rowrun_applies(p.M_pad, p.N, p.R2, p.sk_gs, slots)) { // beyond rank 32 (and not the solo-carry kernel's case): the hybrid carry
-            const int TM = p.M_pad / G_::BM, TN = p.N / BN;
-            p.rowrun = GemmSchedule::run_length(TM, TN, slots);
-            g = (TM * ((TN + p.rowrun - 1) / p.rowrun) + 7) / 8 * 8;
-            dim3 grid(SVDQ_PROBE_GRID(g, tiles, slots)), block(G_::THREADS);
-            record_plan(G_::BM, PLAN_HYBRID_CARRY, (int)grid.x, p);
-            hipLaunchKernelGGL((gemm_w4a4_kernel<DT, FUSE, NW, LAQ, true, false, true>), grid, block, 0, st, p);
-            return;
-        }
-        if (p.R2 > 0 && p.R2 <= 32) {
-            if (rowrun_applies(p.M_pad, p.N, p.R2, p.sk_gs, slots)) {
-                const int TM = p.M_pad / G_::BM, TN = p.N / BN;
-                p.rowrun = GemmSchedule::run_length(TM, TN, slots);
-                g = (TM * ((TN + p.rowrun - 1) / p.rowrun) + 7) / 8 * 8; // a multiple of 8: the XCD-aware numbering keeps consecutive runs on one XCD
-            }
-            dim3 grid(SVDQ_PROBE_GRID(g, tiles, slots)), block(G_::THREADS);
-            record_plan(G_::BM, PLAN_CARRY, (int)grid.x, p);
-            hipLaunchKernelGGL((gemm_w4a4_kernel<DT, FUSE, NW, LAQ, true>), grid, block, 0, st, p);
-            return;
-        }
-    }
-    dim3 grid(SVDQ_PROBE_GRID(g, tiles, slots)), block(G_::THREADS);
-    if constexpr (NW == 8 && !LAQ) {
-        if (p.stage_lu_all && p.la_packed) { // 32 < rank <= 160: the kernel with the all-rank lora_up image, behind the pack of its low-rank activations
-            float16_scales sc;
-            for (int i = 0; i < MAX_LORA_TILES; i++) sc.v[i] = p.lora_scales[i];
-            const int units = p.R / 16;
-            hipLaunchKernelGGL((pack_lora_act_kernel<DT>), dim3(p.M_pad / 32, (units + 3) / 4), dim3(256), 0, st, (const float *)p.lora_act_in,
-                               (typename Half<DT>::V8 *)p.la_packed, p.R, units, sc);
-            if constexpr (FUSE == SVDQ_FUSE_GELU_QUANT) {
-                if (p.act16_packed) { // split low-rank down: pack the next layer's down projection(s), the GEMM with the fragment-storing epilogue, the contraction
-                    record_plan(G_::BM, PLAN_SPLIT_DOWN, (int)grid.x, p);
-                    launch_lowrank_down_split<DT>(p.act16_packed, p.next_lora_down, p.next_lora_down2, p.split_row, p.M_pad, p.N, p.split_R2, (float *)p.lora_act_out,
-                                                  p.workspace + workspace_slab_bytes() + LA_PACK_BYTES, device_cus(), st,
-                                                  [&]() { hipLaunchKernelGGL((gemm_w4a4_kernel<DT, FUSE, NW, LAQ, false, true, false, true>), grid, block, 0, st, p); },
-                                                  p.ld_pre, p.ld2_pre);
-                    return;
-                }
-            }
-            record_plan(G_::BM, PLAN_ALL_RANK, (int)grid.x, p);
-            hipLaunchKernelGGL((gemm_w4a4_kernel<DT, FUSE, NW, LAQ, false, true>), grid, block, 0, st, p);
-            return;
-        }
-    }
-    record_plan(G_::BM, PLAN_PLAIN, (int)grid.x, p);
-    hipLaunchKernelGGL((gemm_w4a4_kernel<DT, FUSE, NW, LAQ>), grid, block, 0, st, p);
-}
-template <int DT, int FUSE, int NW>
-static void launch_one(GemmParams &p, bool with_ws, hipStream_t st) {
-    if (p.lora_fixed) launch_one_laq<DT, FUSE, NW, true>(p, with_ws, st);
-    else launch_one_laq<DT, FUSE, NW, false>(p, with_ws, st);
-}
-// geometry 8: the 128 x 64 wave tile kernel (FUSE_NONE, rank <= 32, fp32 low-rank accumulators); schedule and stream-K split as the 256 x 128 geometry's
-template <int DT>
-static void launch_wt128(GemmParams &p, bool with_ws, hipStream_t st) {
-    const int tiles = (p.M_pad / 256) * (p.N / BN), slots = device_cus();
-    p.sk_gs = with_ws ? streamk_groups_for(tiles, p.K / 128, slots) : 0;
-    p.dynamic = 0; p.stagger = 0; p.rowrun = 0;
-    const int g = persistent_grid(tiles, p.sk_gs, slots);
-    dim3 grid(SVDQ_PROBE_GRID(g, tiles, slots)), block(256);
-    record_plan(256, PLAN_WAVE_TILE_128, (int)grid.x, p);
-    hipLaunchKernelGGL((gemm_w4a4_wt128_kernel<DT>), grid, block, 0, st, p);
-}
+// geometry 8's kernel: the 128 x 64 wave tile (FUSE_NONE, rank <= 32, fp32 low-rank accumulators); schedule and stream-K split as the 256 x 128 geometry's
 static bool wt128_serves(const svdq_gemm_args *a) { return a->fuse == SVDQ_FUSE_NONE && a->lora_act_format == SVDQ_LORA_ACT_F32 && (a->R == 32 || a->R == 0); }
 
-template <int DT, int NW>
-static void launch_fuse(GemmParams &p, int fuse, bool with_ws, hipStream_t st) {
-    switch (fuse) {
-    case SVDQ_FUSE_NONE: launch_one<DT, SVDQ_FUSE_NONE, NW>(p, with_ws, st); break;
-    case SVDQ_FUSE_SILU: launch_one<DT, SVDQ_FUSE_SILU, NW>(p, with_ws, st); break;
-    case SVDQ_FUSE_GELU_QUANT: launch_one<DT, SVDQ_FUSE_GELU_QUANT, NW>(p, with_ws, st); break;
-    case SVDQ_FUSE_RMSNORM_ROPE: launch_one<DT, SVDQ_FUSE_RMSNORM_ROPE, NW>(p, with_ws, st); break;
+// The plan of a launch whose arguments passed validate_gemm_args, on `cus` compute units (the launch: device_cus()).
+static GemmPlan plan_gemm(const svdq_gemm_args *a, int cus) {
+    GemmPlan pl = {};
+    pl.dtype = a->dtype; pl.fuse = a->fuse; pl.cus = cus;
+    pl.laq = a->lora_act_format != SVDQ_LORA_ACT_F32;
+    pl.la_off = workspace_slab_bytes(cus); pl.lu_off = pl.la_off + LA_PACK_BYTES; pl.act16_off = workspace_bytes_needed(cus);
+    const bool gelu = a->fuse == SVDQ_FUSE_GELU_QUANT, with_ws = a->workspace && a->workspace_bytes >= workspace_bytes_needed(cus);
+    const bool whole_pieces = !pl.laq && a->lora_act_in && a->lora_up && (((uintptr_t)a->lora_act_in | (uintptr_t)a->lora_up | (uintptr_t)a->lora_up2) & 15) == 0;
+    // the 256 x 128 geometry stages a tile's low-rank operands in LDS when they are whole 1 KiB pieces: rank 32, fp32, 16-byte aligned
+    pl.stage_lora = a->R == 32 && whole_pieces;
+    // ... beyond rank 32 the all-rank kernels, whose lora_act_in is a packed image in the workspace tail (no workspace, or an image beyond its tail: the
+    // rank > 32 fallback loads of the plain kernels); those without LDS to stage lora_up in read it packed as well, when it fits its tail (one weight set)
+    const bool la_image = a->R > 32 && a->R <= Geo<8>::STG_LU_ALL_MAX_R && whole_pieces && with_ws && (long long)a->M_pad * a->R * 2 <= LA_PACK_BYTES;
+    const bool lu_image = la_image && !a->wgt2 && (long long)a->N * a->R * 2 <= LU_PACK_BYTES;
+
+    // --- geometry.  With a workspace that holds the launch's 16-bit output image behind the packed operands (svdq_gemm_workspace_bytes_for), the split low-rank
+    // down projection: the all-rank kernel on 256 x 128 tiles stores fragments, lowrank_down_split_kernel contracts them.  It takes the solo-carry kernel's
+    // launches: rank-128 fc1 of FLUX 380 -> ~250 us (profiles/r5_split_down_ab.txt).
+    pl.split = la_image && split_down_wanted(a, cus) && a->workspace_bytes >= pl.act16_off + (long long)a->M_pad * a->N * 2;
+    pl.split_R2 = pl.split ? a->R2 : 0;
+    const int R2 = pl.split ? 0 : a->R2; // (the GEMM kernel neither loads nor contracts the down projection)
+    // GELU_QUANT with a next-layer low-rank branch beyond rank 32 (fp32 accumulators) and at least two 128 x 128 tiles per CU: the solo-carry kernel
+    // (geometry 6 asks for it at any size and any next-layer rank <= 128: tests; launches it cannot serve run as with geometry 0)
+    // (measured, profiles/r5_rank_ab.txt: next rank 128: 559 us against 615 us with per-tile atomics on 256 x 128 tiles; next rank 48: 310 against 285 -- one wave
+    //  per SIMD runs the VALU-bound GELU epilogue at half the issue rate, which only pays once the atomics of >= 96 ranks are what it replaces)
+    pl.solo_carry = !pl.split && gelu && !pl.laq && a->R2 > 0 && a->R2 <= 128 &&
+                    (a->geometry == 6 || (a->geometry == 0 && a->R2 >= 96 && (long long)(a->M_pad / 128) * (a->N / BN) >= 2LL * cus));
+    // (1 .. 5 are the caller's; 0, and 6 / 7 / 8 where the kernel they ask for does not serve the launch: the rule)
+    const int geo = pl.split ? 1 : pl.solo_carry ? 3 : (a->geometry >= 1 && a->geometry <= 5) ? a->geometry : auto_geometry(a, with_ws, cus);
+    // the plain epilogue at rank 0 / 32 with a long K (fc2): the 128 x 64 wave tile, one wave per SIMD -- where the rule above picked 256 x 128 tiles
+    // (an explicit geometry 1 keeps the 8-wave kernel: tests, same-box A/B)
+    // (end of round 6: since the scale tile runs on the K = 8 MFMA form and the product MFMA lost its MX scales, the 8-wave loop gained more than the wave-tile
+    //  loop -- at K = 3072 the 8-wave kernel is the faster one again (51.8-53.1 us against 53.4-53.9), at K = 12288 the wave-tile kernel stays ahead (164.7-167.5
+    //  against 169.1-172.4): the library's own choice takes it from K = 8192; profiles/r6_gemm_wave_tile_probe.txt section 8)
+    const bool wave_tile = wt128_serves(a) && (a->geometry == 8 || (a->geometry == 0 && geo == 1 && a->K >= 8192));
+    const bool rows256 = wave_tile || geo == 1;
+    pl.family = wave_tile ? FAMILY_WAVE_TILE : rows256 ? FAMILY_8WAVE : FAMILY_4WAVE;
+    pl.tile_rows = rows256 ? 256 : 128;
+
+    // --- schedule: one workgroup per CU on 256-row tiles, two on 128-row tiles
+    const int TM = a->M_pad / pl.tile_rows, TN = a->N / BN;
+    pl.tiles = TM * TN; pl.slots = rows256 ? cus : 2 * cus;
+    pl.sk_gs = with_ws ? streamk_groups_for(pl.tiles, a->K / 128, pl.slots) : 0;
+    // dynamic tile queues (128 x 128 geometry): when every slot has more than one tile to do and the remainder is not
+    // better served by a K split (long K: few, long tiles -- a queue cannot balance 1.7 tiles per workgroup)
+    pl.dynamic = !rows256 && (geo == 2 || geo == 4) && with_ws && pl.tiles > pl.slots && pl.sk_gs == 0;
+    pl.stagger = !rows256 && (geo == 4 || geo == 5);
+    pl.grid = pl.dynamic ? pl.slots /* every CU hosts two workgroups; the queue balances them */ : persistent_grid(pl.tiles, pl.sk_gs, pl.slots);
+    const bool runs = rows256 && rowrun_applies(a->M_pad, a->N, R2, pl.sk_gs, pl.slots);
+
+    // --- kernel variant: the first that serves the launch
+    const bool can_carry = rows256 && gelu && !pl.laq;
+    if (wave_tile) {
+        pl.variant = PLAN_WAVE_TILE_128;
+    } else if (pl.solo_carry) {
+        // next-layer ranks 48 .. 128: the carry lives behind the ring of ONE 128 x 128 workgroup per CU, one run of column tiles each.  Its low-rank up projection
+        // reads packed fragments of both operands when they fit the workspace tail (rank 48 .. 160, fp32, one weight set: a grouped launch's second lora_up is not packed)
+        pl.variant = PLAN_SOLO_CARRY; pl.carry = true;
+        pl.sk_gs = 0; pl.slots = cus;
+        pl.grid = rowrun_grid(TM, TN, cus, &pl.rowrun);
+        pl.la_packed = pl.lu_packed = lu_image;
+    } else if (!rows256 && lu_image) {
+        // rank 48 .. 160 on 128 x 128 tiles (no LDS to stage in): both low-rank operands packed, then the all-rank kernel of this geometry
+        pl.variant = PLAN_ALL_RANK; pl.rall = true;
+        pl.la_packed = pl.lu_packed = true;
+    } else if (rows256 && gelu && a->lora_act_format == SVDQ_LORA_ACT_Q32_RUNS && R2 > 0 && R2 <= 32 && runs) {
+        // SVDQ_LORA_ACT_Q32_RUNS (ABI 22): the row-run schedule with its fp32 carry, the run's sum converted to fixed point at the flush -- no atomics in a tile
+        pl.variant = PLAN_CARRY; pl.carry = true;
+        pl.grid = rowrun_grid(TM, TN, pl.slots, &pl.rowrun);
+    } else if (can_carry && R2 > 32 && runs) {
+        // beyond rank 32 (and not the solo-carry kernel's case): the hybrid carry
+        pl.variant = PLAN_HYBRID_CARRY; pl.carry = pl.hyb = true;
+        pl.grid = rowrun_grid(TM, TN, pl.slots, &pl.rowrun);
+    } else if (can_carry && R2 > 0 && R2 <= 32) {
+        // the low-rank-down carry (and, from two tiles per workgroup, the row-run schedule that makes it pay): GELU_QUANT on 256 x 128 tiles with an fp32
+        // next-layer low-rank branch of rank <= 32
+        pl.variant = PLAN_CARRY; pl.carry = true;
+        if (runs) pl.grid = rowrun_grid(TM, TN, pl.slots, &pl.rowrun);
+    } else if (rows256 && la_image) {
+        // 32 < rank <= 160: the kernel with the all-rank lora_up image (Geo::STG_LU_ALL_MAX_R; value = the gather's divider ceil(65536 / (R / 8 + 1))), behind the
+        // pack of its low-rank activations -- split: with the fragment-storing epilogue, between the pack of the next layer's down projection(s) and the contraction
+        pl.variant = pl.split ? PLAN_SPLIT_DOWN : PLAN_ALL_RANK; pl.rall = true;
+        pl.stage_lu_all = 65536 / (a->R / 8 + 1) + 1;
+        pl.la_packed = true;
+    } else {
+        pl.variant = PLAN_PLAIN;
     }
+    // ABI 21: the caller's own fragment image replaces the workspace copy (and its per-launch pack kernel)
+    pl.lu_pre = pl.lu_packed && a->lora_up_packed != nullptr;
+    return pl;
+}
+
+// kernel parameters: the arguments, and what the plan decided
+static void fill_params(GemmParams &p, const svdq_gemm_args *a, const GemmPlan &pl) {
+    p.act = (const uint8_t *)a->act; p.wgt = (const uint8_t *)a->wgt; p.ascales = a->ascales; p.wscales = a->wscales; p.bias = a->bias;
+    p.lora_act_in = a->lora_act_in; p.lora_up = a->lora_up;
+    p.out = a->out; p.qout = (uint8_t *)a->qout; p.oscales = a->oscales;
+    p.next_smooth = a->next_smooth; p.next_lora_down = a->next_lora_down; p.lora_act_out = a->lora_act_out;
+    p.norm_q = a->norm_q; p.norm_k = a->norm_k; p.rotary_emb = a->rotary_emb;
+    p.wgt2 = (const uint8_t *)a->wgt2; p.wscales2 = a->wscales2; p.bias2 = a->bias2; p.lora_up2 = a->lora_up2;
+    p.next_smooth2 = a->next_smooth2; p.next_lora_down2 = a->next_lora_down2; p.norm_q2 = a->norm_q2; p.norm_k2 = a->norm_k2;
+    p.split_row = a->wgt2 ? a->split_rows : 0x7fffffff;
+    p.out_vt = a->fuse == SVDQ_FUSE_RMSNORM_ROPE ? a->out_vt : nullptr; p.ldvt = a->ldvt;
+    p.workspace = (uint8_t *)a->workspace; p.workspace_bytes = a->workspace_bytes;
+    p.M = a->M; p.M_pad = a->M_pad; p.N = a->N; p.K = a->K; p.R = a->R; p.R2 = pl.split ? 0 : a->R2; p.ldo = a->ldo;
+    p.lora_fixed = a->lora_act_format;
+    p.status = a->status;
+    p.q_scale = a->q_scale == 0.f ? 1.0f : a->q_scale;
+    for (int i = 0; i < MAX_LORA_TILES; i++) p.lora_scales[i] = (a->lora_scales && i < a->R / 16) ? a->lora_scales[i] : 1.0f;
+    p.sk_gs = pl.sk_gs; p.stagger = pl.stagger; p.dynamic = pl.dynamic; p.rowrun = pl.rowrun; p.solo_carry = pl.solo_carry;
+    p.stage_lora = pl.stage_lora; p.stage_lu_all = pl.stage_lu_all;
+    p.la_packed = pl.la_packed ? p.workspace + pl.la_off : nullptr;
+    p.lu_packed = !pl.lu_packed ? nullptr : pl.lu_pre ? a->lora_up_packed : p.workspace + pl.lu_off;
+    p.lu_pre = pl.lu_pre;
+    p.ld_pre = a->next_lora_down_packed; p.ld2_pre = a->next_lora_down_packed2;
+    p.act16_packed = pl.split ? p.workspace + pl.act16_off : nullptr;
+    p.split_R2 = pl.split_R2;
+    SVDQ_PROBE_FILL(p);
+}
+
+// the pack kernels in front of a GEMM whose low-rank operands run as fragment images
+template <int DT>
+static void launch_packs(const GemmPlan &pl, const GemmParams &p, hipStream_t st) {
+    using V8 = typename Half<DT>::V8;
+    const int units = p.R / 16;
+    if (pl.pack_la()) {
+        float16_scales sc;
+        for (int i = 0; i < MAX_LORA_TILES; i++) sc.v[i] = p.lora_scales[i];
+        hipLaunchKernelGGL((pack_lora_act_kernel<DT>), dim3(p.M_pad / 32, (units + 3) / 4), dim3(256), 0, st, (const float *)p.lora_act_in, (V8 *)p.la_packed, p.R, units, sc);
+    }
+    if (pl.pack_lu())
+        hipLaunchKernelGGL((pack_lora_up_kernel<DT>), dim3(p.N / 32, (units + 3) / 4), dim3(256), 0, st, (const typename Half<DT>::T *)p.lora_up, (V8 *)p.lu_packed, p.R, units);
+}
+// The instantiation the plan's switches name.  The if constexpr guards keep combinations no plan asks for from being instantiated; a plan that asks for one
+// anyway launches nothing and returns false.
+template <int DT, int FUSE, int NW, bool LAQ>
+static bool launch_variant(const GemmPlan &pl, const GemmParams &p, hipStream_t st) {
+    constexpr bool GELU = FUSE == SVDQ_FUSE_GELU_QUANT;
+    const dim3 grid(pl.grid), block(Geo<NW>::THREADS);
+    launch_packs<DT>(pl, p, st);
+    if (pl.split) { // pack the next layer's down projection(s), the GEMM with the fragment-storing epilogue, the contraction
+        if constexpr (NW == 8 && GELU && !LAQ) {
+            launch_lowrank_down_split<DT>(p.act16_packed, p.next_lora_down, p.next_lora_down2, p.split_row, p.M_pad, p.N, p.split_R2, (float *)p.lora_act_out,
+                                          p.workspace + pl.lu_off, pl.cus, st,
+                                          [&]() { hipLaunchKernelGGL((gemm_w4a4_kernel<DT, FUSE, NW, LAQ, false, true, false, true>), grid, block, 0, st, p); },
+                                          p.ld_pre, p.ld2_pre);
+            return true;
+        }
+    } else if (pl.hyb) {
+        if constexpr (NW == 8 && GELU && !LAQ) { hipLaunchKernelGGL((gemm_w4a4_kernel<DT, FUSE, NW, LAQ, true, false, true>), grid, block, 0, st, p); return true; }
+    } else if (pl.carry) { // 256 x 128 tiles (fp32 carry under either accumulator format), or the solo-carry kernel
+        if constexpr (GELU && (NW == 8 || !LAQ)) { hipLaunchKernelGGL((gemm_w4a4_kernel<DT, FUSE, NW, LAQ, true>), grid, block, 0, st, p); return true; }
+    } else if (pl.rall) {
+        if constexpr (!LAQ) { hipLaunchKernelGGL((gemm_w4a4_kernel<DT, FUSE, NW, LAQ, false, true>), grid, block, 0, st, p); return true; }
+    } else {
+        hipLaunchKernelGGL((gemm_w4a4_kernel<DT, FUSE, NW, LAQ>), grid, block, 0, st, p);
+        return true;
+    }
+    return false;
+}
+template <int DT, int NW>
+static bool launch_family(const GemmPlan &pl, const GemmParams &p, hipStream_t st) {
+    switch (pl.fuse * 2 + pl.laq) {
+    case SVDQ_FUSE_NONE * 2: return launch_variant<DT, SVDQ_FUSE_NONE, NW, false>(pl, p, st);
+    case SVDQ_FUSE_NONE * 2 + 1: return launch_variant<DT, SVDQ_FUSE_NONE, NW, true>(pl, p, st);
+    case SVDQ_FUSE_SILU * 2: return launch_variant<DT, SVDQ_FUSE_SILU, NW, false>(pl, p, st);
+    case SVDQ_FUSE_SILU * 2 + 1: return launch_variant<DT, SVDQ_FUSE_SILU, NW, true>(pl, p, st);
+    case SVDQ_FUSE_GELU_QUANT * 2: return launch_variant<DT, SVDQ_FUSE_GELU_QUANT, NW, false>(pl, p, st);
+    case SVDQ_FUSE_GELU_QUANT * 2 + 1: return launch_variant<DT, SVDQ_FUSE_GELU_QUANT, NW, true>(pl, p, st);
+    case SVDQ_FUSE_RMSNORM_ROPE * 2: return launch_variant<DT, SVDQ_FUSE_RMSNORM_ROPE, NW, false>(pl, p, st);
+    case SVDQ_FUSE_RMSNORM_ROPE * 2 + 1: return launch_variant<DT, SVDQ_FUSE_RMSNORM_ROPE, NW, true>(pl, p, st);
+    }
+    return false;
+}
+template <int DT>
+static bool launch_dtype(const GemmPlan &pl, const GemmParams &p, hipStream_t st) {
+    switch (pl.family) {
+    case FAMILY_WAVE_TILE: hipLaunchKernelGGL((gemm_w4a4_wt128_kernel<DT>), dim3(pl.grid), dim3(256), 0, st, p); return true;
+    case FAMILY_8WAVE: return launch_family<DT, 8>(pl, p, st);
+    case FAMILY_4WAVE: return launch_family<DT, 4>(pl, p, st);
+    }
+    return false;
+}
+// Issues the launches of a plan: pack kernels, the GEMM, the split's contraction.  Decides nothing (the probe build's SVDQ_PROBE_GRID experiment aside).
+static bool launch_gemm(GemmPlan pl, const GemmParams &p, hipStream_t st) {
+    pl.grid = SVDQ_PROBE_GRID(pl.grid, pl.tiles, pl.slots);
+    pl.words(g_last_plan);
+    return pl.dtype == SVDQ_BF16 ? launch_dtype<SVDQ_BF16>(pl, p, st) : launch_dtype<SVDQ_FP16>(pl, p, st);
 }
 
 } // namespace svdq
 
 using namespace svdq;
 
-extern "C" int64_t svdq_gemm_workspace_bytes(void) { return workspace_bytes_needed(); }
+extern "C" int64_t svdq_gemm_workspace_bytes(void) { return workspace_bytes_needed(device_cus()); }
 // ABI 20: the size with which THIS launch takes every fast path it has -- svdq_gemm_workspace_bytes(), plus the 16-bit output image of a GELU_QUANT launch whose
 // next-layer low-rank down projection can run split (M_pad * N * 2 bytes).  A smaller workspace is never an error: the launch takes the path that fits.
 extern "C" int64_t svdq_gemm_workspace_bytes_for(const svdq_gemm_args *a) {
-    if (!a) return workspace_bytes_needed();
-    if (a->M_pad <= 0 || a->N <= 0 || a->M_pad % 256 || a->N % 128 || a->R < 0 || a->R2 < 0) return workspace_bytes_needed();
-    const bool want = split_down_shape_ok(a) && (a->geometry == 7 || (a->geometry == 0 && split_down_auto(a)));
-    return workspace_bytes_needed() + (want ? (long long)a->M_pad * a->N * 2 : 0);
+    const long long base = workspace_bytes_needed(device_cus());
+    if (!a || a->M_pad <= 0 || a->N <= 0 || a->M_pad % 256 || a->N % 128 || a->R < 0 || a->R2 < 0) return base;
+    return base + (split_down_wanted(a, device_cus()) ? (long long)a->M_pad * a->N * 2 : 0);
 }
 
 extern "C" int svdq_gemm_last_plan(int32_t *out8) {
@@ -1984,9 +2059,8 @@ extern "C" int svdq_gemm_schedule_ex(int32_t M_pad, int32_t N, int32_t K, int32_
         // would take the plain schedule (fewer than two tiles per workgroup)
         const int TM = M_pad / 256, TN = N / BN;
         if (!rowrun_applies(M_pad, N, 32, 0, cus)) return -1;
-        const int rl = GemmSchedule::run_length(TM, TN, cus);
-        const int G = (TM * ((TN + rl - 1) / rl) + 7) / 8 * 8;
-        int n = 0;
+        int rl, n = 0;
+        const int G = rowrun_grid(TM, TN, cus, &rl);
         for (int pos = 0; pos < G; pos++) {
             GemmSchedule sc;
             sc.init_runs(TM, TN, K / 128, rl, pos);
@@ -2047,7 +2121,8 @@ extern "C" int svdq_pack_lora_up(const void *lu, void *out, int32_t N, int32_t R
     return hip_check(hipGetLastError(), "svdq_pack_lora_up launch");
 }
 
-extern "C" int svdq_gemm_w4a4(const svdq_gemm_args *a, void *stream) {
+// what svdq_gemm_w4a4 refuses, and svdq_gemm_plan with it
+static int validate_gemm_args(const svdq_gemm_args *a) {
     if (!a) { set_error("svdq_gemm_w4a4: args is NULL"); return SVDQ_E_INVALID; }
     if (!a->act || !a->wgt || !a->ascales || !a->wscales) {
         set_error("svdq_gemm_w4a4: act, wgt, ascales and wscales are required");
@@ -2136,103 +2211,26 @@ extern "C" int svdq_gemm_w4a4(const svdq_gemm_args *a, void *stream) {
         set_error("svdq_gemm_w4a4: out, bias, next_smooth, next_lora_down, norm_q, norm_k, lora_act_out must be 8-byte aligned");
         return SVDQ_E_INVALID;
     }
+    return SVDQ_OK;
+}
 
+extern "C" int svdq_gemm_w4a4(const svdq_gemm_args *a, void *stream) {
+    if (const int rc = validate_gemm_args(a)) return rc;
+    const GemmPlan pl = plan_gemm(a, device_cus());
     GemmParams p;
-    p.act = (const uint8_t *)a->act;
-    p.wgt = (const uint8_t *)a->wgt;
-    p.ascales = a->ascales;
-    p.wscales = a->wscales;
-    p.bias = a->bias;
-    p.lora_act_in = a->lora_act_in;
-    p.lora_up = a->lora_up;
-    p.out = a->out;
-    p.qout = (uint8_t *)a->qout;
-    p.oscales = a->oscales;
-    p.next_smooth = a->next_smooth;
-    p.next_lora_down = a->next_lora_down;
-    p.lora_act_out = a->lora_act_out;
-    p.norm_q = a->norm_q;
-    p.norm_k = a->norm_k;
-    p.rotary_emb = a->rotary_emb;
-    p.wgt2 = (const uint8_t *)a->wgt2; p.wscales2 = a->wscales2; p.bias2 = a->bias2; p.lora_up2 = a->lora_up2;
-    p.next_smooth2 = a->next_smooth2; p.next_lora_down2 = a->next_lora_down2; p.norm_q2 = a->norm_q2; p.norm_k2 = a->norm_k2;
-    p.split_row = a->wgt2 ? a->split_rows : 0x7fffffff;
-    p.out_vt = a->fuse == SVDQ_FUSE_RMSNORM_ROPE ? a->out_vt : nullptr;
-    p.ldvt = a->ldvt;
-    p.workspace = (uint8_t *)a->workspace;
-    p.workspace_bytes = a->workspace_bytes;
-    p.M = a->M; p.M_pad = a->M_pad; p.N = a->N; p.K = a->K; p.R = a->R; p.R2 = a->R2; p.ldo = a->ldo;
-    p.lora_fixed = a->lora_act_format;
-    // the 256 x 128 geometry stages a tile's low-rank operands in LDS when they are whole 1 KiB pieces: rank 32, fp32, 16-byte aligned
-    p.stage_lora = a->R == 32 && a->lora_act_format == SVDQ_LORA_ACT_F32 && a->lora_act_in && a->lora_up &&
-                   (((uintptr_t)a->lora_act_in | (uintptr_t)a->lora_up | (uintptr_t)a->lora_up2) & 15) == 0;
-    // ... or, beyond rank 32, the tile's lora_up for every rank (Geo::STG_LU_ALL_MAX_R): value = the gather's divider ceil(65536 / (R / 8 + 1))
-    p.stage_lu_all = 0;
-    if (a->R > 32 && a->R <= Geo<8>::STG_LU_ALL_MAX_R && a->lora_act_format == SVDQ_LORA_ACT_F32 && a->lora_act_in && a->lora_up &&
-        (((uintptr_t)a->lora_act_in | (uintptr_t)a->lora_up | (uintptr_t)a->lora_up2) & 15) == 0)
-        p.stage_lu_all = 65536 / (a->R / 8 + 1) + 1;
-    p.la_packed = nullptr; // (set below once the workspace is known to hold the image)
-    p.status = a->status;
-    p.q_scale = a->q_scale == 0.f ? 1.0f : a->q_scale;
-    for (int i = 0; i < MAX_LORA_TILES; i++) p.lora_scales[i] = (a->lora_scales && i < a->R / 16) ? a->lora_scales[i] : 1.0f;
-    SVDQ_PROBE_FILL(p);
-
-    const bool with_ws = p.workspace && p.workspace_bytes >= workspace_bytes_needed();
-    if (p.stage_lu_all && with_ws && (long long)a->M_pad * a->R * 2 <= LA_PACK_BYTES) p.la_packed = p.workspace + workspace_slab_bytes();
-    else p.stage_lu_all = 0; // (no workspace, or an image beyond its tail: the rank > 32 fallback loads of the plain kernels)
-    p.lu_packed = nullptr;
-    int geo = pick_geometry(a, with_ws);
-    // GELU_QUANT with a next-layer low-rank branch beyond rank 32 (fp32 accumulators) and at least two 128 x 128 tiles per CU: the solo-carry kernel
-    // (geometry 6 asks for it at any size and any next-layer rank <= 128: tests; launches it cannot serve run as with geometry 0)
-    const bool solo_ok = a->fuse == SVDQ_FUSE_GELU_QUANT && a->R2 > 0 && a->R2 <= 128 && a->lora_act_format == SVDQ_LORA_ACT_F32;
-    // (measured, profiles/r5_rank_ab.txt: next rank 128: 559 us against 615 us with per-tile atomics on 256 x 128 tiles; next rank 48: 310 against 285 -- one wave
-    //  per SIMD runs the VALU-bound GELU epilogue at half the issue rate, which only pays once the atomics of >= 96 ranks are what it replaces)
-    p.solo_carry = solo_ok && (a->geometry == 6 || (a->geometry == 0 && a->R2 >= 96 && (long long)(a->M_pad / 128) * (a->N / BN) >= 2LL * device_cus()));
-    // ... or, with a workspace that holds the launch's 16-bit output image behind the packed operands (svdq_gemm_workspace_bytes_for), the split low-rank down
-    // projection: the all-rank kernel on 256 x 128 tiles stores fragments, lowrank_down_split_kernel contracts them (geometry 7 asks for it at any size and from
-    // next-layer rank 48: tests, A/B).  It takes the solo-carry kernel's launches: rank-128 fc1 of FLUX 380 -> ~250 us (profiles/r5_split_down_ab.txt).
-    p.act16_packed = nullptr;
-    p.split_R2 = 0;
-    if (p.la_packed && split_down_shape_ok(a) && p.workspace_bytes >= workspace_bytes_needed() + (long long)a->M_pad * a->N * 2 &&
-        (a->geometry == 7 || (a->geometry == 0 && split_down_auto(a)))) {
-        p.act16_packed = p.workspace + workspace_bytes_needed();
-        p.split_R2 = a->R2;
-        p.R2 = 0; // (the GEMM kernel neither loads nor contracts the down projection)
-        p.solo_carry = 0;
-        geo = 1;
-    } else if (geo == 7) { svdq_gemm_args b = *a; b.geometry = 0; geo = pick_geometry(&b, with_ws); }
-    if (p.solo_carry) {
-        geo = 3;
-        // its low-rank up projection reads packed fragments of both operands when they fit the workspace tail (rank 48 .. 160, fp32, one weight set)
-        if (p.la_packed && !a->wgt2 && (long long)a->N * a->R * 2 <= LU_PACK_BYTES) p.lu_packed = p.workspace + workspace_slab_bytes() + LA_PACK_BYTES;
-        else p.la_packed = nullptr;
-    }
-    else if (geo == 6) { svdq_gemm_args b = *a; b.geometry = 0; geo = pick_geometry(&b, with_ws); }
-    // rank 48 .. 160 on 128 x 128 tiles (no LDS to stage in): both low-rank operands as packed fragments when they fit the workspace tail (one weight set)
-    if (!p.solo_carry && geo != 1 && p.la_packed && !a->wgt2 && (long long)a->N * a->R * 2 <= LU_PACK_BYTES) p.lu_packed = p.workspace + workspace_slab_bytes() + LA_PACK_BYTES;
-    p.dynamic = geo == 2 || geo == 4;
-    p.stagger = geo == 4 || geo == 5;
-    // ABI 21: the caller's own fragment images replace the workspace copies (and their per-launch pack kernels)
-    p.ld_pre = a->next_lora_down_packed; p.ld2_pre = a->next_lora_down_packed2;
-    p.lu_pre = p.lu_packed != nullptr && a->lora_up_packed != nullptr;
-    if (p.lu_pre) p.lu_packed = a->lora_up_packed;
+    fill_params(p, a, pl);
     hipStream_t st = (hipStream_t)stream;
     const int prof = prof_begin(SVDQ_PROF_GEMM_VARIANT(a->fuse), 2.0 * a->M_pad * (double)a->N * a->K + 2.0 * a->M_pad * (double)a->N * a->R, st);
-    // the plain epilogue at rank 0 / 32 with a long K (fc2): the 128 x 64 wave tile, one wave per SIMD -- where the rule above picked 256 x 128 tiles
-    // (an explicit geometry 1 keeps the 8-wave kernel: tests, same-box A/B)
-    // (end of round 6: since the scale tile runs on the K = 8 MFMA form and the product MFMA lost its MX scales, the 8-wave loop gained more than the wave-tile
-    //  loop -- at K = 3072 the 8-wave kernel is the faster one again (51.8-53.1 us against 53.4-53.9), at K = 12288 the wave-tile kernel stays ahead (164.7-167.5
-    //  against 169.1-172.4): the library's own choice takes it from K = 8192; profiles/r6_gemm_wave_tile_probe.txt section 8)
-    if (wt128_serves(a) && (a->geometry == 8 || (a->geometry == 0 && geo == 1 && a->K >= 8192))) {
-        if (a->dtype == SVDQ_BF16) launch_wt128<SVDQ_BF16>(p, with_ws, st);
-        else launch_wt128<SVDQ_FP16>(p, with_ws, st);
-    } else if (geo == 1) {
-        if (a->dtype == SVDQ_BF16) launch_fuse<SVDQ_BF16, 8>(p, a->fuse, with_ws, st);
-        else launch_fuse<SVDQ_FP16, 8>(p, a->fuse, with_ws, st);
-    } else {
-        if (a->dtype == SVDQ_BF16) launch_fuse<SVDQ_BF16, 4>(p, a->fuse, with_ws, st);
-        else launch_fuse<SVDQ_FP16, 4>(p, a->fuse, with_ws, st);
-    }
+    const bool launched = launch_gemm(pl, p, st);
     prof_end(prof, st);
+    if (!launched) { set_error("svdq_gemm_w4a4: no kernel for plan variant %d on %d-row tiles (fuse %d, lora_act_format %d)", pl.variant, pl.tile_rows, a->fuse, a->lora_act_format); return SVDQ_E_UNSUPPORTED; }
     return hip_check(hipGetLastError(), "svdq_gemm_w4a4 launch");
+}
+
+// Host only: the eight words svdq_gemm_last_plan reports after this launch, on `cus` compute units (0 = the device's); launches nothing
+extern "C" int svdq_gemm_plan(const svdq_gemm_args *a, int32_t cus, int32_t *out8) {
+    if (const int rc = validate_gemm_args(a)) return rc;
+    if (!out8 || cus < 0 || cus > 256) { set_error("svdq_gemm_plan: needs out and 0 <= cus=%d <= 256", cus); return SVDQ_E_INVALID; }
+    plan_gemm(a, cus ? cus : device_cus()).words(out8);
+    return SVDQ_OK;
 }

@@ -4,7 +4,9 @@ held to the oracle.  The case tables are module-level constants: tests/test_hot_
 built library holds.
 
 * GEMM and attention rows carry the key of the instantiation they claim, and every launch asserts that ``ops.gemm_last_plan()`` /
-  ``ops.attention_last_plan()`` report that key: the claim is witnessed by the dispatch code itself.
+  ``ops.attention_last_plan()`` report that key: the claim is witnessed by the dispatch code itself.  (A GEMM key needs no launch to be read:
+  ``svdq_gemm_plan`` answers from the same ``plan_gemm`` without a GPU, and tests/test_gemm_plan.py pins its answers there; here the key is
+  read off the launch whose output is checked.)
 * The quantiser has no plan query.  Its rows state their instantiation through ``quant_instantiation`` below, a restatement of the rule in
   csrc/quantize.hip (``launch_quantize``).  That restatement is this ledger's limit, as ``CLASS_RULES`` is the limit of tests/test_dispatch_ledger.py:
   if the launcher changes its rule and the restatement is not changed with it, a row is counted for a kernel it no longer launches.  The same holds for
@@ -70,7 +72,7 @@ H_STEPS_ALLOWED = {("bf16", 512): 4, ("bf16", 1024): 16, ("bf16", 8192): 6, ("fp
 
 
 def gemm_instantiations(case) -> set:
-    """the template arguments behind a row's key, without DT: {(kernel, args)} (launch_one_laq / launch_wt128 of csrc/gemm_w4a4.hip)"""
+    """the template arguments behind a row's key, without DT: {(kernel, args)} (GemmPlan's switches, launch_variant of csrc/gemm_w4a4.hip)"""
     fuse, _, _, _, r2, *_, (rows, variant, laq) = case
     if variant == "wave_tile_128":
         return {("gemm_w4a4_wt128_kernel", ())}

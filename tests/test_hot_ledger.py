@@ -3,7 +3,8 @@ activation quantiser and attention that the built library holds (kernel names in
 names only, no instruction is looked at) against the instantiations the case tables of tests/test_gpu_hot_instantiations.py claim.  Whoever adds an
 instantiation gets a failing test that names the one without a case; whoever drops a table row gets one that names the instantiation left unlaunched.
 
-Its limit: GEMM and attention rows are witnessed on the GPU (every launch asserts the plan the library reports), the quantiser rows are not -- they go
+Its limit: GEMM and attention rows are witnessed by the library (every launch asserts the plan it reports; the GEMM's plan is the host function plan_gemm,
+which svdq_gemm_plan also answers without a GPU: tests/test_gemm_plan.py), the quantiser rows are not -- they go
 through ``quant_instantiation``, a restatement of launch_quantize's rule (csrc/quantize.hip), and the 4- / 8-wave attention kernels through ``L % 256``.
 If a launcher changes such a rule and the restatement is not changed with it, the ledger reports "reached" for a kernel the tables no longer launch."""
 import math
