@@ -132,7 +132,21 @@ typedef struct svdq_quantize_args {
     int32_t reserved;
 } svdq_quantize_args;
 
+/* Addressing reach ("Addressing reach"; refused or re-routed on the host, never wrapped on the device):
+ *   ldx, ldx2           unbounded: the general kernel forms row addresses in 64 bits.  The fast kernel reads x through a buffer descriptor with 32-bit byte
+ *                       offsets; a launch takes it only while M_pad * max(ldx, ldx2) * 2 < 0x7fffffff and R * K * 2 < 0x7fffffff (svdq_quantize_plan)
+ *   M_pad * K, M_pad * R  unbounded: 64-bit products */
 int svdq_quantize_w4a4_act_fuse_lora(const svdq_quantize_args *args, void *stream);
+
+/* Host only, launches nothing (the quantiser's svdq_gemm_plan): validates `args` exactly as svdq_quantize_w4a4_act_fuse_lora does (same return codes and
+ * messages), then writes what that launch would take -- the launch reads the same function and decides nothing else:
+ *   out8[0]  kernel family: 0 = fast (quantize_kernel_v2, 32-bit byte offsets into x), 1 = general (quantize_kernel, 64-bit row addresses)
+ *   out8[1]  fast: the quantize_kernel_v2 switch set (bit 0 smooth, bit 1 LayerNorm front end, bit 2 low rank, bit 3 rank > 32);
+ *            general: the quantize_kernel rank class (0, 1, 2, 4, 8 tiles of 32 ranks)
+ *   out8[2]  chunks of 128 columns per workgroup (cpw)      out8[3]  K slices per row tile
+ *   out8[4]  lora_act_add mode: bit 0 = atomics (K is sliced), bit 1 = Q31.32 format
+ *   out8[5]  grid      out8[6]  fuse_glu      out8[7]  1 = the launch clears lora_act first */
+int svdq_quantize_plan(const svdq_quantize_args *args, int32_t out8[8]);
 
 /* ------------------------------------------------------------------------------------------
  * svdq_gemm_w4a4
@@ -239,6 +253,11 @@ typedef struct svdq_gemm_args {
     const void *lora_up_packed;
 } svdq_gemm_args;
 
+/* Addressing reach ("Addressing reach"):
+ *   ldo                 unbounded.  The wave-tile kernel's epilogue stores take a 32-bit byte offset (254 * ldo + 16 over a wave's 128 rows): it serves
+ *                       ldo <= 16909316; a launch with a wider out takes the 8-wave kernel (64-bit row addresses); svdq_gemm_plan answers which
+ *   ldvt                at most 429496716: the QKV epilogue's lane offset 10 * ldvt + 124 is a 32-bit byte offset; beyond: SVDQ_E_UNSUPPORTED
+ *   M_pad * N, M_pad * K  unbounded: 64-bit products */
 int svdq_gemm_w4a4(const svdq_gemm_args *args, void *stream);
 
 /* ABI 21: the fragment images above.  ld = [R2][N] rank-major (svdq_repack_lowrank(down=1) order), R2 in 48 .. 160, N % 256 == 0 (or R2 = 16 / 32, N % 128 == 0: the
@@ -371,6 +390,11 @@ typedef struct svdq_attention_args {
     const void *qlora_down_packed, *qlora_down_packed2;
 } svdq_attention_args;
 
+/* Addressing reach ("Addressing reach"):
+ *   ldk                 at most 33554424: the geometry-2 loop keeps the K tile stride 128 * ldk in a 32-bit scalar (and key row 63 of a tile sits at the
+ *                       32-bit byte offset 126 * ldk + 240); beyond: SVDQ_E_UNSUPPORTED
+ *   ldvt                at most 16909312: channel row 127 of a V^T tile sits at the 32-bit byte offset 254 * ldvt + 112; beyond: SVDQ_E_UNSUPPORTED
+ *   ldq, ldo, q_hs, k_hs, vt_hs, o_hs   unbounded: 64-bit row and head addresses */
 int svdq_attention(const svdq_attention_args *args, void *stream);
 /* size of the persistent-schedule workspace for the current device (1023 arrival counters + 1 error word + two fp32 slabs per CU: the part a
  * contributor publishes and, for geometry 2, the part the owner of a split task parks while it runs its whole tasks) */
@@ -434,6 +458,10 @@ typedef struct svdq_residual_args {
     int32_t reserved2;
 } svdq_residual_args;
 
+/* Addressing reach ("Addressing reach"):
+ *   ld                  the field's width: (size_t)row * ld
+ *   M, M2, M * ld       int32 row counts; the product is 64-bit
+ *   zero_bytes          int64 */
 int svdq_residual_gate_stats(const svdq_residual_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -472,6 +500,9 @@ typedef struct svdq_residual_diff_args {
     int32_t reserved;
 } svdq_residual_diff_args;
 
+/* Addressing reach:
+ *   ld                  the field's width: (size_t)row * ld
+ *   M, M2, M * ld       int32 row counts (2 * (M + M2) partial sums); the product is 64-bit */
 int svdq_residual_diff(const svdq_residual_diff_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -502,6 +533,9 @@ typedef struct svdq_modulated_diff_args {
     int32_t dtype;
 } svdq_modulated_diff_args;
 
+/* Addressing reach:
+ *   ld                  the field's width: (size_t)row * ld
+ *   M, M2, M * ld       int32 row counts (2 * (M + M2) partial sums); the product is 64-bit */
 int svdq_modulated_diff(const svdq_modulated_diff_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -535,6 +569,9 @@ typedef struct svdq_ip_attention_args {
     float out_scale; /* fp32 */
 } svdq_ip_attention_args;
 
+/* Addressing reach:
+ *   ldq, ldk, ldv, ldo  the field's width: (size_t)row * ld, (size_t)head * 128
+ *   T, T * ld           int32 rows; 64-bit product        N  at most 256 (SVDQ_E_UNSUPPORTED)        H  at most 65535 (the grid) */
 int svdq_ip_attention(const svdq_ip_attention_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -575,6 +612,10 @@ typedef struct svdq_linear_attention_args {
     int32_t reserved;
 } svdq_linear_attention_args;
 
+/* Addressing reach:
+ *   ldq, ldkv, ldo      the field's width: (size_t)row * ld
+ *   q_bs, kv_bs, out_bs int64: (long long)b * bs
+ *   T                   at most 2^30        H, B  at most 65535 each, H * B at most 2^20 (the grid)        T * ld, B * bs  64-bit products */
 int svdq_linear_attention(const svdq_linear_attention_args *args, void *stream);
 int64_t svdq_linear_attention_workspace_bytes(const svdq_linear_attention_args *args);
 
@@ -609,6 +650,10 @@ typedef struct svdq_dwconv3x3_args {
     int32_t reserved;
 } svdq_dwconv3x3_args;
 
+/* Addressing reach:
+ *   ldx, ldo            the field's width: ((long long)h * W + w) * ld
+ *   x_bs, out_bs        int64: (long long)b * bs
+ *   B                   at most 65535        ceil(C/512) * tiles of W * tiles of H  at most 2^31 - 1 (the grid)        H * W * ld, B * bs  64-bit products */
 int svdq_dwconv3x3(const svdq_dwconv3x3_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -649,6 +694,10 @@ typedef struct svdq_cross_attention_args {
     float scale;     /* head_dim^-0.5 in the reference */
 } svdq_cross_attention_args;
 
+/* Addressing reach:
+ *   ldq, ldo            the field's width: (size_t)(b * T + row) * ld
+ *   ldk, ldv            the field's width: (size_t)(key_offsets[b] + key) * ld
+ *   B * H               at most 65535        T  at most 2^30 (the grid)        B * T, Nrows  int32; their products with ld are 64-bit */
 int svdq_cross_attention(const svdq_cross_attention_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -683,6 +732,10 @@ typedef struct svdq_attention_d64_args {
     int32_t reserved;
 } svdq_attention_d64_args;
 
+/* Addressing reach:
+ *   ldq, ldk, ldv, ldo  the field's width: (size_t)row * ld
+ *   q_bs, k_bs, v_bs, out_bs   int64: (size_t)b * bs
+ *   B * H               at most 65535        T, N  at most 2^30 (the grid)        T * ld, N * ld, B * bs  64-bit products */
 int svdq_attention_d64(const svdq_attention_d64_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -737,6 +790,10 @@ typedef struct svdq_sana_glue_args {
     int32_t reserved;
 } svdq_sana_glue_args;
 
+/* Addressing reach:
+ *   ld_res, ld_a, ld_out, ld_mod   the field's width: (size_t)row * ld
+ *   timestep_bs         int64: 64-bit sample offset
+ *   B * T, B * T * ld   int32 rows; 64-bit product */
 int svdq_sana_glue(const svdq_sana_glue_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -779,6 +836,10 @@ typedef struct svdq_sandwich_norm_args {
     int32_t reserved;
 } svdq_sandwich_norm_args;
 
+/* Addressing reach:
+ *   ld_res, ld_a, ld_out, ld_mod   the field's width: (size_t)row * ld
+ *   gate_bs, scale_bs   int64: b * (size_t)bs
+ *   M, M * ld           int32 rows; 64-bit product */
 int svdq_sandwich_norm(const svdq_sandwich_norm_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -811,6 +872,10 @@ typedef struct svdq_qk_norm_rope_args {
     float eps;
 } svdq_qk_norm_rope_args;
 
+/* Addressing reach:
+ *   ld                  the field's width: (size_t)t * ld
+ *   ldvt                the field's width: (size_t)(h * 128 + d) * ldvt
+ *   H                   at most 65535 (the grid)        T, L_pad  int32; T * ld and H * 128 * ldvt are 64-bit products */
 int svdq_qk_norm_rope(const svdq_qk_norm_rope_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -854,6 +919,9 @@ typedef struct svdq_pulid_ca_args {
     float out_scale;     /* fp32 */
 } svdq_pulid_ca_args;
 
+/* Addressing reach:
+ *   ldx, ldo            the field's width: (size_t)row * ld
+ *   T, T * ld, T * H * 32   int32 rows; 64-bit products */
 int svdq_pulid_ca(const svdq_pulid_ca_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -882,6 +950,9 @@ typedef struct svdq_gemv_awq_args {
     int32_t reserved;
 } svdq_gemv_awq_args;
 
+/* Addressing reach:
+ *   ldx                 the field's width: (size_t)m * ldx, M at most 8 (svdq_gemv_awq_batched: M = 1, ldx is not multiplied)
+ *   N * K               the packed weight is indexed in 64 bits */
 int svdq_gemv_awq(const svdq_gemv_awq_args *args, void *stream);
 /* `count` (<= 80) independent GEMVs that share x, M, K, dtype and group_size in ONE launch (extension): all the
  * modulation projections of a denoising step depend only on the timestep embedding, so they can be issued together
@@ -945,6 +1016,9 @@ typedef struct svdq_gemm_awq_args {
     int32_t dtype;            /* SVDQ_BF16 | SVDQ_FP16 */
 } svdq_gemm_awq_args;
 
+/* Addressing reach:
+ *   ldx                 the field's width: (size_t)row * ldx
+ *   M, M * ldx, M * N   int32 rows; 64-bit products */
 int svdq_gemm_awq(const svdq_gemm_awq_args *args, void *stream);
 /* workspace bytes a launch of this shape uses (0: it does not split K) */
 int64_t svdq_gemm_awq_workspace_bytes(int32_t M, int32_t N, int32_t K);

@@ -35,13 +35,33 @@ def _ptr(t: torch.Tensor | None, laid_out: bool = False) -> int | None:
     return t.data_ptr()
 
 
+_I32_MAX, _I64_MAX = (1 << 31) - 1, (1 << 63) - 1
+
+
+def _i32(op: str, name: str, value) -> int:
+    """A stride, an extent or a product of them on its way into a 32-bit field of an args struct.  ctypes keeps the low 32 bits of whatever it is
+    given (2^32 + 16 becomes 16, 2^31 + 8 a negative number): a value that does not fit is an error here, before the library sees a small, valid-looking one."""
+    v = int(value)
+    if not -_I32_MAX - 1 <= v <= _I32_MAX:
+        raise ValueError(f"{op}: {name}={v} does not fit the library's 32-bit field (at most {_I32_MAX})")
+    return v
+
+
+def _i64(op: str, name: str, value) -> int:
+    """the same for the 64-bit head and batch strides"""
+    v = int(value)
+    if not -_I64_MAX - 1 <= v <= _I64_MAX:
+        raise ValueError(f"{op}: {name}={v} does not fit the library's 64-bit field")
+    return v
+
+
 # ---- argument checks of the row passes (residual_gate_stats, residual_diff, modulated_diff; csrc/row_pass.h) ------------------------
 def _row_view(op: str, name: str, t: torch.Tensor) -> tuple:
     """``(M, C, ld, dtype code)`` of the leading tensor of a row pass.  What these checks let through as None (an optional tensor, or a
     required one that is missing) the library judges: it knows which tensors an operation needs."""
     if t.dim() != 2 or t.stride(1) != 1 or t.dtype not in _DT:
         raise ValueError(f"{op}: {name} must be a 2-D 16-bit view with unit column stride")
-    return t.shape[0], t.shape[1], t.stride(0), _DT[t.dtype]
+    return _i32(op, f"{name}.shape[0]", t.shape[0]), _i32(op, f"{name}.shape[1]", t.shape[1]), _i32(op, f"{name}.stride(0)", t.stride(0)), _DT[t.dtype]
 
 
 def _same_view(op: str, ref_name: str, ref: torch.Tensor, **tensors) -> None:
@@ -55,7 +75,7 @@ def _second_rows(op: str, first: torch.Tensor, lead2: torch.Tensor) -> int:
     """M2 of a grouped launch: the second problem has its own row count and nothing else of its own"""
     if lead2.dim() != 2 or lead2.shape[1] != first.shape[1] or lead2.stride() != first.stride() or lead2.dtype != first.dtype:
         raise ValueError(f"{op}: the second problem must have the width, row stride and dtype of the first")
-    return lead2.shape[0]
+    return _i32(op, "second problem: rows", lead2.shape[0])
 
 
 def _vector(op: str, ref_name: str, ref: torch.Tensor, **tensors) -> None:
@@ -472,8 +492,9 @@ class _Ops:
         a.act = _ptr(image)
         a.ascales = _ptr(oscales)
         a.lora_act = _ptr(lora_act_out)
-        a.M, a.M_pad, a.K, a.R = M, M_pad, K, R
-        a.ldx = input.stride(0)
+        op = "quantize_w4a4_act_fuse_lora"
+        a.M, a.M_pad, a.K, a.R = _i32(op, "M", M), _i32(op, "M_pad", M_pad), _i32(op, "K", K), _i32(op, "R", R)
+        a.ldx = _i32(op, "input.stride(0)", input.stride(0))
         a.dtype = _DT[input.dtype]
         a.fuse_glu, a.fp4 = int(bool(fuse_glu)), int(bool(fp4))
         a.lora_act_zeroed = int(bool(lora_act_zeroed))  # extension: lora_act_out already cleared on this stream
@@ -490,7 +511,7 @@ class _Ops:
             x2 = second["input"].reshape(-1, K)
             if x2.stride(-1) != 1:
                 x2 = x2.contiguous()
-            a.x2, a.M2, a.ldx2, a.split_rows = x2.data_ptr(), x2.shape[0], x2.stride(0), M
+            a.x2, a.M2, a.ldx2, a.split_rows = x2.data_ptr(), _i32(op, "second input rows", x2.shape[0]), _i32(op, "second input.stride(0)", x2.stride(0)), a.M
             sm2, ld2 = _param(second.get("smooth"), "vec"), _param(second.get("lora_down"), "down")
             a.smooth2, a.lora_down2 = _ptr(sm2), _ptr(ld2)
             a.ln_stats2, a.mod_scale2, a.mod_shift2 = _ptr(second.get("ln_stats")), _ptr(second.get("mod_scale")), _ptr(second.get("mod_shift"))
@@ -588,8 +609,8 @@ class _Ops:
         if lora_scales is not None and R:
             keep = (C.c_float * (R // 16))(*[float(s) for s in list(lora_scales)[: R // 16]])
             a.lora_scales = C.cast(keep, C.POINTER(C.c_float))
-        a.M_pad, a.N, a.K, a.R = M_pad, N, K, R
-        a.M = M_pad
+        a.M_pad, a.N, a.K, a.R = _i32("gemm_w4a4", "M_pad", M_pad), _i32("gemm_w4a4", "N", N), _i32("gemm_w4a4", "K", K), _i32("gemm_w4a4", "R", R)
+        a.M = a.M_pad
         a.dtype = _DT[ascales.dtype]
         a.act_unsigned = int(bool(act_unsigned))
         if _Ops.gemm_use_workspace:
@@ -606,7 +627,7 @@ class _Ops:
             smooth_factor = _param(smooth_factor, "vec")
             a.qout, a.oscales, a.next_smooth = _ptr(qout_img), _ptr(oscales), _ptr(smooth_factor)
             if lora_down is not None and lora_down.numel() > 0:
-                a.R2 = lora_down.shape[-1]
+                a.R2 = _i32("gemm_w4a4", "lora_down.shape[-1]", lora_down.shape[-1])
                 lora_down = _param(lora_down, "down")
                 a.next_lora_down, a.lora_act_out = _ptr(lora_down), _ptr(lora_act_out)
                 frag_down = _packed_fragments(lora_down, True, N, a.R2)
@@ -628,15 +649,15 @@ class _Ops:
                     raise ValueError("gemm_w4a4: out_vt must be a [N/3, tokens] view with unit column stride in the model dtype")
                 if not out_vt.is_cuda:
                     raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
-                a.out_vt, a.ldvt = out_vt.data_ptr(), out_vt.stride(0)
+                a.out_vt, a.ldvt = out_vt.data_ptr(), _i32("gemm_w4a4", "out_vt.stride(0)", out_vt.stride(0))
         elif out is not None:
             a.fuse = _lib.FUSE_SILU if fuse_silu else _lib.FUSE_NONE
         else:
             raise ValueError("gemm_w4a4: no output tensor given")
         if out is not None:
             a.out = _ptr(out)
-            a.M = out.numel() // out.shape[-1]
-            a.ldo = out.shape[-1]
+            a.M = _i32("gemm_w4a4", "out rows", out.numel() // out.shape[-1])
+            a.ldo = _i32("gemm_w4a4", "out.shape[-1]", out.shape[-1])
             if out.shape[-1] != N:
                 raise ValueError("gemm_w4a4: out.shape[-1] must equal N")
             if a.M > M_pad or M_pad - a.M >= 256:
@@ -658,7 +679,7 @@ class _Ops:
             a.next_lora_down_packed2 = _ptr(frag_down2)
             if a.next_lora_down_packed2 is None:
                 a.next_lora_down_packed = None  # (both sets or none)
-            a.split_rows = int(split_rows)
+            a.split_rows = _i32("gemm_w4a4", "split_rows", split_rows)
             keep2 = (second, conv)  # keeps the tensors alive until the launch has been issued
         if fmt_in is not None:
             if fmt_in not in (torch.float32, torch.int64):
@@ -793,7 +814,8 @@ class _Ops:
         a.bias, a.out = _ptr(bias), out.data_ptr()
         if not x2.is_cuda:
             raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
-        a.M, a.N, a.K, a.ldx = m, n, k, x2.stride(0) if m > 1 else k
+        a.M, a.N, a.K = _i32("gemv_awq", "m", m), _i32("gemv_awq", "n", n), _i32("gemv_awq", "k", k)
+        a.ldx = _i32("gemv_awq", "in_feats row stride", x2.stride(0) if m > 1 else k)
         a.group_size, a.dtype, a.out_chunks = group_size, _DT[in_feats.dtype], int(out_chunks)
         _lib.check(lib.svdq_gemv_awq(C.byref(a), _stream()), "gemv_awq")
         return out
@@ -830,7 +852,8 @@ class _Ops:
         a = _lib.GemmAwqArgs()
         a.x, a.qweight, a.scales, a.scaled_zeros = x2.data_ptr(), _ptr(kernel), _ptr(scaling_factors), _ptr(zeros)
         a.bias, a.out = _ptr(bias), out.data_ptr()
-        a.M, a.N, a.K, a.ldx = M, N, K, x2.stride(0) if M > 1 else K
+        a.M, a.N, a.K = _i32("gemm_awq", "M", M), _i32("gemm_awq", "N", N), _i32("gemm_awq", "K", K)
+        a.ldx = _i32("gemm_awq", "in_feats row stride", x2.stride(0) if M > 1 else K)
         a.group_size, a.dtype = 128, _DT[in_feats.dtype]
         if K % 128 == 0 and N % 64 == 0:  # (otherwise the library reports the shape)
             need = int(lib.svdq_gemm_awq_workspace_bytes(M, N, K))
@@ -863,7 +886,8 @@ class _Ops:
             outs.append(o.view(1, -1))
             a.x, a.qweight, a.scales, a.zeros = x.data_ptr(), _ptr(l.qweight), _ptr(l.wscales), _ptr(l.wzeros)
             a.bias, a.out = _ptr(l.bias), o.data_ptr()
-            a.M, a.N, a.K, a.ldx = 1, l.out_features, k, k
+            a.M, a.N = 1, _i32("gemv_awq_batched", "out_features", l.out_features)
+            a.K = a.ldx = _i32("gemv_awq_batched", "in_feats width", k)
             a.group_size, a.dtype, a.out_chunks = l.group_size, _DT[x.dtype], int(getattr(l, "out_chunks", 1))
         for s0 in range(0, len(layers), 80):
             n = min(80, len(layers) - s0)
@@ -899,7 +923,9 @@ class _Ops:
                 if t.dtype != x.dtype or t.device != x.device:
                     raise ValueError("gemv_awq_lora_batched: every tensor must have in_feats' dtype and device")
             a.x, a.down, a.up, a.out, a.t = x.data_ptr(), _ptr(lo.down), _ptr(lo.up), _ptr(out), _ptr(lo.t)
-            a.strength, a.r, a.N, a.K, a.dtype, a.out_chunks = float(lo.strength), r, n, k, _DT[x.dtype], int(chunks)
+            op = "gemv_awq_lora_batched"
+            a.strength, a.r, a.N, a.K = float(lo.strength), _i32(op, "r", r), _i32(op, "N", n), _i32(op, "K", k)
+            a.dtype, a.out_chunks = _DT[x.dtype], int(chunks)
         for s0 in range(0, len(entries), 80):
             n = min(80, len(entries) - s0)
             _lib.check(lib.svdq_gemv_awq_lora_batched(C.cast(C.byref(arr[s0]), C.POINTER(_lib.GemvLoraArgs)), n, _stream()), "gemv_awq_lora_batched")
@@ -950,10 +976,10 @@ class _Ops:
             raise ValueError("attention: expected q/k/out [L, H, D] and vt [H, D, L]")
         a = _lib.AttentionArgs()
         a.q, a.k, a.vt = q.data_ptr(), k.data_ptr(), vt.data_ptr()
-        a.ldq, a.q_hs = q.stride(0), q.stride(1)
-        a.ldk, a.k_hs = k.stride(0), k.stride(1)
+        a.ldq, a.q_hs = _i32("attention", "q.stride(0)", q.stride(0)), _i64("attention", "q.stride(1)", q.stride(1))
+        a.ldk, a.k_hs = _i32("attention", "k.stride(0)", k.stride(0)), _i64("attention", "k.stride(1)", k.stride(1))
         if out is not None:
-            a.out, a.ldo, a.o_hs = out.data_ptr(), out.stride(0), out.stride(1)
+            a.out, a.ldo, a.o_hs = out.data_ptr(), _i32("attention", "out.stride(0)", out.stride(0)), _i64("attention", "out.stride(1)", out.stride(1))
         if quant is not None:
             # extension: emit the following output projection's quantised activation directly (dict: act, ascales,
             # lora_act (pre-zeroed), smooth, lora_down, R [, smooth2, lora_down2, split_rows])
@@ -970,8 +996,8 @@ class _Ops:
             if fq is not None and (quant.get("lora_down2") is None or fq2 is not None):
                 a.qlora_down_packed, a.qlora_down_packed2 = _ptr(fq), _ptr(fq2)
             a.qsplit_rows = int(quant.get("split_rows", 0))
-        a.vt_hs, a.ldvt = vt.stride(0), vt.stride(1)
-        a.L, a.H, a.head_dim, a.dtype = L, H, D, _DT[q.dtype]
+        a.vt_hs, a.ldvt = _i64("attention", "vt.stride(0)", vt.stride(0)), _i32("attention", "vt.stride(1)", vt.stride(1))
+        a.L, a.H, a.head_dim, a.dtype = _i32("attention", "L", L), _i32("attention", "H", H), _i32("attention", "head_dim", D), _DT[q.dtype]
         a.scale = float(scale)
         a.q_prescaled = 1 if q_prescaled else 0  # Q already carries scale * log2(e) (gemm_w4a4(q_scale=...)): `scale` is not applied again
         if kv_valid is not None:
@@ -1021,8 +1047,9 @@ class _Ops:
                 raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
         a = _lib.IpAttentionArgs()
         a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
-        a.ldq, a.ldk, a.ldv, a.ldo = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
-        a.T, a.H, a.N, a.head_dim, a.dtype = T, H, k.shape[0], D, _DT[q.dtype]
+        a.ldq, a.ldk, a.ldv, a.ldo = (_i32("ip_attention", f"{n}.stride(0)", t.stride(0)) for n, t in (("q", q), ("k", k), ("v", v), ("out", out)))
+        a.T, a.H, a.N, a.head_dim = (_i32("ip_attention", n, val) for n, val in (("T", T), ("H", H), ("N", k.shape[0]), ("head_dim", D)))
+        a.dtype = _DT[q.dtype]
         a.q_prescaled, a.scale, a.out_scale = 1 if q_prescaled else 0, float(scale), float(out_scale)
         _lib.check(lib.svdq_ip_attention(C.byref(a), _stream()), "ip_attention")
 
@@ -1060,8 +1087,10 @@ class _Ops:
         a.x, a.stats, a.a_fold, a.colsum, a.cbias = x.data_ptr(), stats.data_ptr(), a_fold.data_ptr(), colsum.data_ptr(), cbias.data_ptr()
         a.b_fold, a.probs, a.out = b_fold.data_ptr(), probs.data_ptr(), out.data_ptr()
         a.acc, a.o_acc = (None if acc is None else acc.data_ptr()), (None if o_acc is None else o_acc.data_ptr())
-        a.ldx, a.ldo = (x.stride(0), out.stride(0)) if T > 1 else (Cw, Cw)  # (the stride of a one-row view means nothing)
-        a.T, a.C, a.H, a.N, a.dtype, a.out_scale = T, Cw, J // 32, int(n_tokens), _DT[x.dtype], float(out_scale)
+        ldx, ldo = (x.stride(0), out.stride(0)) if T > 1 else (Cw, Cw)  # (the stride of a one-row view means nothing)
+        a.ldx, a.ldo = _i32("pulid_ca", "x.stride(0)", ldx), _i32("pulid_ca", "out.stride(0)", ldo)
+        a.T, a.C, a.H, a.N = _i32("pulid_ca", "T", T), _i32("pulid_ca", "C", Cw), _i32("pulid_ca", "H", J // 32), _i32("pulid_ca", "n_tokens", n_tokens)
+        a.dtype, a.out_scale = _DT[x.dtype], float(out_scale)
         _lib.check(lib.svdq_pulid_ca(C.byref(a), _stream()), "pulid_ca")
 
     @staticmethod
@@ -1100,13 +1129,16 @@ class _Ops:
         if vk is not None and not vk.is_cuda:
             raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
         a = _lib.LinearAttentionArgs()
-        a.B, a.T, a.H, a.head_dim, a.dtype, a.eps = B, T, H, D, _DT[kv.dtype], float(eps)
+        op = "linear_attention"
+        a.B, a.T, a.H, a.head_dim = _i32(op, "B", B), _i32(op, "T", T), _i32(op, "H", H), _i32(op, "head_dim", D)
+        a.dtype, a.eps = _DT[kv.dtype], float(eps)
         # (the strides of dimensions of size 1 are arbitrary in torch: the library gets the natural ones)
         row = lambda t: t.stride(1) if T > 1 else H * t.shape[3]
-        a.kv, a.ldkv, a.kv_bs = kv.data_ptr(), row(kv), kv.stride(0) if B > 1 else 0
+        a.kv, a.ldkv, a.kv_bs = kv.data_ptr(), _i32(op, "kv row stride", row(kv)), _i64(op, "kv batch stride", kv.stride(0) if B > 1 else 0)
         if q is not None:
-            a.q, a.ldq, a.q_bs = views["q"].data_ptr(), row(views["q"]), views["q"].stride(0) if B > 1 else 0
-            a.out, a.ldo, a.out_bs = views["out"].data_ptr(), row(views["out"]), views["out"].stride(0) if B > 1 else 0
+            vq, vo = views["q"], views["out"]
+            a.q, a.ldq, a.q_bs = vq.data_ptr(), _i32(op, "q row stride", row(vq)), _i64(op, "q batch stride", vq.stride(0) if B > 1 else 0)
+            a.out, a.ldo, a.out_bs = vo.data_ptr(), _i32(op, "out row stride", row(vo)), _i64(op, "out batch stride", vo.stride(0) if B > 1 else 0)
         a.vk = None if vk is None else vk.data_ptr()
         need = int(lib.svdq_linear_attention_workspace_bytes(C.byref(a)))
         ws = _workspace(kv.device, "linear_attention", min_bytes=need)  # (a capture cannot grow the buffer: the library then names the size)
@@ -1143,14 +1175,15 @@ class _Ops:
         if bias is not None and not bias.is_contiguous():
             bias = bias.contiguous()
         a = _lib.Dwconv3x3Args()
-        a.B, a.H, a.W, a.C, a.dtype = B, H, W, Cc, _DT[x.dtype]
+        op = "dwconv3x3"
+        a.B, a.H, a.W, a.C, a.dtype = _i32(op, "B", B), _i32(op, "H", H), _i32(op, "W", W), _i32(op, "C", Cc), _DT[x.dtype]
 
         # (the strides of dimensions of size 1 are arbitrary in torch: the library gets the natural ones)
         def row(t):
             return t.stride(2) if W > 1 else t.stride(1) if H > 1 else Cc
 
-        a.x, a.ldx, a.x_bs = x.data_ptr(), row(x), x.stride(0) if B > 1 else 0
-        a.out, a.ldo, a.out_bs = out.data_ptr(), row(out), out.stride(0) if B > 1 else 0
+        a.x, a.ldx, a.x_bs = x.data_ptr(), _i32(op, "x pixel stride", row(x)), _i64(op, "x batch stride", x.stride(0) if B > 1 else 0)
+        a.out, a.ldo, a.out_bs = out.data_ptr(), _i32(op, "out pixel stride", row(out)), _i64(op, "out batch stride", out.stride(0) if B > 1 else 0)
         a.weight, a.bias = taps.data_ptr(), None if bias is None else bias.data_ptr()
         _lib.check(lib.svdq_dwconv3x3(C.byref(a), _stream()), "dwconv3x3")
         del taps
@@ -1188,9 +1221,12 @@ class _Ops:
         a = _lib.CrossAttentionArgs()
         a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
         a.key_offsets, a.key_counts = key_offsets.data_ptr(), key_counts.data_ptr()
-        a.ldq, a.ldo = row(q), row(out)
-        a.ldk, a.ldv = (k.stride(0), v.stride(0)) if k.shape[0] > 1 else (max(k.stride(0), H * D),) * 2
-        a.B, a.T, a.H, a.head_dim, a.Nrows, a.max_keys = B, T, H, D, k.shape[0], int(max_keys)
+        op = "cross_attention"
+        a.ldq, a.ldo = _i32(op, "q row stride", row(q)), _i32(op, "out row stride", row(out))
+        ldk, ldv = (k.stride(0), v.stride(0)) if k.shape[0] > 1 else (max(k.stride(0), H * D),) * 2
+        a.ldk, a.ldv = _i32(op, "k.stride(0)", ldk), _i32(op, "v.stride(0)", ldv)
+        a.B, a.T, a.H, a.head_dim = _i32(op, "B", B), _i32(op, "T", T), _i32(op, "H", H), _i32(op, "head_dim", D)
+        a.Nrows, a.max_keys = _i32(op, "k rows", k.shape[0]), _i32(op, "max_keys", max_keys)
         a.dtype, a.scale = _DT[q.dtype], float(scale)
         _lib.check(lib.svdq_cross_attention(C.byref(a), _stream()), "cross_attention")
 
@@ -1216,9 +1252,10 @@ class _Ops:
         a = _lib.AttentionD64Args()
         a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
         # (the strides of dimensions of size 1 are arbitrary in torch: the library gets the natural ones)
-        a.ldq, a.ldk, a.ldv, a.ldo = (t.stride(1) if t.shape[1] > 1 else H * D for t in (q, k, v, out))
-        a.q_bs, a.k_bs, a.v_bs, a.out_bs = (t.stride(0) if B > 1 else 0 for t in (q, k, v, out))
-        a.B, a.T, a.H, a.N, a.head_dim = B, T, H, N, D
+        op, named = "attention_d64", (("q", q), ("k", k), ("v", v), ("out", out))
+        a.ldq, a.ldk, a.ldv, a.ldo = (_i32(op, f"{n} row stride", t.stride(1) if t.shape[1] > 1 else H * D) for n, t in named)
+        a.q_bs, a.k_bs, a.v_bs, a.out_bs = (_i64(op, f"{n} batch stride", t.stride(0) if B > 1 else 0) for n, t in named)
+        a.B, a.T, a.H, a.N, a.head_dim = (_i32(op, n, val) for n, val in (("B", B), ("T", T), ("H", H), ("N", N), ("head_dim", D)))
         a.dtype, a.scale = _DT[q.dtype], float(scale)
         _lib.check(lib.svdq_attention_d64(C.byref(a), _stream()), "attention_d64")
 
@@ -1254,9 +1291,9 @@ class _Ops:
         args.res, args.a, args.out, args.out_mod = _ptr(res, True), _ptr(a, True), _ptr(out, True), _ptr(out_mod, True)
         args.timestep, args.gate_table, args.mod_table = _ptr(timestep, True), _ptr(gate_table, True), _ptr(mod_table, True)
         args.stats = _ptr(stats, True)
-        args.ld_res, args.ld_a, args.ld_out, args.ld_mod = lds
-        args.timestep_bs = 0 if timestep is None else timestep.stride(0) if B > 1 else 6 * C_feat
-        args.B, args.T, args.C, args.C_pad = M // T, int(T), int(C_feat), int(C_pad)
+        args.ld_res, args.ld_a, args.ld_out, args.ld_mod = (_i32(op, f"row stride of {n}", ld) for n, ld in zip(("res", "a", "out", "out_mod"), lds))
+        args.timestep_bs = _i64(op, "timestep.stride(0)", 0 if timestep is None else timestep.stride(0) if B > 1 else 6 * C_feat)
+        args.B, args.T, args.C, args.C_pad = _i32(op, "B", M // T), _i32(op, "T", T), _i32(op, "C", C_feat), _i32(op, "C_pad", C_pad)
         args.gate_row, args.scale_row, args.shift_row = int(gate_row), int(scale_row), int(shift_row)
         args.dtype, args.eps = _DT[dtype], float(eps)
         _lib.check(lib.svdq_sana_glue(C.byref(args), _stream()), op)
@@ -1289,11 +1326,11 @@ class _Ops:
         args.res, args.a, args.out, args.out_mod = _ptr(res, True), _ptr(a, True), _ptr(out, True), _ptr(out_mod, True)
         args.w_post, args.w_pre, args.gate, args.scale = _ptr(w_post), _ptr(w_pre), _ptr(gate, True), _ptr(scale, True)
         args.stats = _ptr(stats, True)
-        args.ld_res, args.ld_a, args.ld_out, args.ld_mod = lds
+        args.ld_res, args.ld_a, args.ld_out, args.ld_mod = (_i32(op, f"row stride of {n}", ld) for n, ld in zip(("res", "a", "out", "out_mod"), lds))
         # (the strides of dimensions of size 1 are arbitrary in torch: the library gets the natural ones)
-        args.gate_bs = 0 if gate is None else gate.stride(0) if B > 1 else C_feat
-        args.scale_bs = 0 if scale is None else scale.stride(0) if B > 1 else C_feat
-        args.M, args.T, args.C, args.dtype, args.eps = M, int(T), int(C_feat), _DT[dtype], float(eps)
+        args.gate_bs = _i64(op, "gate.stride(0)", 0 if gate is None else gate.stride(0) if B > 1 else C_feat)
+        args.scale_bs = _i64(op, "scale.stride(0)", 0 if scale is None else scale.stride(0) if B > 1 else C_feat)
+        args.M, args.T, args.C, args.dtype, args.eps = _i32(op, "M", M), _i32(op, "T", T), _i32(op, "C", C_feat), _DT[dtype], float(eps)
         _lib.check(lib.svdq_sandwich_norm(C.byref(args), _stream()), op)
 
     @staticmethod
@@ -1318,9 +1355,9 @@ class _Ops:
             raise ValueError(f"{op}: rstd must be a contiguous float32 [{T}, {2 * H}] tensor")
         args.qkv, args.norm_q, args.norm_k, args.freqs = _ptr(qkv, True), _ptr(norm_q), _ptr(norm_k), _ptr(freqs)
         args.vt, args.rstd = _ptr(vt, True), _ptr(rstd)
-        args.ld = qkv.stride(0) if qkv.shape[0] > 1 else max(qkv.stride(0), qkv.shape[1])
-        args.ldvt = 0 if vt is None else vt.stride(0) if vt.shape[0] > 1 else max(vt.stride(0), vt.shape[1])
-        args.T, args.L_pad, args.H, args.head_dim = int(T), int(L_pad), int(H), 128
+        args.ld = _i32(op, "qkv.stride(0)", qkv.stride(0) if qkv.shape[0] > 1 else max(qkv.stride(0), qkv.shape[1]))
+        args.ldvt = _i32(op, "vt.stride(0)", 0 if vt is None else vt.stride(0) if vt.shape[0] > 1 else max(vt.stride(0), vt.shape[1]))
+        args.T, args.L_pad, args.H, args.head_dim = _i32(op, "T", T), _i32(op, "L_pad", L_pad), _i32(op, "H", H), 128
         args.dtype, args.eps = _DT[qkv.dtype], float(eps)
         _lib.check(lib.svdq_qk_norm_rope(C.byref(args), _stream()), op)
 

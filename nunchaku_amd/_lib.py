@@ -221,6 +221,7 @@ class PulidCaArgs(C.Structure):
 
 EXPORTS = {
     "svdq_quantize_w4a4_act_fuse_lora": (C.c_int, [C.POINTER(QuantizeArgs), C.c_void_p]),
+    "svdq_quantize_plan": (C.c_int, [C.POINTER(QuantizeArgs), C.POINTER(C.c_int32)]),
     "svdq_gemm_w4a4": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
     "svdq_attention": (C.c_int, [C.POINTER(AttentionArgs), C.c_void_p]),
     "svdq_gemv_awq": (C.c_int, [C.POINTER(GemvAwqArgs), C.c_void_p]),

@@ -1232,6 +1232,12 @@ extern "C" int svdq_attention_last_plan(int32_t *out4) {
     return SVDQ_OK;
 }
 
+static constexpr long long ATT_REACH = 0xffffffffLL; // the largest 32-bit byte offset
+static constexpr int ATT_LDK_MAX = 33554424;         // the largest multiple of 8 with 128 ldk <= ATT_REACH
+static constexpr int ATT_LDVT_MAX = 16909312;        // the largest multiple of 8 with 254 ldvt + 112 <= ATT_REACH
+static_assert(128LL * ATT_LDK_MAX <= ATT_REACH && 128LL * (ATT_LDK_MAX + 8) > ATT_REACH && 126LL * ATT_LDK_MAX + 240 <= ATT_REACH, "ldk reach");
+static_assert(254LL * ATT_LDVT_MAX + 112 <= ATT_REACH && 254LL * (ATT_LDVT_MAX + 8) + 112 > ATT_REACH, "ldvt reach");
+
 extern "C" int svdq_attention(const svdq_attention_args *a, void *stream) {
     if (!a) { set_error("svdq_attention: args is NULL"); return SVDQ_E_INVALID; }
     if (!a->q || !a->k || !a->vt || (!a->out && !a->qact)) { set_error("svdq_attention: q, k, vt and out (or qact) are required"); return SVDQ_E_INVALID; }
@@ -1262,6 +1268,10 @@ extern "C" int svdq_attention(const svdq_attention_args *a, void *stream) {
         set_error("svdq_attention: strides must be multiples of 8 elements, ldq/ldk/ldo >= 128 and ldvt >= L");
         return SVDQ_E_INVALID;
     }
+    // addressing reach: the K / V^T staging offsets are 32-bit byte offsets from a wave-uniform tile base -- key row 63 of a K tile
+    // (126 ldk + 240), the geometry-2 loop's tile stride (128 ldk, a scalar register), channel row 127 of a V^T tile (254 ldvt + 112).  Everything else is 64-bit.
+    if (128LL * a->ldk > ATT_REACH) { set_error("svdq_attention: ldk=%d is beyond the kernel's addressing reach (at most %d)", a->ldk, ATT_LDK_MAX); return SVDQ_E_UNSUPPORTED; }
+    if (254LL * a->ldvt + 112 > ATT_REACH) { set_error("svdq_attention: ldvt=%d is beyond the kernel's addressing reach (at most %d)", a->ldvt, ATT_LDVT_MAX); return SVDQ_E_UNSUPPORTED; }
     if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->vt | (uintptr_t)a->out) & 15) { set_error("svdq_attention: q, k, vt, out must be 16-byte aligned"); return SVDQ_E_INVALID; }
     if (a->dtype != SVDQ_BF16 && a->dtype != SVDQ_FP16) { set_error("svdq_attention: unknown dtype %d", a->dtype); return SVDQ_E_INVALID; }
     if (a->zero_ptr && (a->zero_bytes < 0 || a->zero_bytes % 16 || ((uintptr_t)a->zero_ptr & 15))) {

@@ -1813,7 +1813,15 @@ static int auto_geometry(const svdq_gemm_args *a, bool with_ws, int cus) {
     return (use1 < 0.9 && tiles2 >= 4 * cus) ? 2 : 1;
 }
 // geometry 8's kernel: the 128 x 64 wave tile (FUSE_NONE, rank <= 32, fp32 low-rank accumulators); schedule and stream-K split as the 256 x 128 geometry's
-static bool wt128_serves(const svdq_gemm_args *a) { return a->fuse == SVDQ_FUSE_NONE && a->lora_act_format == SVDQ_LORA_ACT_F32 && (a->R == 32 || a->R == 0); }
+// (addressing reach, DESIGN.md section 7: the wave-tile epilogue's stores take a 32-bit byte offset from the wave's first row -- row 127 of its 128 is 254 ldo + 16
+// bytes away; a launch with a wider out takes the 8-wave kernel, whose row addresses are 64-bit)
+static constexpr int GEMM_LDVT_MAX = 429496716; // the largest even ldvt with 10 ldvt + 124 <= 0xffffffff (the QKV epilogue's out_vt)
+static_assert(10LL * GEMM_LDVT_MAX + 124 <= 0xffffffffLL && 10LL * (GEMM_LDVT_MAX + 2) + 124 > 0xffffffffLL, "ldvt reach of the QKV epilogue");
+static constexpr int WT128_LDO_MAX = 16909316; // the largest multiple of 4 with 254 ldo + 16 <= 0xffffffff
+static_assert(254LL * WT128_LDO_MAX + 16 <= 0xffffffffLL && 254LL * (WT128_LDO_MAX + 4) + 16 > 0xffffffffLL, "ldo reach of the wave-tile kernel");
+static bool wt128_serves(const svdq_gemm_args *a) {
+    return a->fuse == SVDQ_FUSE_NONE && a->lora_act_format == SVDQ_LORA_ACT_F32 && (a->R == 32 || a->R == 0) && a->ldo <= WT128_LDO_MAX;
+}
 
 // The plan of a launch whose arguments passed validate_gemm_args, on `cus` compute units (the launch: device_cus()).
 static GemmPlan plan_gemm(const svdq_gemm_args *a, int cus) {
@@ -2164,6 +2172,11 @@ static int validate_gemm_args(const svdq_gemm_args *a) {
     case SVDQ_FUSE_RMSNORM_ROPE:
         if (!a->out || !a->norm_q || !a->norm_k || !a->rotary_emb) { set_error("svdq_gemm_w4a4: RMSNORM_ROPE needs out, norm_q, norm_k and rotary_emb"); return SVDQ_E_INVALID; }
         if (a->N % 384) { set_error("svdq_gemm_w4a4: RMSNORM_ROPE needs N=%d to be a multiple of 3*128", a->N); return SVDQ_E_INVALID; }
+        // (addressing reach, DESIGN.md section 7: the V^T stores' lane offset is a 32-bit byte offset, channel row 5 of a piece plus 62 tokens = 10 ldvt + 124)
+        if (a->out_vt && 10LL * a->ldvt + 124 > 0xffffffffLL) {
+            set_error("svdq_gemm_w4a4: ldvt=%d is beyond the kernel's addressing reach (at most %d)", a->ldvt, GEMM_LDVT_MAX);
+            return SVDQ_E_UNSUPPORTED;
+        }
         if (a->out_vt && (a->ldvt < a->M || a->ldvt % 2 || ((uintptr_t)a->out_vt & 3))) {
             set_error("svdq_gemm_w4a4: out_vt needs an even ldvt=%d >= M=%d and a 4-byte aligned pointer", a->ldvt, a->M);
             return SVDQ_E_INVALID;

@@ -639,32 +639,61 @@ __global__ __launch_bounds__(256, MULTI ? 2 : 4) void quantize_kernel_v2(QuantPa
     }
 }
 
-template <int DT>
-static int launch_quantize(const svdq_quantize_args *a, hipStream_t st) {
-    using T = typename Half<DT>::T;
+// What a launch takes -- the one place that decides it; svdq_quantize_w4a4_act_fuse_lora and svdq_quantize_plan read it.  Pure: no HIP call, no state.
+struct QuantPlan {
+    int fast;    // 1: quantize_kernel_v2 (reads x through a buffer descriptor with 32-bit byte offsets), 0: quantize_kernel (64-bit row addresses)
+    int sel;     // fast: the quantize_kernel_v2 switch set (bit 0 smooth, 1 LayerNorm front end, 2 low rank, 3 rank > 32); general: the rank class RT (0, 1, 2, 4, 8)
+    int cpw, slices;
+    int atomics; // lora_act_add mode: bit 0 = K is sliced over workgroups, bit 1 = Q31.32 format
+    int grid, glu;
+    int memset;  // the launch clears lora_act first
+};
+
+static QuantPlan quantize_plan(const svdq_quantize_args *a) {
+    QuantPlan pl{};
     const int KP = a->K / 128, tiles = a->M_pad / 32;
     // enough workgroups to fill 256 CUs several times over, but at least one chunk per wave
     int cpw = 4; // chunks per workgroup = 4 waves x 1 chunk: many short waves hide the HBM round trip
     // (the doubling ends at cpw >= KP: one slice per row tile is all there is to merge -- beyond 8192 row tiles, M_pad > 262144, the grid is simply larger)
     while (cpw < KP && (long)tiles * ((KP + cpw - 1) / cpw) > 8192) cpw *= 2;
     if (cpw > KP) cpw = ((KP + 3) / 4) * 4;
-    const int slices = (KP + cpw - 1) / cpw;
+    pl.cpw = cpw;
+    pl.slices = (KP + cpw - 1) / cpw;
     const int q32 = a->lora_act_format == SVDQ_LORA_ACT_Q32 || a->lora_act_format == SVDQ_LORA_ACT_Q32_RUNS;
-    const int atomics = (slices > 1 ? 1 : 0) | (q32 ? 2 : 0); // lora_act_add mode
-    if (a->R > 0 && (atomics & 1) && !a->lora_act_zeroed) {
+    pl.atomics = (pl.slices > 1 ? 1 : 0) | (q32 ? 2 : 0);
+    pl.memset = a->R > 0 && (pl.atomics & 1) && !a->lora_act_zeroed;
+    pl.grid = tiles * pl.slices;
+    pl.glu = a->fuse_glu ? 1 : 0;
+    // the fast kernel's reach: every byte offset into x (row < M_pad) and into lora_down fits the descriptor's 31 bits; a launch beyond it takes the general kernel
+    pl.fast = !a->fuse_glu && a->R <= 160 && cpw == 4 && (long long)a->M_pad * (a->ldx > a->ldx2 ? a->ldx : a->ldx2) * 2 < 0x7fffffffLL &&
+              (long long)a->R * a->K * 2 < 0x7fffffffLL;
+    if (pl.fast) {
+        pl.sel = (a->R > 32 ? 8 : 0) | (a->R > 0 ? 4 : 0) | (a->ln_stats ? 2 : 0) | (a->smooth ? 1 : 0); // (rank > 160: the general kernel, above)
+    } else {
+        const int rt32 = (a->R + 31) / 32;
+        pl.sel = rt32 == 0 ? 0 : rt32 <= 1 ? 1 : rt32 <= 2 ? 2 : rt32 <= 4 ? 4 : 8;
+    }
+    return pl;
+}
+
+template <int DT>
+static int launch_quantize(const svdq_quantize_args *a, hipStream_t st) {
+    using T = typename Half<DT>::T;
+    const QuantPlan pl = quantize_plan(a);
+    const int cpw = pl.cpw, atomics = pl.atomics;
+    const int q32 = (atomics & 2) != 0;
+    if (pl.memset) {
         // the reference zeroes the buffer inside the op as well (launch_impl.cuh:487)
         int rc = hip_check(hipMemsetAsync(a->lora_act, 0, (size_t)a->M_pad * a->R * (q32 ? 8 : 4), st), "svdq_quantize memset");
         if (rc) return rc;
     }
-    dim3 grid(tiles * slices), block(256);
-    const int rt32 = (a->R + 31) / 32;
+    dim3 grid(pl.grid), block(256);
     QuantSecond s2{a->x2, a->smooth2, a->lora_down2, a->mod_scale2, a->mod_shift2, a->ln_stats2, a->M2, a->ldx2, a->split_rows};
-    if (!a->fuse_glu && a->R <= 160 && cpw == 4 && (long long)a->M_pad * (a->ldx > a->ldx2 ? a->ldx : a->ldx2) * 2 < 0x7fffffffLL && (long long)a->R * a->K * 2 < 0x7fffffffLL) {
+    if (pl.fast) {
         // fast path: one chunk per wave, 4 waves = 4 neighbouring chunks of one row tile (same grid as the general kernel at cpw = 4)
         QuantParams qp{a->x, a->smooth, a->lora_down, a->mod_scale, a->mod_shift, a->ln_stats, (uint8_t *)a->act, a->ascales, a->lora_act,
                        a->M, a->K, a->R, a->ldx, atomics, s2};
-        const int sel = (a->R > 32 ? 8 : 0) | (a->R > 0 ? 4 : 0) | (a->ln_stats ? 2 : 0) | (a->smooth ? 1 : 0); // (rank > 160: the general kernel, above)
-        switch (sel) {
+        switch (pl.sel) {
 #define SVDQ_QV2(n, LORA, LN, SM, MULTI) case n: hipLaunchKernelGGL((quantize_kernel_v2<DT, LORA, LN, SM, MULTI>), grid, block, 0, st, qp); break;
             SVDQ_QV2(0, false, false, false, false) SVDQ_QV2(1, false, false, true, false) SVDQ_QV2(2, false, true, false, false) SVDQ_QV2(3, false, true, true, false)
             SVDQ_QV2(4, true, false, false, false) SVDQ_QV2(5, true, false, true, false) SVDQ_QV2(6, true, true, false, false) SVDQ_QV2(7, true, true, true, false)
@@ -678,11 +707,13 @@ static int launch_quantize(const svdq_quantize_args *a, hipStream_t st) {
                        (const T *)a->lora_down, (uint8_t *)a->act, (T *)a->ascales, a->lora_act, a->M, a->K, a->R,    \
                        a->ldx, cpw, atomics, a->ln_stats, (const T *)a->mod_scale, (const T *)a->mod_shift, s2)
 #define SVDQ_LAUNCH_Q(RT) do { if (a->fuse_glu) SVDQ_LAUNCH_QG(RT, true); else SVDQ_LAUNCH_QG(RT, false); } while (0)
-    if (rt32 == 0) SVDQ_LAUNCH_Q(0);
-    else if (rt32 <= 1) SVDQ_LAUNCH_Q(1);
-    else if (rt32 <= 2) SVDQ_LAUNCH_Q(2);
-    else if (rt32 <= 4) SVDQ_LAUNCH_Q(4);
-    else SVDQ_LAUNCH_Q(8);
+    switch (pl.sel) {
+    case 0: SVDQ_LAUNCH_Q(0); break;
+    case 1: SVDQ_LAUNCH_Q(1); break;
+    case 2: SVDQ_LAUNCH_Q(2); break;
+    case 4: SVDQ_LAUNCH_Q(4); break;
+    default: SVDQ_LAUNCH_Q(8); break;
+    }
 #undef SVDQ_LAUNCH_Q
 #undef SVDQ_LAUNCH_QG
     return hip_check(hipGetLastError(), "svdq_quantize_w4a4_act_fuse_lora launch");
@@ -692,7 +723,8 @@ static int launch_quantize(const svdq_quantize_args *a, hipStream_t st) {
 
 using namespace svdq;
 
-extern "C" int svdq_quantize_w4a4_act_fuse_lora(const svdq_quantize_args *a, void *stream) {
+// what svdq_quantize_w4a4_act_fuse_lora refuses, and svdq_quantize_plan with it
+static int validate_quantize_args(const svdq_quantize_args *a) {
     if (!a) { set_error("svdq_quantize: args is NULL"); return SVDQ_E_INVALID; }
     if (a->fp4) { set_error("svdq_quantize: fp4 (NVFP4) is not supported on gfx950"); return SVDQ_E_UNSUPPORTED; }
     if (a->fuse_glu && (a->ln_stats || a->x2)) { set_error("svdq_quantize: fuse_glu does not combine with the LayerNorm front end or a grouped launch"); return SVDQ_E_INVALID; }
@@ -745,6 +777,20 @@ extern "C" int svdq_quantize_w4a4_act_fuse_lora(const svdq_quantize_args *a, voi
             return SVDQ_E_INVALID;
         }
     }
+    return SVDQ_OK;
+}
+
+extern "C" int svdq_quantize_plan(const svdq_quantize_args *a, int32_t *out8) {
+    if (!out8) { set_error("svdq_quantize_plan: out is required"); return SVDQ_E_INVALID; }
+    if (int rc = validate_quantize_args(a)) return rc;
+    const QuantPlan pl = quantize_plan(a);
+    out8[0] = pl.fast ? 0 : 1; out8[1] = pl.sel; out8[2] = pl.cpw; out8[3] = pl.slices;
+    out8[4] = pl.atomics; out8[5] = pl.grid; out8[6] = pl.glu; out8[7] = pl.memset;
+    return SVDQ_OK;
+}
+
+extern "C" int svdq_quantize_w4a4_act_fuse_lora(const svdq_quantize_args *a, void *stream) {
+    if (int rc = validate_quantize_args(a)) return rc;
     hipStream_t st = (hipStream_t)stream;
     // algorithmic bytes: x in, codes + scales + lora_act out, lora_down in (once)
     const double bytes = (double)(a->M + (a->x2 ? a->M2 : 0)) * a->K * (a->fuse_glu ? 4 : 2) + (double)a->M_pad * a->K * 3 / 4 + (double)a->M_pad * (a->K / 64) * 2 +

@@ -7,10 +7,10 @@ built library holds.
   ``ops.attention_last_plan()`` report that key: the claim is witnessed by the dispatch code itself.  (A GEMM key needs no launch to be read:
   ``svdq_gemm_plan`` answers from the same ``plan_gemm`` without a GPU, and tests/test_gemm_plan.py pins its answers there; here the key is
   read off the launch whose output is checked.)
-* The quantiser has no plan query.  Its rows state their instantiation through ``quant_instantiation`` below, a restatement of the rule in
-  csrc/quantize.hip (``launch_quantize``).  That restatement is this ledger's limit, as ``CLASS_RULES`` is the limit of tests/test_dispatch_ledger.py:
-  if the launcher changes its rule and the restatement is not changed with it, a row is counted for a kernel it no longer launches.  The same holds for
-  the 4- / 8-wave choice of attention_kernel (``L % 256``), which the attention plan does not report.
+* The quantiser's rows state their instantiation through ``quant_instantiation`` below, which asks ``svdq_quantize_plan``: the host function
+  ``quantize_plan`` of csrc/quantize.hip, which ``launch_quantize`` consumes and beside which it decides nothing.  What
+  remains restated here is the 4- / 8-wave choice of attention_kernel (``L % 256``), which the attention plan does not report: if the launcher changes
+  that rule and the table is not changed with it, a row is counted for a kernel it no longer launches.
 """
 import functools
 import math
@@ -105,25 +105,53 @@ QUANT_CASES = tuple(
 )
 
 
+def quant_plan(R, smooth, ln, glu, grouped, fmt, M, K, M_pad, ldx=None, ldx2=None) -> dict:
+    """``svdq_quantize_plan`` for a launch of this shape: what ``launch_quantize`` consumes (csrc/quantize.hip, ``quantize_plan``), from the library itself, host
+    only.  The addresses are made up (aligned, never dereferenced: the query validates and decides, nothing else).  ``grouped``: 256 rows of the first stream,
+    the rest in a second one, as ``test_quantize_case`` launches it.  ``ldx`` / ``ldx2``: row strides of the inputs (default: contiguous)."""
+    import ctypes as C
+
+    from nunchaku_amd import _lib
+
+    a, base = _lib.QuantizeArgs(), 1 << 20
+    a.x, a.act, a.ascales = base, 2 * base, 3 * base
+    a.smooth = 4 * base if smooth else None
+    a.lora_down, a.lora_act = (5 * base, 6 * base) if R else (None, None)
+    if ln:
+        a.ln_stats, a.mod_scale, a.mod_shift = 7 * base, 8 * base, 9 * base
+    a.M, a.M_pad, a.K, a.R = (256 if grouped else M), M_pad, K, R
+    a.ldx = (2 * K if glu else K) if ldx is None else ldx
+    a.fuse_glu = int(glu)
+    a.lora_act_format = {"f32": _lib.LORA_ACT_F32, "q32": _lib.LORA_ACT_Q32}[fmt]
+    if grouped:
+        a.x2, a.M2, a.ldx2, a.split_rows = 10 * base, M - 256, (K if ldx2 is None else ldx2), 256
+        a.smooth2 = 11 * base if smooth else None
+        a.lora_down2 = 12 * base if R else None
+        if ln:
+            a.ln_stats2, a.mod_scale2, a.mod_shift2 = 13 * base, 14 * base, 15 * base
+    out = (C.c_int32 * 8)()
+    lib = _lib.load()
+    rc = lib.svdq_quantize_plan(C.byref(a), out)
+    assert rc == 0, (rc, lib.svdq_last_error().decode())
+    return {"family": ("fast", "general")[out[0]], "sel": out[1], "cpw": out[2], "slices": out[3], "lora_act_add": out[4], "grid": out[5], "glu": bool(out[6]),
+            "memset": bool(out[7])}
+
+
 def quant_grid(M_pad: int, K: int):
-    """(chunks per workgroup, K slices) of launch_quantize"""
-    KP, tiles, cpw = K // 128, M_pad // 32, 4
-    while cpw < KP and tiles * math.ceil(KP / cpw) > 8192:
-        cpw *= 2
-    if cpw > KP:
-        cpw = (KP + 3) // 4 * 4
-    return cpw, math.ceil(KP / cpw)
+    """(chunks per workgroup, K slices) of launch_quantize, as the library's plan states them (they depend on M_pad and K alone)"""
+    pl = quant_plan(0, False, False, False, False, "f32", M_pad, K, M_pad)
+    return pl["cpw"], pl["slices"]
 
 
 def quant_instantiation(case):
-    """The restated rule: ("quantize_kernel_v2", (LORA, LN, SMOOTH, MULTI)) on the fast path -- no GLU, rank <= 160, four chunks per workgroup -- else
-    ("quantize_kernel", (RT32 class of ceil(R / 32), 1, GLU))"""
-    R, smooth, ln, glu, _, _, M, K, pad = case
-    cpw, _ = quant_grid(math.ceil(M / pad) * pad, K)
-    if not glu and R <= 160 and cpw == 4:
-        return "quantize_kernel_v2", (int(R > 0), int(ln), int(smooth), int(R > 32))
-    rt = math.ceil(R / 32)
-    return "quantize_kernel", (0 if rt == 0 else 1 if rt <= 1 else 2 if rt <= 2 else 4 if rt <= 4 else 8, 1, int(glu))
+    """The instantiation ``svdq_quantize_plan`` names for a row: ("quantize_kernel_v2", (LORA, LN, SMOOTH, MULTI)) for the fast family, its switch set spelt
+    out; ("quantize_kernel", (RT32 class, 1, GLU)) for the general one"""
+    R, smooth, ln, glu, grouped, fmt, M, K, pad = case
+    pl = quant_plan(R, smooth, ln, glu, grouped, fmt, M, K, math.ceil(M / pad) * pad)
+    sel = pl["sel"]
+    if pl["family"] == "fast":
+        return "quantize_kernel_v2", (sel >> 2 & 1, sel >> 1 & 1, sel & 1, sel >> 3 & 1)
+    return "quantize_kernel", (sel, 1, int(pl["glu"]))
 
 
 # ---- the attention table --------------------------------------------------------------------------------------------------------------

@@ -3,10 +3,11 @@ activation quantiser and attention that the built library holds (kernel names in
 names only, no instruction is looked at) against the instantiations the case tables of tests/test_gpu_hot_instantiations.py claim.  Whoever adds an
 instantiation gets a failing test that names the one without a case; whoever drops a table row gets one that names the instantiation left unlaunched.
 
-Its limit: GEMM and attention rows are witnessed by the library (every launch asserts the plan it reports; the GEMM's plan is the host function plan_gemm,
-which svdq_gemm_plan also answers without a GPU: tests/test_gemm_plan.py), the quantiser rows are not -- they go
-through ``quant_instantiation``, a restatement of launch_quantize's rule (csrc/quantize.hip), and the 4- / 8-wave attention kernels through ``L % 256``.
-If a launcher changes such a rule and the restatement is not changed with it, the ledger reports "reached" for a kernel the tables no longer launch."""
+GEMM, quantiser and attention rows are witnessed by the library: every GEMM and attention launch asserts the plan it reports (the GEMM's plan is the host
+function plan_gemm, which svdq_gemm_plan also answers without a GPU: tests/test_gemm_plan.py), and the quantiser rows ask svdq_quantize_plan, the host function
+launch_quantize consumes (``quant_instantiation``; tests/test_addressing_reach.py pins its answers around the fast kernel's 2 GiB rule).  Its limit: the
+4- / 8-wave attention kernels go through ``L % 256``, a restatement; if the launcher changes that rule and the table is not changed with it, the ledger reports
+"reached" for a kernel the tables no longer launch."""
 import math
 import os
 import re
