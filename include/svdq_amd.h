@@ -196,7 +196,11 @@ typedef struct svdq_gemm_args {
      * One workspace must never be used by launches that can be in flight concurrently (two streams, two
      * threads on different streams): keep one per (device, stream), as nunchaku_amd/_C.py does.  A violated
      * contract cannot hang the GPU -- an owner's wait is bounded -- but it invalidates the results; it is
-     * reported by svdq_gemm_workspace_status(). */
+     * reported by svdq_gemm_workspace_status().
+     * Only the header -- the first 8192 bytes: arrival counters, error word, ticket counters -- needs the one-time zero fill, and every
+     * launch leaves all of it at zero.  The bytes behind it (partial-tile slabs, packed low-rank images, the split's 16-bit image) need no
+     * initialisation: a launch reads none it did not write itself, so they may hold anything, NaN patterns and the leftovers of a launch
+     * of another shape, geometry or epilogue included (tests/test_gpu_workspace_hygiene.py). */
     void *workspace;
     int64_t workspace_bytes;
     /* SVDQ_FUSE_RMSNORM_ROPE only, optional: the V third of the output (columns [2N/3, N)) is written
@@ -360,7 +364,10 @@ typedef struct svdq_attention_args {
      * KV tiles of all tasks dealt evenly, partial (O, m, l) exchanged through this buffer.  Same contract as
      * svdq_gemm_args.workspace: never shared by launches that can be in flight concurrently; a waiting workgroup gives up
      * after ~1 s and raises the error word svdq_attention_workspace_status() reports.  NULL (or too small): plain grid.
-     * Results of the two schedules differ by fp32 summation order only. */
+     * Results of the two schedules differ by fp32 summation order only.
+     * Only the header -- the first 4096 bytes: arrival counters and the error word -- needs the one-time zero fill, and every launch leaves
+     * all of it at zero.  The bytes behind it (contributor and stash slabs, the split quantiser's packed factor and row image) need no
+     * initialisation: a launch reads none it did not write itself (tests/test_gpu_workspace_hygiene.py). */
     void *workspace;
     int64_t workspace_bytes;
     int32_t qlora_act_format; /* SVDQ_LORA_ACT_F32 | SVDQ_LORA_ACT_Q32 (deterministic head sum) */

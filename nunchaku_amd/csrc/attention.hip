@@ -312,10 +312,13 @@ __device__ __forceinline__ void finish_rows(const AttnParams &p, const v16f (&o)
             for (int dt = 0; dt < 4; dt++)
 #pragma unroll
                 for (int qq = 0; qq < 2; qq++) {
-                    V8 gv;
+                    // (rounded as pack2_scaled rounds the 16-bit output, like the A operand of lowrank_pass below: written `f2h<T>(o * inv)` the fp16 build rounds
+                    //  the fp32 product a second time, and the contraction then read rows one fp16 step from the kernel's own output on ~1e-4 of the elements --
+                    //  fp16 qlora_act of the split 1.20x outside the quantiser rows' bound, tests/test_gpu_workspace_hygiene.py.  bf16: the same bits either way.)
+                    unsigned gp[4];
 #pragma unroll
-                    for (int j = 0; j < 8; j++) gv[j] = f2h<T>(o[dt][qq * 8 + j] * inv);
-                    a16[(dt * 2 + qq) * 64] = gv;
+                    for (int j = 0; j < 4; j++) gp[j] = pack2_scaled<DT>(o[dt][qq * 8 + 2 * j], o[dt][qq * 8 + 2 * j + 1], inv);
+                    a16[(dt * 2 + qq) * 64] = __builtin_bit_cast(V8, v4i{(int)gp[0], (int)gp[1], (int)gp[2], (int)gp[3]});
                 }
         } else {
         if (p.qR > 0) lowrank_pass(0);                                     // (straight-line, as in rounds 2-4: the rank-32 step runs exactly this)
