@@ -99,8 +99,8 @@ typedef struct svdq_quantize_args {
     const void *smooth;    /* [K] 16-bit, natural order (see svdq_repack_vec); NULL = ones    */
     const void *lora_down; /* [K*R] 16-bit in svdq_repack_lowrank(down=1) order; NULL if R==0 */
     void *act;             /* out: FP6 image of the int4 codes, M_pad*K*3/4 bytes            */
-    void *ascales;         /* out: (K/64)*M_pad 16-bit                                        */
-    void *lora_act;        /* out: M_pad*R fp32 -- or int64, see lora_act_format -- (zeroed + accumulated inside the call) */
+    void *ascales;         /* out: (K/64)*M_pad 16-bit, 2-byte aligned (svdq_gemm_w4a4 reads it 16-byte aligned) */
+    void *lora_act;        /* out: M_pad*R fp32 -- or int64, see lora_act_format -- (zeroed + accumulated inside the call); 4-byte aligned, 8-byte as int64 */
     int32_t M;             /* actual rows                                                     */
     int32_t M_pad;         /* multiple of 256, >= M                                           */
     int32_t K;             /* multiple of 128                                                 */
@@ -132,6 +132,15 @@ typedef struct svdq_quantize_args {
     int32_t reserved;
 } svdq_quantize_args;
 
+/* Alignment of the operands of svdq_quantize_w4a4_act_fuse_lora ("Alignment").  A pointer or stride that is no multiple of its line is
+ * refused with SVDQ_E_INVALID before anything is launched; NULL counts as aligned.  tests/test_alignment_contract.py holds the widest access behind every line:
+ *   act                                                         16 bytes
+ *   x, smooth, lora_down, ln_stats, mod_scale, mod_shift        8 bytes (x: 16 with fuse_glu)
+ *   x2, smooth2, lora_down2, ln_stats2, mod_scale2, mod_shift2  8 bytes
+ *   lora_act                                                    4 bytes in fp32, 8 in the Q31.32 formats
+ *   ascales                                                     2 bytes
+ *   ldx, ldx2                                                   4 elements (ldx: 8 with fuse_glu)
+ * The fast kernel fetches lora_down(2) in 16-byte pieces by LDS-DMA, from 8-byte addresses where the caller passes one (section 7 says what was observed). */
 /* Addressing reach ("Addressing reach"; refused or re-routed on the host, never wrapped on the device):
  *   ldx, ldx2           unbounded: the general kernel forms row addresses in 64 bits.  The fast kernel reads x through a buffer descriptor with 32-bit byte
  *                       offsets; a launch takes it only while M_pad * max(ldx, ldx2) * 2 < 0x7fffffff and R * K * 2 < 0x7fffffff (svdq_quantize_plan)
@@ -168,7 +177,7 @@ typedef struct svdq_gemm_args {
     void *out;                /* [M, N] 16-bit, row stride ldo; required unless GELU_QUANT     */
     /* SVDQ_FUSE_GELU_QUANT: this layer emits the NEXT layer's quantized activation */
     void *qout;               /* FP6 image of the uint4 codes, M_pad*N*3/4 bytes               */
-    void *oscales;            /* (N/64)*M_pad 16-bit, scale image                              */
+    void *oscales;            /* (N/64)*M_pad 16-bit, scale image, 2-byte aligned              */
     const void *next_smooth;  /* [N] 16-bit natural order                                      */
     const void *next_lora_down; /* [N*R2] 16-bit, svdq_repack_lowrank(down=1) order, or NULL   */
     void *lora_act_out;       /* M_pad*R2 fp32 (or int64, see lora_act_format); MUST be zeroed by the caller on the
@@ -257,6 +266,17 @@ typedef struct svdq_gemm_args {
     const void *lora_up_packed;
 } svdq_gemm_args;
 
+/* Alignment of the operands of svdq_gemm_w4a4 ("Alignment").  A pointer or stride that is no multiple of its line is
+ * refused with SVDQ_E_INVALID before anything is launched; NULL counts as aligned.  tests/test_alignment_contract.py holds the widest access behind every line:
+ *   act, wgt, ascales, wscales, lora_act_in, lora_up, qout, rotary_emb, workspace            16 bytes
+ *   wgt2, wscales2, lora_up2, lora_up_packed, next_lora_down_packed, next_lora_down_packed2  16 bytes
+ *   out, bias, next_smooth, next_lora_down, lora_act_out, norm_q, norm_k                     8 bytes
+ *   bias2, next_smooth2, next_lora_down2, norm_q2, norm_k2                                   8 bytes
+ *   out_vt, status                                                                           4 bytes
+ *   oscales                                                                                  2 bytes
+ *   ldo                                                                                      4 elements: every row of out starts on 8 bytes
+ *   ldvt                                                                                     2 elements: every row of out_vt starts on 4 bytes
+ * lora_scales is a HOST pointer to floats.  out is stored in 16-byte pieces, at 8-byte addresses where out or ldo put a row there (section 7). */
 /* Addressing reach ("Addressing reach"):
  *   ldo                 unbounded.  The wave-tile kernel's epilogue stores take a 32-bit byte offset (254 * ldo + 16 over a wave's 128 rows): it serves
  *                       ldo <= 16909316; a launch with a wider out takes the 8-wave kernel (64-bit row addresses); svdq_gemm_plan answers which
@@ -353,8 +373,8 @@ typedef struct svdq_attention_args {
      * bytes: a contraction kernel behind the attention kernel, ABI 20), and qlora_act zeroed by the caller on this stream.
      * Rows >= qsplit_rows (a multiple of 256; 0 = off) use qsmooth2 / qlora_down2 (joint attention: text rows first). */
     void *qact;               /* FP6 image, L * (H*128) * 3/4 bytes                                 */
-    void *qscales;            /* scale image, (H*128/64) * L 16-bit                                 */
-    void *qlora_act;          /* [L, R] fp32 (or int64: qlora_act_format), pre-zeroed               */
+    void *qscales;            /* scale image, (H*128/64) * L 16-bit, 2-byte aligned                 */
+    void *qlora_act;          /* [L, R] fp32 (or int64: qlora_act_format), pre-zeroed; 4-byte aligned, 8-byte as int64 */
     const void *qsmooth, *qlora_down;   /* [H*128] natural; [R][H*128] rank-major (svdq_repack_lowrank(down=1)) */
     const void *qsmooth2, *qlora_down2;
     int32_t qR, qsplit_rows;
@@ -397,6 +417,14 @@ typedef struct svdq_attention_args {
     const void *qlora_down_packed, *qlora_down_packed2;
 } svdq_attention_args;
 
+/* Alignment of the operands of svdq_attention ("Alignment").  A pointer or stride that is no multiple of its line is
+ * refused with SVDQ_E_INVALID before anything is launched; NULL counts as aligned.  tests/test_alignment_contract.py holds the widest access behind every line:
+ *   q, k, vt, out, zero_ptr, qact, workspace, qlora_down_packed, qlora_down_packed2  16 bytes
+ *   qsmooth, qlora_down, qsmooth2, qlora_down2                                       8 bytes
+ *   qlora_act                                                                        4 bytes in fp32, 8 in the Q31.32 formats
+ *   status                                                                           4 bytes
+ *   qscales                                                                          2 bytes
+ *   ldq, ldk, ldvt, ldo, q_hs, k_hs, vt_hs, o_hs                                     8 elements */
 /* Addressing reach ("Addressing reach"):
  *   ldk                 at most 33554424: the geometry-2 loop keeps the K tile stride 128 * ldk in a 32-bit scalar (and key row 63 of a tile sits at the
  *                       32-bit byte offset 126 * ldk + 240); beyond: SVDQ_E_UNSUPPORTED
@@ -465,6 +493,11 @@ typedef struct svdq_residual_args {
     int32_t reserved2;
 } svdq_residual_args;
 
+/* Alignment of the operands of svdq_residual_gate_stats ("Alignment").  A pointer or stride that is no multiple of its line is
+ * refused with SVDQ_E_INVALID before anything is launched; NULL counts as aligned.  tests/test_alignment_contract.py holds the widest access behind every line:
+ *   res, a, b, gate, out, zero_ptr, res2, a2, b2, gate2, out2  16 bytes
+ *   stats, stats2                                              8 bytes
+ *   ld                                                         8 elements */
 /* Addressing reach ("Addressing reach"):
  *   ld                  the field's width: (size_t)row * ld
  *   M, M2, M * ld       int32 row counts; the product is 64-bit
@@ -507,6 +540,11 @@ typedef struct svdq_residual_diff_args {
     int32_t reserved;
 } svdq_residual_diff_args;
 
+/* Alignment of the operands of svdq_residual_diff ("Alignment").  A pointer or stride that is no multiple of its line is
+ * refused with SVDQ_E_INVALID before anything is launched; NULL counts as aligned.  tests/test_alignment_contract.py holds the widest access behind every line:
+ *   cur, base, prev, out_res, cur2, base2, prev2, out_res2  16 bytes
+ *   partials, result                                        8 bytes
+ *   ld                                                      8 elements */
 /* Addressing reach:
  *   ld                  the field's width: (size_t)row * ld
  *   M, M2, M * ld       int32 row counts (2 * (M + M2) partial sums); the product is 64-bit */
@@ -540,6 +578,11 @@ typedef struct svdq_modulated_diff_args {
     int32_t dtype;
 } svdq_modulated_diff_args;
 
+/* Alignment of the operands of svdq_modulated_diff ("Alignment").  A pointer or stride that is no multiple of its line is
+ * refused with SVDQ_E_INVALID before anything is launched; NULL counts as aligned.  tests/test_alignment_contract.py holds the widest access behind every line:
+ *   x, mod_scale, mod_shift, prev, out_mod  16 bytes
+ *   stats, partials, result                 8 bytes
+ *   ld                                      8 elements */
 /* Addressing reach:
  *   ld                  the field's width: (size_t)row * ld
  *   M, M2, M * ld       int32 row counts (2 * (M + M2) partial sums); the product is 64-bit */
@@ -797,6 +840,11 @@ typedef struct svdq_sana_glue_args {
     int32_t reserved;
 } svdq_sana_glue_args;
 
+/* Alignment of the operands of svdq_sana_glue ("Alignment").  A pointer or stride that is no multiple of its line is
+ * refused with SVDQ_E_INVALID before anything is launched; NULL counts as aligned.  tests/test_alignment_contract.py holds the widest access behind every line:
+ *   res, a, timestep, gate_table, mod_table, out, out_mod  16 bytes
+ *   stats                                                  8 bytes
+ *   ld_res, ld_a, ld_out, ld_mod, timestep_bs              8 elements */
 /* Addressing reach:
  *   ld_res, ld_a, ld_out, ld_mod   the field's width: (size_t)row * ld
  *   timestep_bs         int64: 64-bit sample offset
@@ -843,6 +891,11 @@ typedef struct svdq_sandwich_norm_args {
     int32_t reserved;
 } svdq_sandwich_norm_args;
 
+/* Alignment of the operands of svdq_sandwich_norm ("Alignment").  A pointer or stride that is no multiple of its line is
+ * refused with SVDQ_E_INVALID before anything is launched; NULL counts as aligned.  tests/test_alignment_contract.py holds the widest access behind every line:
+ *   res, a, w_post, gate, w_pre, scale, out, out_mod  16 bytes
+ *   stats                                             8 bytes
+ *   ld_res, ld_a, ld_out, ld_mod, gate_bs, scale_bs   8 elements */
 /* Addressing reach:
  *   ld_res, ld_a, ld_out, ld_mod   the field's width: (size_t)row * ld
  *   gate_bs, scale_bs   int64: b * (size_t)bs
@@ -879,6 +932,11 @@ typedef struct svdq_qk_norm_rope_args {
     float eps;
 } svdq_qk_norm_rope_args;
 
+/* Alignment of the operands of svdq_qk_norm_rope ("Alignment").  A pointer or stride that is no multiple of its line is
+ * refused with SVDQ_E_INVALID before anything is launched; NULL counts as aligned.  tests/test_alignment_contract.py holds the widest access behind every line:
+ *   qkv, norm_q, norm_k, freqs, vt  16 bytes
+ *   rstd                            4 bytes
+ *   ld, ldvt                        8 elements */
 /* Addressing reach:
  *   ld                  the field's width: (size_t)t * ld
  *   ldvt                the field's width: (size_t)(h * 128 + d) * ldvt
@@ -926,6 +984,11 @@ typedef struct svdq_pulid_ca_args {
     float out_scale;     /* fp32 */
 } svdq_pulid_ca_args;
 
+/* Alignment of the operands of svdq_pulid_ca ("Alignment").  A pointer or stride that is no multiple of its line is
+ * refused with SVDQ_E_INVALID before anything is launched; NULL counts as aligned.  tests/test_alignment_contract.py holds the widest access behind every line:
+ *   x, a_fold, colsum, cbias, b_fold, probs, out, acc, o_acc  16 bytes
+ *   stats                                                     8 bytes
+ *   ldx, ldo                                                  8 elements */
 /* Addressing reach:
  *   ldx, ldo            the field's width: (size_t)row * ld
  *   T, T * ld, T * H * 32   int32 rows; 64-bit products */
@@ -943,7 +1006,7 @@ int svdq_pulid_ca(const svdq_pulid_ca_args *args, void *stream);
 typedef struct svdq_gemv_awq_args {
     const void *x;        /* [M, K] 16-bit, row stride ldx */
     const void *qweight;  /* [N/4, K/2] int32 */
-    const void *scales;   /* [K/64, N] 16-bit */
+    const void *scales;   /* [K/64, N] 16-bit, 2-byte aligned as zeros, bias and out */
     const void *zeros;    /* [K/64, N] 16-bit */
     const void *bias;     /* [N] 16-bit or NULL */
     void *out;            /* [M, N] 16-bit, contiguous */
@@ -957,6 +1020,11 @@ typedef struct svdq_gemv_awq_args {
     int32_t reserved;
 } svdq_gemv_awq_args;
 
+/* Alignment of the operands of svdq_gemv_awq and svdq_gemv_awq_batched ("Alignment").  A pointer or stride that is no multiple of its line is
+ * refused with SVDQ_E_INVALID before anything is launched; NULL counts as aligned.  tests/test_alignment_contract.py holds the widest access behind every line:
+ *   x, qweight                16 bytes
+ *   scales, zeros, bias, out  2 bytes
+ *   ldx                       8 elements */
 /* Addressing reach:
  *   ldx                 the field's width: (size_t)m * ldx, M at most 8 (svdq_gemv_awq_batched: M = 1, ldx is not multiplied)
  *   N * K               the packed weight is indexed in 64 bits */
@@ -992,6 +1060,10 @@ typedef struct svdq_gemv_lora_args {
     int32_t reserved[2];
 } svdq_gemv_lora_args;
 
+/* Alignment of the operands of svdq_gemv_awq_lora_batched ("Alignment").  A pointer or stride that is no multiple of its line is
+ * refused with SVDQ_E_INVALID before anything is launched; NULL counts as aligned.  tests/test_alignment_contract.py holds the widest access behind every line:
+ *   x, down, up  16 bytes
+ *   out, t       2 bytes */
 int svdq_gemv_awq_lora_batched(const svdq_gemv_lora_args *entries, int32_t count, void *stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -1015,7 +1087,7 @@ typedef struct svdq_gemm_awq_args {
     const void *scales;       /* [G_pad, N] 16-bit */
     const void *scaled_zeros; /* [G_pad, N] 16-bit (zeros already scaled and negated: w = q*scale + scaled_zero) */
     const void *bias;         /* [N] 16-bit or NULL */
-    void *out;                /* [M, N] 16-bit, contiguous */
+    void *out;                /* [M, N] 16-bit, contiguous, 8-byte aligned (the K-split's second kernel stores four elements at a time) */
     void *workspace;          /* fp32 partial tiles of the K-split, or NULL */
     int64_t workspace_bytes;
     int32_t M, N, K, ldx;
@@ -1023,6 +1095,12 @@ typedef struct svdq_gemm_awq_args {
     int32_t dtype;            /* SVDQ_BF16 | SVDQ_FP16 */
 } svdq_gemm_awq_args;
 
+/* Alignment of the operands of svdq_gemm_awq ("Alignment").  A pointer or stride that is no multiple of its line is
+ * refused with SVDQ_E_INVALID before anything is launched; NULL counts as aligned.  tests/test_alignment_contract.py holds the widest access behind every line:
+ *   x, qweight, workspace       16 bytes
+ *   out                         8 bytes: the K-split's second kernel stores four elements at a time
+ *   scales, scaled_zeros, bias  2 bytes
+ *   ldx                         8 elements */
 /* Addressing reach:
  *   ldx                 the field's width: (size_t)row * ldx
  *   M, M * ldx, M * N   int32 rows; 64-bit products */

@@ -1257,7 +1257,13 @@ extern "C" int svdq_attention(const svdq_attention_args *a, void *stream) {
             set_error("svdq_attention: fused quantiser: qact must be 16-byte aligned, the vectors 8-byte");
             return SVDQ_E_INVALID;
         }
+        // (qscales is written one 16-bit element at a time; qlora_act takes one atomic per element: 4 bytes in fp32, 8 in the Q31.32 formats)
+        if (((uintptr_t)a->qscales & 1) || ((uintptr_t)a->qlora_act & (a->qlora_act_format == SVDQ_LORA_ACT_F32 ? 3 : 7))) {
+            set_error("svdq_attention: fused quantiser: qscales must be 2-byte aligned, qlora_act 4-byte aligned (8-byte in the Q31.32 formats)");
+            return SVDQ_E_INVALID;
+        }
     }
+    if ((uintptr_t)a->status & 3) { set_error("svdq_attention: status must be 4-byte aligned"); return SVDQ_E_INVALID; }
     if (a->qlora_act_format != SVDQ_LORA_ACT_F32 && a->qlora_act_format != SVDQ_LORA_ACT_Q32 && a->qlora_act_format != SVDQ_LORA_ACT_Q32_RUNS) { set_error("svdq_attention: unknown qlora_act_format %d", a->qlora_act_format); return SVDQ_E_INVALID; }
     if (a->kv_len0 < 0 || a->kv_len0 > a->L || (a->kv_len0 == 0 && (a->kv_start1 || a->kv_end1)) ||
         (a->kv_len0 > 0 && (a->kv_start1 < a->kv_len0 || a->kv_end1 < a->kv_start1 || a->kv_end1 > a->L) && (a->kv_start1 || a->kv_end1))) {

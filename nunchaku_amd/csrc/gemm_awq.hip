@@ -286,9 +286,13 @@ extern "C" int svdq_gemm_awq(const svdq_gemm_awq_args *a, void *stream) {
     if (a->K <= 0 || a->K % AWQ_GEMM_GROUP) { set_error("svdq_gemm_awq: K=%d must be a positive multiple of 128", a->K); return SVDQ_E_INVALID; }
     if (a->ldx < a->K || a->ldx % 8) { set_error("svdq_gemm_awq: ldx=%d must be >= K and a multiple of 8", a->ldx); return SVDQ_E_INVALID; }
     if (((uintptr_t)a->x | (uintptr_t)a->qweight) & 15) { set_error("svdq_gemm_awq: x and qweight must be 16-byte aligned"); return SVDQ_E_INVALID; }
+    // (the K-split's reduce kernel stores out in 8-byte pieces of four elements; scales, scaled_zeros and bias are read one element at a time)
+    if ((uintptr_t)a->out & 7) { set_error("svdq_gemm_awq: out must be 8-byte aligned"); return SVDQ_E_INVALID; }
+    if (((uintptr_t)a->scales | (uintptr_t)a->scaled_zeros | (uintptr_t)a->bias) & 1) { set_error("svdq_gemm_awq: scales, scaled_zeros and bias must be 2-byte aligned"); return SVDQ_E_INVALID; }
+    if ((uintptr_t)a->workspace & 15) { set_error("svdq_gemm_awq: workspace must be 16-byte aligned"); return SVDQ_E_INVALID; }
     const AwqPlan p = awq_plan(a->M, a->N, a->K, a->workspace != nullptr);
     const int64_t need = awq_workspace_bytes(p, a->M, a->N);
-    if (a->workspace && (a->workspace_bytes < need || ((uintptr_t)a->workspace & 15))) {
+    if (a->workspace && a->workspace_bytes < need) {
         set_error("svdq_gemm_awq: workspace of %lld bytes; this launch needs %lld (svdq_gemm_awq_workspace_bytes), 16-byte aligned",
                   (long long)a->workspace_bytes, (long long)need);
         return SVDQ_E_INVALID;

@@ -2224,6 +2224,15 @@ static int validate_gemm_args(const svdq_gemm_args *a) {
         set_error("svdq_gemm_w4a4: out, bias, next_smooth, next_lora_down, norm_q, norm_k, lora_act_out must be 8-byte aligned");
         return SVDQ_E_INVALID;
     }
+    // (the fragment images are read in 16-byte pieces; oscales is written one 16-bit element at a time, status is one 32-bit word)
+    if (((uintptr_t)a->lora_up_packed | (uintptr_t)a->next_lora_down_packed | (uintptr_t)a->next_lora_down_packed2) & 15) {
+        set_error("svdq_gemm_w4a4: lora_up_packed, next_lora_down_packed and next_lora_down_packed2 must be 16-byte aligned");
+        return SVDQ_E_INVALID;
+    }
+    if (((uintptr_t)a->oscales & 1) || ((uintptr_t)a->status & 3)) {
+        set_error("svdq_gemm_w4a4: oscales must be 2-byte aligned, status 4-byte aligned");
+        return SVDQ_E_INVALID;
+    }
     return SVDQ_OK;
 }
 

@@ -323,6 +323,8 @@ static int validate_gemv(const svdq_gemv_awq_args *a) {
     if (a->N <= 0 || a->N % 4 || a->K <= 0 || a->K % AWQ_GROUP) { set_error("svdq_gemv_awq: need N=%d %% 4 == 0 and K=%d %% 64 == 0", a->N, a->K); return SVDQ_E_INVALID; }
     if (a->ldx < a->K || a->ldx % 8) { set_error("svdq_gemv_awq: ldx=%d must be >= K and a multiple of 8", a->ldx); return SVDQ_E_INVALID; }
     if (((uintptr_t)a->x | (uintptr_t)a->qweight) & 15) { set_error("svdq_gemv_awq: x and qweight must be 16-byte aligned"); return SVDQ_E_INVALID; }
+    // (read and written one 16-bit element at a time)
+    if (((uintptr_t)a->scales | (uintptr_t)a->zeros | (uintptr_t)a->bias | (uintptr_t)a->out) & 1) { set_error("svdq_gemv_awq: scales, zeros, bias and out must be 2-byte aligned"); return SVDQ_E_INVALID; }
     if (a->dtype != SVDQ_BF16 && a->dtype != SVDQ_FP16) { set_error("svdq_gemv_awq: unknown dtype %d", a->dtype); return SVDQ_E_INVALID; }
     if (a->out_chunks < 0 || (a->out_chunks > 1 && a->N % a->out_chunks)) { set_error("svdq_gemv_awq: out_chunks=%d must divide N=%d", a->out_chunks, a->N); return SVDQ_E_INVALID; }
     return SVDQ_OK;

@@ -744,6 +744,8 @@ static int validate_quantize_args(const svdq_quantize_args *a) {
     if (a->R < 0 || a->R % 16 || a->R > 256) { set_error("svdq_quantize: R=%d must be a multiple of 16 in [0, 256]", a->R); return SVDQ_E_INVALID; }
     if (a->R > 0 && (!a->lora_down || !a->lora_act)) { set_error("svdq_quantize: R > 0 needs lora_down and lora_act"); return SVDQ_E_INVALID; }
     if (((uintptr_t)a->act) & 15) { set_error("svdq_quantize: act must be 16-byte aligned"); return SVDQ_E_INVALID; }
+    // (both are written one element at a time: 16-bit scales, fp32 sums -- the Q31.32 sums are checked above)
+    if (((uintptr_t)a->ascales & 1) || ((uintptr_t)a->lora_act & 3)) { set_error("svdq_quantize: ascales must be 2-byte aligned, an fp32 lora_act 4-byte aligned"); return SVDQ_E_INVALID; }
     if (((uintptr_t)a->x | (uintptr_t)a->lora_down | (uintptr_t)a->smooth) & 7) {
         set_error("svdq_quantize: x, lora_down and smooth must be 8-byte aligned");
         return SVDQ_E_INVALID;
@@ -763,7 +765,7 @@ static int validate_quantize_args(const svdq_quantize_args *a) {
     if (a->x2) { // grouped launch
         if (a->split_rows <= 0 || a->split_rows % 256 || a->M != a->split_rows || a->M2 <= 0 || a->split_rows + a->M2 > a->M_pad ||
             a->ldx2 < a->K || a->ldx2 % 4) {
-            set_error("svdq_quantize: grouped launch needs M == split_rows (a multiple of 256), 0 < M2, split_rows + M2 <= M_pad, ldx2 >= K");
+            set_error("svdq_quantize: grouped launch needs M == split_rows (a multiple of 256), 0 < M2, split_rows + M2 <= M_pad, ldx2=%d >= K and a multiple of 4", a->ldx2);
             return SVDQ_E_INVALID;
         }
         if ((a->smooth != nullptr) != (a->smooth2 != nullptr) || (a->R > 0 && !a->lora_down2) ||

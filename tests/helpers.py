@@ -87,6 +87,33 @@ def checked_codes(qx, asc, x: np.ndarray, smooth, dtype: str, max_flips: float =
     return codes, scales
 
 
+def retargeted(monkeypatch, symbol: str, launch, edit=None, **fields):
+    """``launch()`` with the args struct of the library entry point ``symbol`` changed on its way into the library: ``fields`` are written into it, then
+    ``edit(args)`` may change it further (it sees the struct the wrapper built, addresses included).  A batched entry point (``(entries, count, stream)``)
+    gets both for each of its ``count`` entries, ``edit(args, i)``.  Everything else about the call is the wrapper's.  Synchronises; -> what ``launch()``
+    returned.  (tests/test_gpu_large_extents.py: wide strides; tests/test_gpu_min_alignment.py: the smallest admitted alignments.)"""
+    from nunchaku_amd import _lib
+
+    lib = _lib.load()
+    real = getattr(lib, symbol)
+    batched = len(_lib.EXPORTS[symbol][1]) == 3
+
+    def patched(ref, *rest):
+        entries = [ref[i] for i in range(rest[0])] if batched else [ref._obj]
+        for i, a in enumerate(entries):
+            for k, v in fields.items():
+                setattr(a, k, v)
+            if edit is not None:
+                edit(a, i) if batched else edit(a)
+        return real(ref, *rest)
+
+    with monkeypatch.context() as m:
+        m.setattr(lib, symbol, patched)
+        res = launch()
+    torch.cuda.synchronize()
+    return res
+
+
 def served_fragment_images(module: torch.nn.Module):
     """The MFMA-fragment images of low-rank factors (``nunchaku_amd._C._packed_fragments``, ABI 21) that the cache would SERVE for the parameters of
     ``module`` now -- entries whose version is the parameter's current ``_version`` -- each compared with a fresh pack of the parameter's current

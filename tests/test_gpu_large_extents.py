@@ -26,7 +26,7 @@ import torch
 from oracle import svdq_oracle as O
 from tests import test_gpu_dispatch_classes as D
 from tests import test_gpu_hot_instantiations as T
-from tests.helpers import TORCH_DT, ULP16, attn_softmax64, checked_codes, f32, t16
+from tests.helpers import TORCH_DT, ULP16, attn_softmax64, checked_codes, f32, retargeted, t16
 
 pytestmark = pytest.mark.gpu
 
@@ -399,21 +399,7 @@ LDVT_GEMM = 2 ** 23 + 2 ** 16  # 256 channel rows: row 255 starts beyond 2^32 by
 
 def _retargeted(monkeypatch, run, **fields):
     """run.launch() with `fields` written into the args struct just before the library sees it -> plan"""
-    from nunchaku_amd import _lib
-
-    lib = _lib.load()
-    real = lib.svdq_gemm_w4a4
-
-    def patched(ref, stream):
-        for k, v in fields.items():
-            setattr(ref._obj, k, v)
-        return real(ref, stream)
-
-    with monkeypatch.context() as m:
-        m.setattr(lib, "svdq_gemm_w4a4", patched)
-        _, plan = run.launch()
-    torch.cuda.synchronize()
-    return plan
+    return retargeted(monkeypatch, "svdq_gemm_w4a4", run.launch, **fields)[1]
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
