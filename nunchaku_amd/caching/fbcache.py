@@ -114,19 +114,20 @@ def are_two_tensors_similar(t1: torch.Tensor, t2: torch.Tensor, *, threshold: fl
 
 
 def apply_prev_hidden_states_residual(hidden_states: torch.Tensor, encoder_hidden_states: torch.Tensor | None = None,
-                                      mode: str = "multi") -> Tuple[torch.Tensor, torch.Tensor]:
-    """Add the stored residuals of the skipped blocks: ``(hidden, encoder_hidden)`` for ``mode="multi"``, ``hidden`` for ``"single"``."""
+                                      mode: str = "multi", suffix: str = "") -> Tuple[torch.Tensor, torch.Tensor]:
+    """Add the stored residuals of the skipped blocks: ``(hidden, encoder_hidden)`` for ``mode="multi"``, ``hidden`` for ``"single"``.
+    ``suffix`` (extension): appended to the buffer names."""
     if mode == "multi":
-        hidden_states_residual = get_buffer("multi_hidden_states_residual")
+        hidden_states_residual = get_buffer("multi_hidden_states_residual" + suffix)
         assert hidden_states_residual is not None, "multi_hidden_states_residual must be set before"
         hidden_states = (hidden_states + hidden_states_residual).contiguous()
         if encoder_hidden_states is not None:
-            enc_hidden_res = get_buffer("multi_encoder_hidden_states_residual")
+            enc_hidden_res = get_buffer("multi_encoder_hidden_states_residual" + suffix)
             assert enc_hidden_res is not None, "multi_encoder_hidden_states_residual must be set before"
             encoder_hidden_states = (encoder_hidden_states + enc_hidden_res).contiguous()
         return hidden_states, encoder_hidden_states
     elif mode == "single":
-        single_residual = get_buffer("single_hidden_states_residual")
+        single_residual = get_buffer("single_hidden_states_residual" + suffix)
         assert single_residual is not None, "single_hidden_states_residual must be set before"
         return (hidden_states + single_residual).contiguous()
     raise ValueError(f"Unknown mode {mode}; expected 'multi' or 'single'")
@@ -140,9 +141,11 @@ def _first_name(mode: str) -> str:
     raise ValueError(f"Unknown mode {mode}; expected 'multi' or 'single'")
 
 
-def get_can_use_cache(first_hidden_states_residual: torch.Tensor, threshold: float, parallelized: bool = False, mode: str = "multi"):
-    """``(can_use_cache, diff)``: the stored first residual of ``mode`` against the current one; no stored residual: ``(False, threshold)``."""
-    prev_res = get_buffer(_first_name(mode))
+def get_can_use_cache(first_hidden_states_residual: torch.Tensor, threshold: float, parallelized: bool = False, mode: str = "multi",
+                      suffix: str = ""):
+    """``(can_use_cache, diff)``: the stored first residual of ``mode`` against the current one; no stored residual: ``(False, threshold)``.
+    ``suffix`` (extension): appended to the buffer name -- one set of buffers per branch of a true-CFG step."""
+    prev_res = get_buffer(_first_name(mode) + suffix)
     if prev_res is None:
         first_hidden_states_residual.__dict__.pop("_fbcache_compared", None)
         return torch.tensor(False), torch.tensor(threshold)
@@ -152,19 +155,24 @@ def get_can_use_cache(first_hidden_states_residual: torch.Tensor, threshold: flo
 def check_and_apply_cache(*, first_residual: torch.Tensor, hidden_states: torch.Tensor,
                           encoder_hidden_states: Optional[torch.Tensor] = None, threshold: float, parallelized: bool, mode: str,
                           verbose: bool, call_remaining_fn, remaining_kwargs,
-                          apply_residual_fn=None) -> Tuple[torch.Tensor, Optional[torch.Tensor], float]:
+                          apply_residual_fn=None, suffix: str = "") -> Tuple[torch.Tensor, Optional[torch.Tensor], float]:
     """The state machine of a cached step.  Hit: the stored residuals are added (the stored FIRST residual stays).  Miss: ``first_residual``
     is stored, ``call_remaining_fn(hidden_states=..., encoder_hidden_states=..., **remaining_kwargs)`` runs the other blocks and returns
     ``(hidden, encoder_hidden, hidden_residual, encoder_residual)`` (``"multi"``) or ``(hidden, residual)`` (``"single"``), which are stored.
     Returns ``(hidden, encoder_hidden or None, threshold)``.  ``apply_residual_fn(hidden_states, encoder_hidden_states, mode)`` (extension)
-    replaces :func:`apply_prev_hidden_states_residual` on a hit: the engine adds the residuals with its fused pass."""
-    can_use_cache, diff = get_can_use_cache(first_residual, threshold=threshold, parallelized=parallelized, mode=mode)
+    replaces :func:`apply_prev_hidden_states_residual` on a hit: the engine adds the residuals with its fused pass.  ``suffix`` (extension)
+    is appended to every buffer name (an ``apply_residual_fn`` reads the same names).  A ``"multi"`` step that hands in no text
+    stream and gets no text residual back stores none."""
+    can_use_cache, diff = get_can_use_cache(first_residual, threshold=threshold, parallelized=parallelized, mode=mode, suffix=suffix)
 
     if can_use_cache:
         if verbose:
             diff_val = diff.item() if isinstance(diff, torch.Tensor) else diff
             print(f"[{mode.upper()}] Cache hit! diff={diff_val:.4f}, new threshold={threshold:.4f}")
-        out = (apply_residual_fn or apply_prev_hidden_states_residual)(hidden_states, encoder_hidden_states, mode=mode)
+        if apply_residual_fn is not None:
+            out = apply_residual_fn(hidden_states, encoder_hidden_states, mode=mode)
+        else:
+            out = apply_prev_hidden_states_residual(hidden_states, encoder_hidden_states, mode=mode, suffix=suffix)
         updated_h, updated_enc = out if isinstance(out, tuple) else (out, None)
         return updated_h, updated_enc, threshold
 
@@ -172,14 +180,15 @@ def check_and_apply_cache(*, first_residual: torch.Tensor, hidden_states: torch.
         diff_val = diff.item() if isinstance(diff, torch.Tensor) else diff
         print(f"[{mode.upper()}] Cache miss. diff={diff_val:.4f}, was={threshold:.4f} => now={threshold:.4f}")
 
-    set_buffer(_first_name(mode), first_residual)
+    set_buffer(_first_name(mode) + suffix, first_residual)
     result = call_remaining_fn(hidden_states=hidden_states, encoder_hidden_states=encoder_hidden_states, **remaining_kwargs)
 
     if mode == "multi":
         updated_h, updated_enc, hs_res, enc_res = result
-        set_buffer("multi_hidden_states_residual", hs_res)
-        set_buffer("multi_encoder_hidden_states_residual", enc_res)
+        set_buffer("multi_hidden_states_residual" + suffix, hs_res)
+        if enc_res is not None or encoder_hidden_states is not None:
+            set_buffer("multi_encoder_hidden_states_residual" + suffix, enc_res)
         return updated_h, updated_enc, threshold
     updated_cat_states, cat_res = result
-    set_buffer("single_hidden_states_residual", cat_res)
+    set_buffer("single_hidden_states_residual" + suffix, cat_res)
     return updated_cat_states, None, threshold

@@ -29,7 +29,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..ops.attention import attention_packed, kv_valid_ranges, q_prescale
-from ..ops.elementwise import residual_gate_stats
+from ..ops.elementwise import residual_diff, residual_gate_stats
 from ..ops.fused import fused_qkv_norm_rottary, fused_qkv_norm_rottary_pair, linear_pair
 from ..ops.gemv import awq_gemv_w4a16_batched, awq_gemv_w4a16_cuda
 from ..utils import pad_tensor
@@ -212,16 +212,17 @@ class NunchakuQwenImageTransformerBlock(nn.Module):
             outs.append(m)
         return outs
 
-    def forward_fused(self, hidden, enc, temb_act, packed_rot, stats, mods=None, kv_valid=None):
+    def forward_fused(self, hidden, enc, temb_act, packed_rot, stats, mods=None, kv_valid=None, keep_input: bool = False):
         """The block on this library's fused passes (models/blocks.py ``dual_stream_block``; B = 1, token counts multiples of 256).
         Same 16-bit rounding points as :meth:`forward`'s torch ops (the fused passes are bit-exact restatements of them, DESIGN.md
         section 6e).  ``stats`` = ((img stats, ZeroPool or None), (txt stats, ZeroPool or None)) of the block's inputs, as in
-        models/flux.py; returns (enc, hidden, stats of the outputs)."""
+        models/flux.py; returns (enc, hidden, stats of the outputs).  ``keep_input``: the two input tensors stay as they are (the
+        same launches; the streams are updated in place otherwise)."""
         im, tm = mods if mods is not None else self.modulation(temb_act)
         # the reference clips both streams at the end of an fp16 block (:300-303)
         return blocks.dual_stream_block(
             lambda h, e, ln, ln_ctx: self.attn.forward_fused_norm(h, e, packed_rot, ln, ln_ctx, kv_valid=kv_valid), self.attn, self.img_mlp,
-            self.txt_mlp, hidden, enc, stats, im, tm, clamp_img=True)
+            self.txt_mlp, hidden, enc, stats, im, tm, clamp_img=True, keep_input=keep_input)
 
     def forward(self, hidden_states, encoder_hidden_states, encoder_hidden_states_mask=None, temb=None, image_rotary_emb=None,
                 joint_attention_kwargs=None, kv_valid=None):
@@ -404,7 +405,19 @@ class NunchakuQwenImageTransformer2DModel(_DiffusersQwen if HAVE_DIFFUSERS_QWEN 
     def forward(self, hidden_states, encoder_hidden_states=None, encoder_hidden_states_mask=None, timestep=None, img_shapes=None,
                 txt_seq_lens=None, guidance=None, attention_kwargs=None, controlnet_block_samples=None, return_dict: bool = True):
         """hidden_states [1, T_img, 64] (packed 2x2 latent patches); encoder_hidden_states [1, T_txt, 3584]; timestep [1] (already
-        divided by 1000 by the pipeline); img_shapes [(frames, H/2, W/2)] of the latent grid.  -> [1, T_img, 64]."""
+        divided by 1000 by the pipeline); img_shapes [(frames, H/2, W/2)] of the latent grid.  -> [1, T_img, 64].
+        The step is its stages run back to back (``_prologue``, ``_launch_mods``, ``_run_blocks``, ``_tail``); :meth:`forward_cached`
+        is the same stages with the First-Block-Cache decision in between."""
+        st = self._prologue(hidden_states, encoder_hidden_states, encoder_hidden_states_mask, timestep, img_shapes, attention_kwargs,
+                            controlnet_block_samples)
+        n = len(self.transformer_blocks)
+        self._launch_mods(st, 0, n)  # all 2 x num_layers modulation projections depend on temb only: ONE batched GEMV launch
+        self._run_blocks(st, 0, n)
+        return self._output(self._tail(st), return_dict)
+
+    def _prologue(self, hidden_states, encoder_hidden_states, encoder_hidden_states_mask=None, timestep=None, img_shapes=None,
+                  attention_kwargs=None, controlnet_block_samples=None) -> "_Step":
+        """Embedders, rotary tables, padding of the two streams and their first LayerNorm statistics."""
         dt = self.dtype_
         hidden = self.img_in(hidden_states)
         enc = self.txt_in(self.txt_norm(encoder_hidden_states))
@@ -438,39 +451,163 @@ class NunchakuQwenImageTransformer2DModel(_DiffusersQwen if HAVE_DIFFUSERS_QWEN 
         if kv_valid is not None:
             enc, hidden = F.pad(enc, (0, 0, 0, -t_txt % 256)), F.pad(hidden, (0, 0, 0, -t_img % 256))
         fused = self.fused_norm and hot and enc.shape[1] % 256 == 0 and hidden.shape[1] % 256 == 0
-        stats = mods = temb_act = None
+        st = _Step()
+        st.hidden, st.enc, st.temb, st.rot, st.kv_valid, st.t_txt, st.t_img, st.fused = hidden, enc, temb, rot, kv_valid, t_txt, t_img, fused
+        st.mask, st.attention_kwargs, st.cn, st.compute_stream = encoder_hidden_states_mask, attention_kwargs, controlnet_block_samples, compute_stream
+        st.stats, st.temb_act, st.mods = None, None, {}
         if fused:
-            temb_act = F.silu(temb)  # img_mod[0] / txt_mod[0] of every block: the same SiLU of the same embedding
-            stats = ((residual_gate_stats(hidden)[1], None), (residual_gate_stats(enc)[1], None))  # (image, text), each with its ZeroPool
-            if not self.offload and self.batched_mods:
-                # all 2 x num_layers modulation projections depend on temb only: ONE batched GEMV launch, +1 on the scale rows in two ops
-                lins = [SimpleNamespace(qweight=l.qweight, wscales=l.wscales, wzeros=l.wzeros, bias=l.bias, out_features=l.out_features,
-                                        in_features=l.in_features, group_size=l.group_size, out_chunks=6, _lora=l._lora)
-                        for b in self.transformer_blocks for l in (b.img_mod[1], b.txt_mod[1])]
-                outs = awq_gemv_w4a16_batched(temb_act, lins)
-                base = outs[0]._base if outs[0]._base is not None else outs[0]  # the launch's one output buffer: the layers' vectors back to back
-                allm = base.reshape(-1)[: len(lins) * 6 * self.inner_dim].view(len(lins), 6, self.inner_dim)
-                if self.transformer_blocks[0].scale_shift != 0:
-                    allm[:, 1::3] += self.transformer_blocks[0].scale_shift
-                mods = [(allm[2 * i], allm[2 * i + 1]) for i in range(len(self.transformer_blocks))]
-        for i, block in enumerate(self.transformer_blocks):
-            if self.offload:
-                block = self.offload_manager.get_block(i)
-            if fused:
-                enc, hidden, stats = block.forward_fused(hidden, enc, temb_act, rot, stats, mods=None if mods is None else mods[i], kv_valid=kv_valid)
+            st.temb_act = F.silu(temb)  # img_mod[0] / txt_mod[0] of every block: the same SiLU of the same embedding
+            st.stats = ((residual_gate_stats(hidden)[1], None), (residual_gate_stats(enc)[1], None))  # (image, text), each with its ZeroPool
+        return st
+
+    def _launch_mods(self, st: "_Step", lo: int, hi: int) -> None:
+        """The modulation projections of blocks ``lo .. hi - 1`` (two each) in one batched GEMV launch, +1 on the scale rows in one op
+        (resident models on the fused path; a block whose projections were not launched here runs its own)."""
+        if not (st.fused and not self.offload and self.batched_mods) or hi <= lo:
+            return
+        lins = [SimpleNamespace(qweight=l.qweight, wscales=l.wscales, wzeros=l.wzeros, bias=l.bias, out_features=l.out_features,
+                                in_features=l.in_features, group_size=l.group_size, out_chunks=6, _lora=l._lora)
+                for b in self.transformer_blocks[lo:hi] for l in (b.img_mod[1], b.txt_mod[1])]
+        outs = awq_gemv_w4a16_batched(st.temb_act, lins)
+        base = outs[0]._base if outs[0]._base is not None else outs[0]  # the launch's one output buffer: the layers' vectors back to back
+        allm = base.reshape(-1)[: len(lins) * 6 * self.inner_dim].view(len(lins), 6, self.inner_dim)
+        if self.transformer_blocks[0].scale_shift != 0:
+            allm[:, 1::3] += self.transformer_blocks[0].scale_shift
+        for k in range(hi - lo):
+            st.mods[lo + k] = (allm[2 * k], allm[2 * k + 1])
+
+    def _run_blocks(self, st: "_Step", lo: int, hi: int, keep_input: bool = False) -> None:
+        """Blocks ``lo .. hi - 1``.  ``keep_input`` (fused path): block ``lo`` leaves its two input tensors as they are (the streams are
+        updated in place otherwise)."""
+        n = len(self.transformer_blocks)
+        for i in range(lo, hi):
+            block = self.offload_manager.get_block(i) if self.offload else self.transformer_blocks[i]
+            if st.fused:
+                st.enc, st.hidden, st.stats = block.forward_fused(st.hidden, st.enc, st.temb_act, st.rot, st.stats, mods=st.mods.get(i),
+                                                                  kv_valid=st.kv_valid, keep_input=keep_input and i == lo)
             else:
-                enc, hidden = block(hidden_states=hidden, encoder_hidden_states=enc, encoder_hidden_states_mask=encoder_hidden_states_mask,
-                                    temb=temb, image_rotary_emb=rot, joint_attention_kwargs=attention_kwargs, kv_valid=kv_valid)
-            if controlnet_block_samples is not None:
+                st.enc, st.hidden = block(hidden_states=st.hidden, encoder_hidden_states=st.enc, encoder_hidden_states_mask=st.mask,
+                                          temb=st.temb, image_rotary_emb=st.rot, joint_attention_kwargs=st.attention_kwargs, kv_valid=st.kv_valid)
+            if st.cn is not None:
                 # the reference's (= diffusers') choice of the residual behind block i (transformer_qwenimage.py:546-550)
-                hidden, h_stats = blocks.add_control(hidden, controlnet_block_samples, i, len(self.transformer_blocks), want_stats=fused)
-                if fused:
-                    stats = ((h_stats, stats[0][1]), stats[1])
+                st.hidden, h_stats = blocks.add_control(st.hidden, st.cn, i, n, want_stats=st.fused)
+                if st.fused:
+                    st.stats = ((h_stats, st.stats[0][1]), st.stats[1])
             if self.offload:
-                self.offload_manager.step(compute_stream)
-        out = self.proj_out(self.norm_out(hidden[:, :t_img], F.silu(temb)))
+                self.offload_manager.step(st.compute_stream)
+
+    def _tail(self, st: "_Step") -> torch.Tensor:
+        """The real image rows through AdaLayerNormContinuous and the output projection."""
+        return self.proj_out(self.norm_out(st.hidden[:, :st.t_img], F.silu(st.temb)))
+
+    @staticmethod
+    def _output(out: torch.Tensor, return_dict: bool):
         if not return_dict:
             return (out,)
         from .transformer_flux import Transformer2DModelOutput
 
         return Transformer2DModelOutput(sample=out)
+
+    def _fused_step(self, batch: int, t_txt: int, t_img: int, attention_kwargs) -> bool:
+        """whether :meth:`_prologue` will put a step of these shapes on the fused path (its own conditions, from the shapes alone)"""
+        pad = (lambda n: n + -n % 256) if self.padded_tokens else (lambda n: n)
+        return bool(self.fused_norm and batch == 1 and NunchakuQwenAttention.fused_qkv and self.transformer_blocks[0].attn.head_dim == 128
+                    and not attention_kwargs and pad(t_txt) % 256 == 0 and pad(t_img) % 256 == 0)
+
+    def forward_cached(self, hidden_states, encoder_hidden_states=None, encoder_hidden_states_mask=None, timestep=None, img_shapes=None,
+                       txt_seq_lens=None, guidance=None, attention_kwargs=None, controlnet_block_samples=None, return_dict: bool = True, *,
+                       residual_diff_threshold: float = 0.12, first_blocks: int = 1, branch: int = 0, verbose: bool = False):
+        """One denoising step with First-Block Cache (semantics: the reference's ``cached_forward_v2`` / ``check_and_apply_cache``, which
+        it has for FLUX only): the stages of :meth:`forward` with the decision of ``caching.fbcache.check_and_apply_cache`` in between.
+
+        The first ``first_blocks`` blocks always run (``1 <= first_blocks < num_layers``), with only their modulation projections
+        launched.  What they did to the REAL image rows (``[:t_img]``; the rows that pad the stream to 256 never enter a sum) is compared
+        with the same residual of the last computed step of the same ``branch`` (``svdq_residual_diff``: subtraction and comparison in
+        one pass).  Hit (``ratio < residual_diff_threshold``): the stored residual of the other blocks is added to the image rows (one
+        ``svdq_residual_gate_stats`` pass) and the tail runs -- nothing of the other blocks is launched, and the text stream stays as it
+        is: nothing behind the blocks reads it.  Miss: the other blocks' modulation projections and the blocks run, ``final - after the
+        first blocks`` (image rows) and the first residual are stored.
+
+        ``branch`` selects the buffers (``first_multi_hidden_states_residual_<branch>``, ``multi_hidden_states_residual_<branch>`` in the
+        active context): the conditional and the unconditional call of a true-CFG step have different text lengths and are never compared
+        with each other.  A stored buffer with another shape, dtype or device counts as not stored (a miss).
+
+        ``residual_diff_threshold <= 0`` runs the plain forward.  The decision is read on the host, which synchronises the stream.
+        Refused before anything is launched: no active ``fbcache.cache_context`` and a stream under capture (RuntimeError); batch > 1,
+        ``controlnet_block_samples``, ``first_blocks`` out of range (ValueError); an offloaded model -- skipped blocks break the
+        prefetch order of ``CPUOffloadManager`` -- and a step off the fused path: ``attention_kwargs``, a head dim other than 128,
+        ``fused_norm`` / ``fused_qkv`` / ``padded_tokens`` switched off (NotImplementedError)."""
+        from ..caching import fbcache
+
+        if residual_diff_threshold <= 0:
+            return NunchakuQwenImageTransformer2DModel.forward(
+                self, hidden_states, encoder_hidden_states, encoder_hidden_states_mask, timestep, img_shapes, txt_seq_lens, guidance,
+                attention_kwargs, controlnet_block_samples, return_dict)
+        ctx = fbcache.get_current_cache_context()
+        if ctx is None:
+            raise RuntimeError("First-Block Cache needs an active cache context: cache_context must be set before "
+                               "(with fbcache.cache_context(fbcache.create_cache_context()): ...)")
+        if hidden_states.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("First-Block Cache reads its decision on the host, which synchronises the stream: a cached forward cannot be "
+                               "captured into a graph (run the uncached forward under capture: residual_diff_threshold <= 0)")
+        if hidden_states.shape[0] != 1:
+            raise ValueError(f"First-Block Cache supports batch 1 only (got {hidden_states.shape[0]}): run the samples one by one, each in "
+                             "its own cache context or branch")
+        if controlnet_block_samples is not None:
+            raise ValueError("First-Block Cache does not support ControlNet residuals: the skipped blocks' residuals would be dropped")
+        n = len(self.transformer_blocks)
+        if not 1 <= int(first_blocks) < n:
+            raise ValueError(f"first_blocks must be in [1, {n - 1}] for a model of {n} blocks, got {first_blocks}")
+        if self.offload:
+            raise NotImplementedError("First-Block Cache does not support an offloaded model: skipped blocks break the prefetch order of "
+                                      "CPUOffloadManager (set_offload(False), or run the uncached forward)")
+        t_txt, t_img = encoder_hidden_states.shape[1], hidden_states.shape[1]
+        if not self._fused_step(1, t_txt, t_img, attention_kwargs):
+            raise NotImplementedError("First-Block Cache runs on the fused path only: no attention_kwargs, head_dim 128, and fused_norm, "
+                                      "fused_qkv and padded_tokens left on")
+        first_blocks, suffix = int(first_blocks), f"_{int(branch)}"
+        first_name = "first_multi_hidden_states_residual" + suffix
+
+        st = self._prologue(hidden_states, encoder_hidden_states, encoder_hidden_states_mask, timestep, img_shapes)
+        self._launch_mods(st, 0, first_blocks)  # of the blocks that run whatever the decision
+        h0 = st.hidden
+        self._run_blocks(st, 0, first_blocks, keep_input=True)
+        cur = st.hidden[0, :t_img]
+        first = torch.empty(1, t_img, self.inner_dim, dtype=cur.dtype, device=cur.device)
+        prev = ctx.get_buffer(first_name)
+        if prev is not None and (prev.shape != first.shape or prev.dtype != first.dtype or prev.device != first.device or not prev.is_contiguous()):
+            ctx.buffers.pop(first_name)  # of another token count, dtype or device: as good as not stored -- this step is a miss and replaces it
+            prev = None
+        _, record = residual_diff(cur, h0[0, :t_img], None if prev is None else prev[0], first[0])
+        del h0
+        if prev is not None:
+            fbcache.attach_comparison(first, prev, record)  # subtracted and compared in the one launch: the decision reads this record
+
+        def apply_residual(hidden_states, encoder_hidden_states, mode):
+            """a hit: the stored image residual is added in place to the real rows (one 16-bit add); the text stream is not touched"""
+            res = ctx.get_buffer("multi_hidden_states_residual" + suffix)
+            rows = hidden_states[0, :t_img]
+            if res is None or res.shape[1:] != rows.shape or res.dtype != rows.dtype or res.device != rows.device:
+                raise RuntimeError("First-Block Cache: a hit, but no residual of a computed step with this step's shape is stored")
+            residual_gate_stats(rows, res[0], want_stats=False)
+            return hidden_states, encoder_hidden_states
+
+        def remaining(hidden_states, encoder_hidden_states):
+            """a miss: the other blocks; the first blocks' image stream survives for the residual"""
+            self._launch_mods(st, first_blocks, n)
+            self._run_blocks(st, first_blocks, n, keep_input=True)
+            res, _ = residual_diff(st.hidden[0, :t_img], hidden_states[0, :t_img])
+            return st.hidden, st.enc, res.unsqueeze(0), None
+
+        st.hidden, _, _ = fbcache.check_and_apply_cache(
+            first_residual=first, hidden_states=st.hidden, encoder_hidden_states=None, threshold=residual_diff_threshold, parallelized=False,
+            mode="multi", verbose=verbose, call_remaining_fn=remaining, remaining_kwargs={}, apply_residual_fn=apply_residual, suffix=suffix)
+        return self._output(self._tail(st), return_dict)
+
+
+class _Step:
+    """What one denoising step carries between the stages of :class:`NunchakuQwenImageTransformer2DModel`: the two streams, the LayerNorm
+    statistics that travel with them on the fused path, the modulation vectors launched so far (by block index) and the step's constants."""
+
+    __slots__ = ("hidden", "enc", "temb", "temb_act", "rot", "kv_valid", "t_txt", "t_img", "fused", "stats", "mods", "mask",
+                 "attention_kwargs", "cn", "compute_stream")
