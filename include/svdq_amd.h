@@ -944,6 +944,53 @@ typedef struct svdq_qk_norm_rope_args {
 int svdq_qk_norm_rope(const svdq_qk_norm_rope_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Qwen-Image rotary tables for one or several latent grids (added WITHOUT a version bump: one new symbol and a new args struct, nothing
+ * existing changes, so SVDQ_ABI_VERSION stays 24.  reference: diffusers QwenEmbedRope.forward / _compute_video_freqs, as the Edit pipelines
+ * call it with img_shapes = [[(1, h, w), (1, h1, w1), ...]] -- the noise latents and one to three reference images).  One launch writes
+ * what nunchaku_amd/models/qwenimage.py pack_qwen_rotary returns, gathered from two per-axis tables that depend on theta and axes_dim only:
+ *   pos_cs[k, c] = (cos, sin)(float(k) * inv[c])          k = 0 .. 4095, c = 0 .. 63
+ *   neg_cs[k, c] = (cos, sin)(float(-(k + 1)) * inv[c])   row k holds position -(k + 1)
+ * with the channels of the frame, height and width axes side by side: [0, c_frame), [c_frame, c_frame + c_height), the rest.
+ * Image rows: the grids back to back, grid g (0-based, extents (F, H, W)) flattened frame-major, then height, then width.  Row (f, h, w) of
+ * grid g reads position g + f on the frame axis, h - (H - H / 2) on the height axis with scale_rope (h without) and w - (W - W / 2) (w) on the
+ * width axis.  Text row t reads position txt_start + t on all three axes (diffusers: txt_start = max over the grids of max(H / 2, W / 2)
+ * with scale_rope, of max(H, W) without -- the caller's rule, not the library's).
+ * Outputs (each optional; NULL skips it; all fp32).  T = the image rows, pad(n) = n rounded up to 256:
+ *   img [pad(T), 128], txt [pad(txt_len), 128], all [pad(txt_len) + pad(T), 128]: (sin, cos) in the QKV epilogue's order (svdq_gemm_args.rotary_emb,
+ *       models/embeddings.py pack_rotemb); `all` is the joint sequence [text | image] with each stream on a 256-row boundary
+ *   img_cs [T, 64, 2], txt_cs [txt_len, 64, 2]: plain (cos, sin)
+ * Rows at or beyond a stream's length are +0, the gap between the padded text and the image in `all` included: every byte of every given
+ * output is written (callers pass uninitialised memory).  Pure data movement -- bit-equal to the torch sequence on the same axis tables; no
+ * atomics; 16-byte stores, consecutive lanes consecutive addresses.
+ * Validation (no launch), SVDQ_E_INVALID: NULL args, NULL pos_cs or neg_cs, no output given; count outside 1 .. 8; an extent below 1;
+ * a position the launch would read at or beyond 4096 (g + F > 4096; max(H, W) - max(H, W) / 2 > 4096 with scale_rope, max(H, W) > 4096
+ * without; txt_start + txt_len > 4096); txt_len or txt_start negative; c_frame / c_height negative or more than 64 together; a pointer
+ * that is not 16-byte aligned; more than 33554432 rows (see the reach below).
+ * ------------------------------------------------------------------------------------------ */
+#define SVDQ_QWEN_ROTARY_MAX_GRIDS 8
+#define SVDQ_QWEN_ROTARY_POSITIONS 4096
+#define SVDQ_QWEN_ROTARY_MAX_ROWS 33554432
+typedef struct svdq_qwen_rotary_args {
+    const float *pos_cs;  /* [4096, 64, 2] fp32 */
+    const float *neg_cs;  /* [4096, 64, 2] fp32 */
+    float *img, *txt, *all, *img_cs, *txt_cs;
+    int32_t grids[3 * SVDQ_QWEN_ROTARY_MAX_GRIDS]; /* (F, H, W) of grid 0, grid 1, ...: by value */
+    int32_t count;        /* grids in use, 1 .. 8 */
+    int32_t txt_len;      /* text rows (0: the text tables are empty, `all` is the image alone) */
+    int32_t txt_start;    /* position of text row 0 */
+    int32_t scale_rope;   /* non-zero: height and width positions centred */
+    int32_t c_frame, c_height; /* channels (complex entries) of the frame and the height axis: 8 and 28 for axes_dim (16, 56, 56) */
+} svdq_qwen_rotary_args;
+
+/* Alignment of the operands of svdq_qwen_rotary: a pointer that is no multiple of its line is refused with SVDQ_E_INVALID before anything is
+ * launched; NULL counts as aligned.
+ *   pos_cs, neg_cs, img, txt, all, img_cs, txt_cs  16 bytes (the outputs are stored in 16-byte pieces; the tables are read in 8-byte pairs) */
+/* Addressing reach:
+ *   rows                a work item is one 16-byte piece and its index a 32-bit unsigned: at most 96 pieces per padded row over the five
+ *                       outputs, so pad(T) + pad(txt_len) <= 33554432 (96 * 2^25 < 2^32); beyond: SVDQ_E_INVALID.  Byte offsets are 64-bit */
+int svdq_qwen_rotary(const svdq_qwen_rotary_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Folded identity cross-attention (PuLID for FLUX; added WITHOUT a version bump: one new symbol and a new args struct, nothing existing
  * changes, so SVDQ_ABI_VERSION stays 24.  reference: PerceiverAttentionCA, nunchaku/models/pulid/encoders_transformer.py:62-128 -- two
  * LayerNorms, to_q, to_kv, a 16-bit softmax and to_out in torch ops, called from FluxModel.cpp's residual_callback).  K and V depend on the

@@ -1361,6 +1361,39 @@ class _Ops:
         args.dtype, args.eps = _DT[qkv.dtype], float(eps)
         _lib.check(lib.svdq_qk_norm_rope(C.byref(args), _stream()), op)
 
+    @staticmethod
+    def qwen_rotary(pos_cs, neg_cs, grids, txt_len, txt_start, scale_rope, c_frame, c_height, img, txt, all_, img_cs, txt_cs):
+        """Extension (Qwen-Image): the rotary tables of ``grids`` (up to 8 ``(frames, height, width)``, their rows back to back) and ``txt_len``
+        text tokens in one launch (``svdq_qwen_rotary``), gathered from the two axis tables ``pos_cs`` / ``neg_cs`` (contiguous float32
+        ``[4096, 64, 2]``).  ``img`` / ``txt`` / ``all_``: packed (sin, cos) tables, float32 ``[rows padded to 256, 128]``; ``img_cs`` / ``txt_cs``:
+        plain float32 ``[rows, 64, 2]``; None skips a table.  Every given output is written completely.  The extents, the positions and the
+        number of grids the library judges."""
+        op, lib, args = "qwen_rotary", _lib.load(), _lib.QwenRotaryArgs()
+        grids = [tuple(int(v) for v in g) for g in grids]
+        if any(len(g) != 3 for g in grids):
+            raise ValueError(f"{op}: a grid is (frames, height, width), got {grids}")
+        for name, t in (("pos_cs", pos_cs), ("neg_cs", neg_cs)):
+            if t is None:
+                continue  # (refused by the library)
+            if t.dtype != torch.float32 or tuple(t.shape) != (_lib.QWEN_ROTARY_POSITIONS, 64, 2) or not t.is_contiguous():
+                raise ValueError(f"{op}: {name} must be a contiguous float32 [{_lib.QWEN_ROTARY_POSITIONS}, 64, 2] tensor")
+        count = len(grids)
+        if count <= _lib.QWEN_ROTARY_MAX_GRIDS and all(min(g) >= 1 for g in grids):  # (else the shapes below mean nothing: the library refuses the call)
+            t_img = sum(f * h * w for f, h, w in grids)
+            pad = lambda n: n + -n % 256
+            want = (("img", img, (pad(t_img), 128)), ("txt", txt, (pad(txt_len), 128)), ("all", all_, (pad(txt_len) + pad(t_img), 128)),
+                    ("img_cs", img_cs, (t_img, 64, 2)), ("txt_cs", txt_cs, (txt_len, 64, 2)))
+            for name, t, shape in want:
+                if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous()):
+                    raise ValueError(f"{op}: {name} must be a contiguous float32 {list(shape)} tensor, got {t.dtype} {list(t.shape)}")
+        args.pos_cs, args.neg_cs = _ptr(pos_cs), _ptr(neg_cs)
+        args.img, args.txt, args.all, args.img_cs, args.txt_cs = _ptr(img), _ptr(txt), _ptr(all_), _ptr(img_cs), _ptr(txt_cs)
+        for k, v in enumerate(v for g in grids[:_lib.QWEN_ROTARY_MAX_GRIDS] for v in g):
+            args.grids[k] = _i32(op, "a grid extent", v)
+        args.count, args.txt_len, args.txt_start = _i32(op, "the number of grids", count), _i32(op, "txt_len", txt_len), _i32(op, "txt_start", txt_start)
+        args.scale_rope, args.c_frame, args.c_height = int(bool(scale_rope)), _i32(op, "c_frame", c_frame), _i32(op, "c_height", c_height)
+        _lib.check(lib.svdq_qwen_rotary(C.byref(args), _stream()), op)
+
 
 class _Utils:
     """reference: csrc/pybind.cpp:118-123 -- logging / sm_75 toggles; no-ops here."""

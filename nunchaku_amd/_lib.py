@@ -209,6 +209,19 @@ class QkNormRopeArgs(C.Structure):
     ]
 
 
+QWEN_ROTARY_MAX_GRIDS, QWEN_ROTARY_POSITIONS = 8, 4096
+
+
+class QwenRotaryArgs(C.Structure):
+    _fields_ = [
+        ("pos_cs", C.c_void_p), ("neg_cs", C.c_void_p),
+        ("img", C.c_void_p), ("txt", C.c_void_p), ("all", C.c_void_p), ("img_cs", C.c_void_p), ("txt_cs", C.c_void_p),
+        ("grids", C.c_int32 * (3 * QWEN_ROTARY_MAX_GRIDS)),
+        ("count", C.c_int32), ("txt_len", C.c_int32), ("txt_start", C.c_int32), ("scale_rope", C.c_int32),
+        ("c_frame", C.c_int32), ("c_height", C.c_int32),
+    ]
+
+
 class PulidCaArgs(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("stats", C.c_void_p), ("a_fold", C.c_void_p), ("colsum", C.c_void_p), ("cbias", C.c_void_p),
@@ -242,6 +255,7 @@ EXPORTS = {
     "svdq_sandwich_norm": (C.c_int, [C.POINTER(SandwichNormArgs), C.c_void_p]),
     "svdq_qk_norm_rope": (C.c_int, [C.POINTER(QkNormRopeArgs), C.c_void_p]),
     "svdq_pulid_ca": (C.c_int, [C.POINTER(PulidCaArgs), C.c_void_p]),
+    "svdq_qwen_rotary": (C.c_int, [C.POINTER(QwenRotaryArgs), C.c_void_p]),
     "svdq_gemm_workspace_bytes": (C.c_int64, []),
     "svdq_gemm_workspace_bytes_for": (C.c_int64, [C.POINTER(GemmArgs)]),
     "svdq_gemm_workspace_status": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -5,7 +5,7 @@ import subprocess
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libsvdq_amd.so")
-SOURCES = ["repack.hip", "quantize.hip", "gemm_w4a4.hip", "attention.hip", "gemv_awq.hip", "gemv_awq_lora.hip", "gemm_awq.hip", "residual.hip", "residual_diff.hip", "modulated_diff.hip", "ip_attention.hip", "linear_attention.hip", "dwconv.hip", "cross_attention.hip", "sana_glue.hip", "attention_d64.hip", "sandwich_norm.hip", "qk_norm_rope.hip", "pulid_ca.hip"]
+SOURCES = ["repack.hip", "quantize.hip", "gemm_w4a4.hip", "attention.hip", "gemv_awq.hip", "gemv_awq_lora.hip", "gemm_awq.hip", "residual.hip", "residual_diff.hip", "modulated_diff.hip", "ip_attention.hip", "linear_attention.hip", "dwconv.hip", "cross_attention.hip", "sana_glue.hip", "attention_d64.hip", "sandwich_norm.hip", "qk_norm_rope.hip", "pulid_ca.hip", "qwen_rotary.hip"]
 # -ffp-contract=off: the quantiser's arithmetic is specified operation by operation;
 # the hot loop uses explicit fma.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared"]

@@ -32,6 +32,7 @@ from ..ops.attention import attention_packed, kv_valid_ranges, q_prescale
 from ..ops.elementwise import residual_diff, residual_gate_stats
 from ..ops.fused import fused_qkv_norm_rottary, fused_qkv_norm_rottary_pair, linear_pair
 from ..ops.gemv import awq_gemv_w4a16_batched, awq_gemv_w4a16_cuda
+from ..ops.rotary import QWEN_ROTARY_TABLES, qwen_rotary
 from ..utils import pad_tensor
 from . import blocks
 from .blocks import FeedForward as NunchakuFeedForward, _GELUProj  # noqa: F401  (reference: models/attention.py:76-123)
@@ -170,6 +171,76 @@ def qwen_rope_freqs(img_shape: tuple[int, int, int], txt_len: int, axes_dim=(16,
     tpos = torch.arange(start, start + txt_len, device=device)
     txt = torch.cat([axis(tpos, d) for d in axes_dim], dim=-1)
     return img, txt
+
+
+ROPE_THETA = 10000.0
+ROPE_POSITIONS = 4096  # positions per sign the axis tables hold (diffusers builds its own for 4096 at construction)
+
+
+def _rope_axis(pos: torch.Tensor, d: int, theta: float, device) -> torch.Tensor:
+    """``exp(i * pos * theta^(-2j/d))`` -- the expressions of :func:`qwen_rope_freqs`'s ``axis``, operation for operation"""
+    inv = 1.0 / theta ** (torch.arange(0, d, 2, dtype=torch.float32, device=device) / d)
+    return torch.polar(torch.ones(len(pos), d // 2, device=device), pos.float()[:, None] * inv[None])
+
+
+def qwen_rope_freqs_multi(grids, txt_len: int, axes_dim=(16, 56, 56), theta: float = 10000.0, scale_rope: bool = True, device="cpu"):
+    """:func:`qwen_rope_freqs` for SEVERAL latent grids whose tokens follow each other in the image stream -- what diffusers'
+    ``QwenEmbedRope.forward`` / ``_compute_video_freqs`` make of ``img_shapes = [[(1, h, w), (1, h1, w1), ...]]`` (the Edit pipelines: the noise
+    latents, then the reference images).  Grid number ``idx`` of shape (frames, height, width): frame positions ``idx .. idx + frames - 1``,
+    height and width positions centred per grid when ``scale_rope``; a grid's table is the three axis parts side by side, flattened
+    frame-major, then height, then width; the image table is the grids' tables in order.  The text positions start behind the largest half
+    extent of ANY grid (``max(height // 2, width // 2)`` over the grids; ``max(height, width)`` without ``scale_rope``).
+    -> (img_freqs [sum F*H*W, 64] complex64, txt_freqs [txt_len, 64] complex64); for one grid ``torch.equal`` to :func:`qwen_rope_freqs`."""
+    grids = [tuple(int(v) for v in g) for g in grids]
+    if not grids or any(len(g) != 3 or min(g) < 1 for g in grids):
+        raise ValueError(f"qwen_rope_freqs_multi: grids must be a non-empty list of (frames, height, width) with extents >= 1, got {grids}")
+
+    def centred(n):
+        return torch.cat([torch.arange(-(n - n // 2), 0, device=device), torch.arange(0, n // 2, device=device)]) if scale_rope \
+            else torch.arange(n, device=device)
+
+    parts = []
+    for idx, (frame, height, width) in enumerate(grids):
+        ff = _rope_axis(torch.arange(idx, idx + frame, device=device), axes_dim[0], theta, device)[:, None, None, :].expand(frame, height, width, -1)
+        fh = _rope_axis(centred(height), axes_dim[1], theta, device)[None, :, None, :].expand(frame, height, width, -1)
+        fw = _rope_axis(centred(width), axes_dim[2], theta, device)[None, None, :, :].expand(frame, height, width, -1)
+        parts.append(torch.cat([ff, fh, fw], dim=-1).reshape(frame * height * width, -1))
+    img = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+    start = max(max(h // 2, w // 2) if scale_rope else max(h, w) for _, h, w in grids)
+    tpos = torch.arange(start, start + txt_len, device=device)
+    txt = torch.cat([_rope_axis(tpos, d, theta, device) for d in axes_dim], dim=-1)
+    return img, txt
+
+
+def qwen_rope_axis_tables(axes_dim=(16, 56, 56), theta: float = 10000.0, device="cpu"):
+    """The two tables every rotary table of a Qwen-Image step is a gather from (``ops.qwen_rotary``): float32 ``[4096, 64, 2]`` (cos, sin),
+    the channels of the frame, height and width axes side by side.  ``pos_cs[k]`` holds position ``k``; ``neg_cs[k]`` holds position
+    ``-(k + 1)``.  Built with the expressions of :func:`qwen_rope_freqs` on ``device``: the same fp32 product ``float(pos) * inv[j]`` and
+    the same elementwise ``polar`` there, so an entry gathered from them has the bits of the entry :func:`qwen_rope_freqs` computes."""
+    pos = torch.arange(ROPE_POSITIONS, device=device)
+
+    def table(p):
+        return torch.view_as_real(torch.cat([_rope_axis(p, d, theta, device) for d in axes_dim], dim=-1)).contiguous()
+
+    return table(pos), table(-(pos + 1))
+
+
+def latent_grids(img_shapes, t_img: int) -> list:
+    """The latent grids of a forward's ``img_shapes`` in any of its spellings -- ``[(f, h, w)]``, ``[[(f, h, w)]]``, ``[[(f, h, w), (f1, h1,
+    w1), ...]]`` (batch entry 0; the Edit pipelines pass the noise grid and the reference images' grids) -- or, without ``img_shapes``, the
+    square grid of ``t_img`` tokens.  Several grids must account for every one of the ``t_img`` image tokens (ValueError)."""
+    if not img_shapes:
+        side = int(math.isqrt(t_img))
+        return [(1, side, side)]
+    shape = img_shapes[0]
+    grids = list(shape) if isinstance(shape, (list, tuple)) and isinstance(shape[0], (list, tuple)) else [shape]
+    grids = [tuple(int(v) for v in g) for g in grids]
+    if len(grids) > 1:
+        rows = sum(f * h * w for f, h, w in grids)
+        if rows != t_img:
+            raise ValueError(f"img_shapes {grids} describe {rows} image tokens, hidden_states has {t_img}: the rotary table would not fit the "
+                             "image stream (the noise latents and every reference image must be listed, in the order of their tokens)")
+    return grids
 
 
 class NunchakuQwenImageTransformerBlock(nn.Module):
@@ -405,7 +476,9 @@ class NunchakuQwenImageTransformer2DModel(_DiffusersQwen if HAVE_DIFFUSERS_QWEN 
     def forward(self, hidden_states, encoder_hidden_states=None, encoder_hidden_states_mask=None, timestep=None, img_shapes=None,
                 txt_seq_lens=None, guidance=None, attention_kwargs=None, controlnet_block_samples=None, return_dict: bool = True):
         """hidden_states [1, T_img, 64] (packed 2x2 latent patches); encoder_hidden_states [1, T_txt, 3584]; timestep [1] (already
-        divided by 1000 by the pipeline); img_shapes [(frames, H/2, W/2)] of the latent grid.  -> [1, T_img, 64].
+        divided by 1000 by the pipeline); img_shapes [(frames, H/2, W/2)] of the latent grid, or -- the Edit pipelines -- [[(1, h, w), (1, h1, w1),
+        ...]]: the noise latents' grid and the reference images' grids, whose tokens follow the noise tokens in hidden_states (:func:`latent_grids`).
+        -> [1, T_img, 64]: every image row, reference-image rows included (the Edit pipelines cut the noise rows off themselves).
         The step is its stages run back to back (``_prologue``, ``_launch_mods``, ``_run_blocks``, ``_tail``); :meth:`forward_cached`
         is the same stages with the First-Block-Cache decision in between."""
         st = self._prologue(hidden_states, encoder_hidden_states, encoder_hidden_states_mask, timestep, img_shapes, attention_kwargs,
@@ -419,26 +492,12 @@ class NunchakuQwenImageTransformer2DModel(_DiffusersQwen if HAVE_DIFFUSERS_QWEN 
                   attention_kwargs=None, controlnet_block_samples=None) -> "_Step":
         """Embedders, rotary tables, padding of the two streams and their first LayerNorm statistics."""
         dt = self.dtype_
+        grids = latent_grids(img_shapes, hidden_states.shape[1])  # (refuses grids that do not add up to the image stream before anything is launched)
         hidden = self.img_in(hidden_states)
         enc = self.txt_in(self.txt_norm(encoder_hidden_states))
         temb = self.time_text_embed(timestep.to(dt), dt)
         t_txt, t_img = enc.shape[1], hidden.shape[1]
-        shape = img_shapes[0] if img_shapes else (1, int(math.isqrt(hidden.shape[1])), int(math.isqrt(hidden.shape[1])))
-        if isinstance(shape, (list, tuple)) and isinstance(shape[0], (list, tuple)):
-            shape = shape[0]
-        # the rotary tables depend on the grid, the text length and the device only: built once per (shape, length) and kept (one entry) --
-        # except while the stream is capturing: then they are computed inside the graph, whose pool owns them (a graph must not point at
-        # tables that only this cache keeps alive: the next eager call with another grid would free them under it; models/flux.py)
-        rkey = (tuple(shape), t_txt, str(hidden.device))
-        use_cache = not (hidden.is_cuda and torch.cuda.is_current_stream_capturing())
-        cached = getattr(self, "_rot_cache", None) if use_cache else None
-        if cached is not None and cached[0] == rkey:
-            rot = cached[1]
-        else:
-            rot = pack_qwen_rotary(*qwen_rope_freqs(tuple(shape), t_txt, self.axes, device=hidden.device))
-            if use_cache:
-                self._rot_cache = (rkey, rot)
-        compute_stream = torch.cuda.current_stream()
+        compute_stream = torch.cuda.current_stream() if hidden.is_cuda else None
         if self.offload:
             self.offload_manager.initialize(compute_stream)
         # EVERY token count runs the hot path (the reference pads any M to 256 rows, Linear.cpp:445-446; its own quality gate is 1664 x 928 =
@@ -451,6 +510,23 @@ class NunchakuQwenImageTransformer2DModel(_DiffusersQwen if HAVE_DIFFUSERS_QWEN 
         if kv_valid is not None:
             enc, hidden = F.pad(enc, (0, 0, 0, -t_txt % 256)), F.pad(hidden, (0, 0, 0, -t_img % 256))
         fused = self.fused_norm and hot and enc.shape[1] % 256 == 0 and hidden.shape[1] % 256 == 0
+        # the fused blocks read the joint table alone; the torch-op blocks may read any of the five (NunchakuQwenAttention.forward)
+        tables = ("all",) if hidden.is_cuda and fused else QWEN_ROTARY_TABLES
+        # the rotary tables depend on the grids, the text length and the device only: built once per (grids, length) and kept (one entry) --
+        # except while the stream is capturing: then they are computed inside the graph, whose pool owns them (a graph must not point at
+        # tables that only this cache keeps alive: the next eager call with another grid would free them under it; models/flux.py)
+        rkey = (tuple(grids), t_txt, str(hidden.device), tables)
+        use_cache = not (hidden.is_cuda and torch.cuda.is_current_stream_capturing())
+        cached = getattr(self, "_rot_cache", None) if use_cache else None
+        if cached is not None and cached[0] == rkey:
+            rot = cached[1]
+        else:
+            if hidden.is_cuda:  # one gather launch from the axis tables (inside a captured graph: one kernel node)
+                rot = qwen_rotary(*self._rope_axis_tables(hidden.device, use_cache), grids, t_txt, axes_dim=self.axes, tables=tables)
+            else:
+                rot = pack_qwen_rotary(*qwen_rope_freqs_multi(grids, t_txt, self.axes, device=hidden.device))
+            if use_cache:
+                self._rot_cache = (rkey, rot)
         st = _Step()
         st.hidden, st.enc, st.temb, st.rot, st.kv_valid, st.t_txt, st.t_img, st.fused = hidden, enc, temb, rot, kv_valid, t_txt, t_img, fused
         st.mask, st.attention_kwargs, st.cn, st.compute_stream = encoder_hidden_states_mask, attention_kwargs, controlnet_block_samples, compute_stream
@@ -459,6 +535,19 @@ class NunchakuQwenImageTransformer2DModel(_DiffusersQwen if HAVE_DIFFUSERS_QWEN 
             st.temb_act = F.silu(temb)  # img_mod[0] / txt_mod[0] of every block: the same SiLU of the same embedding
             st.stats = ((residual_gate_stats(hidden)[1], None), (residual_gate_stats(enc)[1], None))  # (image, text), each with its ZeroPool
         return st
+
+    def _rope_axis_tables(self, device, keep: bool = True):
+        """(pos_cs, neg_cs) of :func:`qwen_rope_axis_tables` on ``device``: built at the first step there and kept, once per (device, axes,
+        theta) -- plain attributes, no buffers: ``state_dict()`` and the strict loads do not see them.  ``keep`` False (a first step that
+        runs under stream capture): the tables are built inside the graph, whose pool owns them, and not kept."""
+        tables = self.__dict__.setdefault("_rope_tables", {})
+        key = (str(device), tuple(self.axes), ROPE_THETA)
+        got = tables.get(key)
+        if got is None:
+            got = qwen_rope_axis_tables(self.axes, ROPE_THETA, device)
+            if keep:
+                tables[key] = got
+        return got
 
     def _launch_mods(self, st: "_Step", lo: int, hi: int) -> None:
         """The modulation projections of blocks ``lo .. hi - 1`` (two each) in one batched GEMV launch, +1 on the scale rows in one op
@@ -521,7 +610,8 @@ class NunchakuQwenImageTransformer2DModel(_DiffusersQwen if HAVE_DIFFUSERS_QWEN 
         it has for FLUX only): the stages of :meth:`forward` with the decision of ``caching.fbcache.check_and_apply_cache`` in between.
 
         The first ``first_blocks`` blocks always run (``1 <= first_blocks < num_layers``), with only their modulation projections
-        launched.  What they did to the REAL image rows (``[:t_img]``; the rows that pad the stream to 256 never enter a sum) is compared
+        launched.  What they did to the REAL image rows (``[:t_img]``; the rows that pad the stream to 256 never enter a sum; under an Edit
+        pipeline -- several grids in ``img_shapes`` -- the rows of the reference images are real rows and are included) is compared
         with the same residual of the last computed step of the same ``branch`` (``svdq_residual_diff``: subtraction and comparison in
         one pass).  Hit (``ratio < residual_diff_threshold``): the stored residual of the other blocks is added to the image rows (one
         ``svdq_residual_gate_stats`` pass) and the tail runs -- nothing of the other blocks is launched, and the text stream stays as it
