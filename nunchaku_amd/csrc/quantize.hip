@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256, OCC) void quantize_kernel(const typename Half<
             // q = rne(x_hat / scale) as FP6 e2m3 = q/8, packed 32 x 6 bits: ONE v_cvt_scalef32_2xpk16_fp6_f32 (scale 8 =
             // divide by 2^3; element 2i from the first source, 2i+1 from the second; RNE; |x_hat/scale| <= 7 by
             // construction so the -8..7 clamp never fires; probed on gfx950 with tools/ubench5.hip) instead of
-            // rint / clamp / sign-magnitude encode / shift / or per element.
+            // rint / clamp / sign-magnitude encode / shift / or per element.  "By construction" is pinned, not assumed: tests/test_gpu_quantiser_profiles.py::test_every_16_bit_amax_gives_the_oracles_codes_and_scale feeds EVERY positive finite 16-bit value as amax to both families and finds x = +-amax at +-7, and every other code and scale bit, equal to the IEEE oracle's wherever the fp32 scale is a normal number (all of fp16; bf16 from 8.3e-38 up); the same file holds all five copies of this quantiser to the converter's ties-to-even.
             // NaN: FP6 has no NaN encoding and the converter emits 0x3F for one (sign + largest magnitude, -7.5: measured on an MI355X by
             // tests/test_gpu_numeric_edges.py before nan_to_zero() -- one v_med3_f32 -- was added; attention.hip's quantiser has no such guard), where the reference's cvt.rni gives code 0 (gemm_w4a4.cuh:483-497).  A NaN
             // arrives here as a NaN input element (fmaxf above skips it, as __hmax does) or as inf * 0 in a group holding +-inf (scale inf, rscale 0):
