@@ -789,6 +789,52 @@ typedef struct svdq_attention_d64_args {
 int svdq_attention_d64(const svdq_attention_d64_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Attention at head dimension 64 with a relative-position score bias and an optional per-key bias (the self-attention of the T5 text
+ * encoder; added WITHOUT a version bump: one new symbol and a new args struct, nothing existing changes, so SVDQ_ABI_VERSION stays 24.
+ * reference: transformers' T5Attention -- three view / transpose copies, a [B, H, T, N] score matmul rounded to 16 bits, the add of the
+ * [1, H, T, N] position bias, the add of the mask, a softmax, a second matmul and a copy back).
+ * Per sample b < B, head h < H, query t < T and keys n < N:
+ *   out[b, t, h, :] = round16( softmax_n(scale * q[b, t, h, :] . k[b, n, h, :] + rel_bias[h, n - t + T - 1] + key_bias[b, n]) . v[b, n, h, :] )
+ * rel_bias is [H, T + N - 1] fp32, contiguous, required: one Toeplitz vector per head, entry d + T - 1 for the distance d = key - query
+ * (T5: relative_attention_bias[bucket(d), h]); no [H, T, N] tensor exists anywhere.  key_bias is [B, N] fp32, contiguous, or NULL (zeros):
+ * a padding mask.  Both are added to the fp32 score, never to a rounded one.
+ * q, k, v, out and the fields in front of rel_bias are svdq_attention_d64_args' field for field, with its conventions: strides in elements,
+ * the thirds of one packed buffer or separate buffers read in place, bf16 and fp16, no workspace, no atomics, no synchronisation: the call
+ * can be captured and two launches are bit-identical.  The online softmax is svdq_attention_d64's (64-key chunks from key 0; probabilities
+ * rounded to 16 bits before they meet V, the row sum over the rounded values, the division last).
+ * Exclusion: a key_bias value at or below -2^100 (-inf and torch.finfo(bfloat16).min included; NaN too) EXCLUDES its key: probability
+ * exactly 0.  (Such a value times log2(e) overflows fp32; the rule replaces the arithmetic.)  A row all of whose keys are excluded is
+ * written as zeros, as a sample without keys is by svdq_cross_attention.  Excluded keys are still loaded: in a 64-key chunk (keys 64 c ..
+ * 64 c + 63) that holds at least one key that is not excluded, the excluded keys' rows of k and v enter the matrix unit with weight 0 and
+ * must be finite; a chunk all of whose keys are excluded is skipped and what its rows of k and v hold changes nothing.  rel_bias must be
+ * finite (not checked: it lives on the device).  Rows of k / v at or beyond N, rows of q / out at or beyond T, columns beyond H * 64,
+ * rel_bias outside its H * (T + N - 1) floats and key_bias outside its B * N floats are neither read nor written.
+ * Validation (no launch): svdq_attention_d64's list, and SVDQ_E_INVALID for a NULL rel_bias, a rel_bias or key_bias that is not 4-byte
+ * aligned, T + N - 1 > 2^31, out overlapping rel_bias or key_bias.  SVDQ_E_UNSUPPORTED: head_dim != 64.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct svdq_attention_d64_bias_args {
+    const void *q;   /* [B][T, H * 64] 16-bit, row stride ldq, batch stride q_bs */
+    const void *k;   /* [B][N, H * 64], row stride ldk, batch stride k_bs */
+    const void *v;   /* [B][N, H * 64], row stride ldv, batch stride v_bs */
+    void *out;       /* [B][T, H * 64], row stride ldo, batch stride out_bs */
+    int64_t q_bs, k_bs, v_bs, out_bs; /* in elements; ignored at B = 1 */
+    int32_t ldq, ldk, ldv, ldo;       /* in elements */
+    int32_t B, T, H, N;
+    int32_t head_dim; /* 64 */
+    int32_t dtype;
+    float scale;      /* 1.0 in T5 */
+    int32_t reserved;
+    const float *rel_bias; /* [H, T + N - 1] fp32 contiguous */
+    const float *key_bias; /* [B, N] fp32 contiguous, or NULL */
+} svdq_attention_d64_bias_args;
+
+/* Addressing reach (svdq_attention_d64's):
+ *   ldq, ldk, ldv, ldo  the field's width: (size_t)row * ld
+ *   q_bs, k_bs, v_bs, out_bs   int64: (size_t)b * bs
+ *   B * H               at most 65535        T, N  at most 2^30 (the grid)        T * ld, N * ld, B * bs, head * (T + N - 1), b * N  64-bit products */
+int svdq_attention_d64_bias(const svdq_attention_d64_bias_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * SANA block glue (the element-wise passes between the three layers of a SANA block; added WITHOUT a version bump: one new symbol and a
  * new args struct, nothing existing changes, so SVDQ_ABI_VERSION stays 24.  reference: SanaLinearTransformerBlock::forward,
  * src/SanaModel.cpp:234-322 -- a copy of timestep, one add of scale_shift_table, two LayerNorms and five mul_add_batch launches per block;

@@ -1260,6 +1260,40 @@ class _Ops:
         _lib.check(lib.svdq_attention_d64(C.byref(a), _stream()), "attention_d64")
 
     @staticmethod
+    def attention_d64_bias(q, k, v, out, rel_bias, key_bias, scale):
+        """Extension (T5): ``attention_d64`` with ``rel_bias[h, n - t + T - 1] + key_bias[b, n]`` added to the fp32 scores
+        (``svdq_attention_d64_bias``).  ``q`` / ``k`` / ``v`` / ``out``: as for ``attention_d64``.  ``rel_bias``: float32 ``[H, T + N - 1]``,
+        ``key_bias``: float32 ``[B, N]`` or None, both contiguous.  A ``key_bias`` value at or below ``-2**100`` excludes its key."""
+        op, lib = "attention_d64_bias", _lib.load()
+        named = (("q", q), ("k", k), ("v", v), ("out", out))
+        for name, t in named:
+            if t is None or t.dim() != 4 or t.stride(3) != 1 or (t.shape[2] > 1 and t.stride(2) != t.shape[3]):
+                raise ValueError(f"{op}: {name} must be a [B, rows, H, D] view with unit channel stride and heads D elements apart")
+        if q.dtype not in _DT or k.dtype != q.dtype or v.dtype != q.dtype or out.dtype != q.dtype:
+            raise ValueError(f"{op}: q, k, v, out must share one 16-bit dtype (bfloat16 or float16)")
+        B, T, H, D = q.shape
+        N = k.shape[1]
+        if tuple(out.shape) != (B, T, H, D) or tuple(k.shape) != (B, N, H, D) or tuple(v.shape) != (B, N, H, D):
+            raise ValueError(f"{op}: expected q / out [B, T, H, D] and k / v [B, N, H, D]")
+        for name, t, shape in (("rel_bias", rel_bias, (H, T + N - 1)), ("key_bias", key_bias, (B, N))):
+            if t is None and name == "key_bias":
+                continue
+            if t is None or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{op}: {name} must be a contiguous float32 {list(shape)} tensor")
+        for t in (q, k, v, out, rel_bias, key_bias):
+            if t is not None and not t.is_cuda:
+                raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
+        a = _lib.AttentionD64BiasArgs()
+        a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+        a.rel_bias, a.key_bias = rel_bias.data_ptr(), None if key_bias is None else key_bias.data_ptr()
+        # (the strides of dimensions of size 1 are arbitrary in torch: the library gets the natural ones)
+        a.ldq, a.ldk, a.ldv, a.ldo = (_i32(op, f"{n} row stride", t.stride(1) if t.shape[1] > 1 else H * D) for n, t in named)
+        a.q_bs, a.k_bs, a.v_bs, a.out_bs = (_i64(op, f"{n} batch stride", t.stride(0) if B > 1 else 0) for n, t in named)
+        a.B, a.T, a.H, a.N, a.head_dim = (_i32(op, n, val) for n, val in (("B", B), ("T", T), ("H", H), ("N", N), ("head_dim", D)))
+        a.dtype, a.scale = _DT[q.dtype], float(scale)
+        _lib.check(lib.svdq_attention_d64_bias(C.byref(a), _stream()), op)
+
+    @staticmethod
     def sana_glue(res, a, timestep, gate_table, mod_table, out, out_mod, stats, T, C_feat, C_pad, lds, gate_row=-1, scale_row=0, shift_row=0, eps=1e-6):
         """Extension (SANA): the glue pass of a SANA block (``svdq_sana_glue``): the gated residual ``t`` of ``res`` and ``a``, written to ``out``,
         its LayerNorm statistics to ``stats`` and the LayerNorm modulated per sample with rows ``scale_row`` / ``shift_row`` of

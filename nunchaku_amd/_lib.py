@@ -177,6 +177,11 @@ class AttentionD64Args(C.Structure):
     ]
 
 
+class AttentionD64BiasArgs(AttentionD64Args):
+    """svdq_attention_d64_bias_args: svdq_attention_d64_args field for field, then the two bias operands"""
+    _fields_ = [("rel_bias", C.c_void_p), ("key_bias", C.c_void_p)]
+
+
 class SanaGlueArgs(C.Structure):
     _fields_ = [
         ("res", C.c_void_p), ("a", C.c_void_p), ("timestep", C.c_void_p), ("gate_table", C.c_void_p), ("mod_table", C.c_void_p),
@@ -252,6 +257,7 @@ EXPORTS = {
     "svdq_cross_attention": (C.c_int, [C.POINTER(CrossAttentionArgs), C.c_void_p]),
     "svdq_sana_glue": (C.c_int, [C.POINTER(SanaGlueArgs), C.c_void_p]),
     "svdq_attention_d64": (C.c_int, [C.POINTER(AttentionD64Args), C.c_void_p]),
+    "svdq_attention_d64_bias": (C.c_int, [C.POINTER(AttentionD64BiasArgs), C.c_void_p]),
     "svdq_sandwich_norm": (C.c_int, [C.POINTER(SandwichNormArgs), C.c_void_p]),
     "svdq_qk_norm_rope": (C.c_int, [C.POINTER(QkNormRopeArgs), C.c_void_p]),
     "svdq_pulid_ca": (C.c_int, [C.POINTER(PulidCaArgs), C.c_void_p]),

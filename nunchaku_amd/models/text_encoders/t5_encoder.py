@@ -1,6 +1,8 @@
 """NunchakuT5EncoderModel: the 4-bit (AWQ W4A16, group 128) T5 text encoder of the FLUX pipelines, loaded from one local
 ``.safetensors`` file (role of the reference's ``nunchaku/models/text_encoders/t5_encoder.py``).  Every ``nn.Linear`` with a
-``<name>.qweight`` entry in the file becomes a :class:`W4Linear`; everything else is transformers' ``T5EncoderModel``.
+``<name>.qweight`` entry in the file becomes a :class:`W4Linear`; everything else is transformers' ``T5EncoderModel``, except its attention:
+on a GPU, at ``d_kv == 64``, the encoder's self-attention runs as one ``ops.attention_d64_bias`` launch per layer (:func:`fused_t5_attention`,
+registered with transformers' attention-function registry under :data:`ATTENTION_NAME`; ``T5Attention.forward`` itself is not touched).
 transformers is imported when this module is."""
 
 import json
@@ -12,7 +14,9 @@ from transformers import T5Config, T5EncoderModel
 
 from .linear import W4Linear
 
-__all__ = ["NunchakuT5EncoderModel"]
+__all__ = ["NunchakuT5EncoderModel", "ATTENTION_NAME", "fused_t5_attention", "toeplitz_rel_bias"]
+
+ATTENTION_NAME = "nunchaku_amd_t5_d64"  # the name ``config._attn_implementation`` carries when the fused attention is selected
 
 # tied embedding of T5EncoderModel: a file that stores one of the two names serves both
 _TIED = ("shared.weight", "encoder.embed_tokens.weight")
@@ -29,13 +33,111 @@ def _read_safetensors(path: str) -> tuple[dict, dict]:
     return tensors, meta
 
 
+def toeplitz_rel_bias(position_bias: torch.Tensor) -> torch.Tensor:
+    """The float32 ``[H, T + N - 1]`` vector per head behind a ``[1, H, T, N]`` position bias that depends on ``key - query`` only
+    (``T5Attention.compute_bias``): entry ``d + T - 1`` holds the bias of distance ``d`` -- column 0 reversed (d = -(T-1) .. -1), then row 0
+    (d = 0 .. N-1).  Built once per tensor and version (the 24 layers of an encoder share one position bias)."""
+    from ..._C import _cached_conversion
+
+    def build(pb):
+        return torch.cat((pb[0, :, 1:, 0].flip(-1), pb[0, :, 0, :]), dim=-1).float().contiguous()
+
+    return _cached_conversion(position_bias, "t5_toeplitz", build)
+
+
+def _key_bias(mask, B: int, N: int):
+    """``(True, key_bias)`` for a mask the kernel takes -- None, ``[B, 1, 1, N]``, or ``[B, 1, T, N]`` expanded along T (stride 0): float32
+    ``[B, N]`` or None; ``(False, None)`` for any other mask (it may vary along queries or heads)."""
+    if mask is None:
+        return True, None
+    if (not isinstance(mask, torch.Tensor) or mask.dim() != 4 or not mask.is_floating_point() or mask.shape[0] != B or mask.shape[1] != 1
+            or mask.shape[3] != N or not (mask.shape[2] == 1 or mask.stride(2) == 0)):
+        return False, None
+    from ..._C import _cached_conversion
+
+    return True, _cached_conversion(mask, "t5_key_bias", lambda m: m[:, 0, 0, :].float().contiguous())
+
+
+def _serves(module, query, key, value, attention_mask, dropout, position_bias) -> bool:
+    """whether the kernel serves this call, from shapes, strides, dtypes and flags alone (the device is the caller's question)"""
+    B, H, T, D = query.shape
+    N = key.shape[2]
+    return bool(D == 64 and not getattr(module, "is_decoder", False) and not (module.training and dropout > 0.0)
+                and query.dtype in (torch.bfloat16, torch.float16) and key.dtype == query.dtype and value.dtype == query.dtype
+                and isinstance(position_bias, torch.Tensor) and tuple(position_bias.shape) == (1, H, T, N) and tuple(value.shape) == tuple(key.shape)
+                and not (torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad or position_bias.requires_grad))
+                # [B, H, rows, 64] views of token-major [B, rows, H * 64] projections
+                and all(t.stride(3) == 1 and (H == 1 or t.stride(1) == 64) for t in (query, key, value))
+                and _key_bias(attention_mask, B, N)[0])
+
+
+def fused_t5_attention(module, query, key, value, attention_mask, scaling=None, dropout=0.0, position_bias=None, **kwargs):
+    """An attention function for transformers' registry (the signature of its ``eager_attention_forward``): the T5 encoder's self-attention as one
+    ``ops.attention_d64_bias`` launch.  ``query`` / ``key`` / ``value`` are the ``[B, H, T, 64]`` transposed views of the projections' outputs:
+    they are taken back to their token-major ``[B, T, H * 64]`` rows without a copy; the ``[1, H, T, N]`` position bias becomes its Toeplitz
+    vector (:func:`toeplitz_rel_bias`), a padding mask the kernel's ``key_bias``.  Returns ``([B, T, H, 64], None)``.
+    Everything else goes to transformers' own eager function, unchanged: a CPU tensor, ``d_kv != 64``, a decoder, training with dropout or
+    with gradients, a mask that varies along queries or heads, a position bias that is not ``[1, H, T, N]``, projections that are not
+    token-major rows.
+    One visible difference from the eager function: a sample whose padding mask leaves NO key (``finfo(bfloat16).min`` on every key) comes out
+    as exact zeros here, where eager's softmax over ``finfo.min + score`` gives a weighting of the padded keys."""
+    if not (query.is_cuda and _serves(module, query, key, value, attention_mask, dropout, position_bias)):
+        from transformers.models.t5.modeling_t5 import eager_attention_forward
+
+        return eager_attention_forward(module, query, key, value, attention_mask, scaling=scaling, dropout=dropout, position_bias=position_bias,
+                                       **kwargs)
+    from ...ops.attention import attention_d64_bias
+
+    B, H, T, _ = query.shape
+    rows = [t.transpose(1, 2) for t in (query, key, value)]
+    q, k, v = (r.flatten(2) if r.stride(2) == 64 else r.reshape(B, -1, H * 64) for r in rows)
+    out = attention_d64_bias(q, k, v, H, toeplitz_rel_bias(position_bias), _key_bias(attention_mask, B, key.shape[2])[1],
+                             scale=1.0 if scaling is None else scaling)
+    return out.unflatten(-1, (H, 64)), None
+
+
+def _padding_mask(batch_size, q_length, kv_length, q_offset=0, kv_offset=0, mask_function=None, attention_mask=None, dtype=torch.float32,
+                  use_vmap=False, **kwargs):
+    """The mask function that goes with :data:`ATTENTION_NAME` (transformers drops the mask of an attention name it has no mask function
+    for): a 2-D padding mask of a bidirectional encoder becomes the additive ``[B, 1, 1, N]`` tensor -- 0 / ``finfo(dtype).min`` -- it is, not
+    the ``[B, 1, T, N]`` copies of it that the eager mask function materialises; no mask stays None.  Anything else is the eager mask function's."""
+    from transformers.masking_utils import bidirectional_mask_function, eager_mask
+
+    if (mask_function is bidirectional_mask_function and not use_vmap and isinstance(q_offset, int) and q_offset == 0
+            and isinstance(kv_offset, int) and kv_offset == 0):
+        if attention_mask is None:
+            return None
+        if attention_mask.dim() == 2 and tuple(attention_mask.shape) == (batch_size, kv_length):
+            keep = attention_mask.to(torch.bool)[:, None, None, :]
+            return torch.where(keep, torch.zeros((), dtype=dtype, device=keep.device), torch.finfo(dtype).min)
+    return eager_mask(batch_size=batch_size, q_length=q_length, kv_length=kv_length, q_offset=q_offset, kv_offset=kv_offset,
+                      mask_function=mask_function, attention_mask=attention_mask, dtype=dtype, use_vmap=use_vmap, **kwargs)
+
+
+def register_fused_attention() -> bool:
+    """Put :func:`fused_t5_attention` and its mask function into transformers' registries; False when the installed transformers has none
+    (the model then runs transformers' eager attention, as before)."""
+    try:
+        from transformers.masking_utils import ALL_MASK_ATTENTION_FUNCTIONS, bidirectional_mask_function, eager_mask  # noqa: F401
+        from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
+        from transformers.models.t5.modeling_t5 import eager_attention_forward  # noqa: F401
+    except ImportError:
+        return False
+    if ATTENTION_NAME not in ALL_ATTENTION_FUNCTIONS:
+        ALL_ATTENTION_FUNCTIONS.register(ATTENTION_NAME, fused_t5_attention)
+        ALL_MASK_ATTENTION_FUNCTIONS.register(ATTENTION_NAME, _padding_mask)
+    return True
+
+
 class NunchakuT5EncoderModel(T5EncoderModel):
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path: str | os.PathLike, **kwargs) -> T5EncoderModel:
         """``pretrained_model_name_or_path``: a local ``.safetensors`` file whose metadata entry ``config`` holds the T5 config
         as JSON (hub names are not resolved).  ``torch_dtype`` (default bfloat16) is the compute dtype, ``device`` (default
         ``"cuda"``) where the model is materialised.  The model is built on the meta device, its quantised linears swapped
-        for W4Linear (group 128), then materialised and loaded with ``strict=True``."""
+        for W4Linear (group 128), then materialised and loaded with ``strict=True``.  ``fused_attention`` (default True) selects
+        :func:`fused_t5_attention` on the model's config when the device is a GPU, ``d_kv == 64`` and the model is an encoder; False keeps
+        transformers' eager attention."""
         path = os.fspath(pretrained_model_name_or_path)
         if not os.path.isfile(path):
             raise FileNotFoundError(f"NunchakuT5EncoderModel.from_pretrained: {path!r} is not a local .safetensors file "
@@ -60,4 +162,7 @@ class NunchakuT5EncoderModel(T5EncoderModel):
         device = torch.device(kwargs.get("device", "cuda"))
         model.to_empty(device=device)
         model.load_state_dict(state_dict, strict=True)
+        if (kwargs.get("fused_attention", True) and device.type == "cuda" and config.d_kv == 64 and not config.is_decoder
+                and register_fused_attention()):
+            model.config._attn_implementation = ATTENTION_NAME
         return model

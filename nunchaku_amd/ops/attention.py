@@ -257,6 +257,39 @@ def cross_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: in
     return out
 
 
+def _d64_operands(op: str, q, k, v, heads: int, out):
+    """the checks ``attention_d64`` and ``attention_d64_bias`` share; returns ``out`` and the four ``[B, rows, H, 64]`` views the library takes"""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{op}: {name} must be a tensor")
+        if t.dtype not in (torch.bfloat16, torch.float16):
+            raise TypeError(f"{op}: {name} must be bfloat16 or float16, got {t.dtype}")
+    if k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError(f"{op}: k ({k.dtype}) and v ({v.dtype}) must have q's dtype {q.dtype}")
+    if q.dim() not in (2, 3) or k.dim() != q.dim() or v.dim() != q.dim():
+        raise ValueError(f"{op}: q, k and v must all be [B, rows, H*64] or all [rows, H*64], got {tuple(q.shape)}, {tuple(k.shape)}, "
+                         f"{tuple(v.shape)}")
+    hd = q.shape[-1]
+    if heads < 1 or hd % heads:
+        raise ValueError(f"{op}: {hd} columns are not a multiple of heads={heads}")
+    head_dim = hd // heads
+    if head_dim != 64:
+        raise NotImplementedError(f"{op}: head_dim={head_dim}: 64 is implemented ({hd} columns, {heads} heads)")
+    if k.shape[-1] != hd or tuple(v.shape) != tuple(k.shape) or k.shape[:-2] != q.shape[:-2] or q.shape[-2] < 1 or k.shape[-2] < 1:
+        raise ValueError(f"{op}: expected q [B, T, {hd}] and k / v [B, N, {hd}] of one batch size with T, N >= 1, got {tuple(q.shape)}, "
+                         f"{tuple(k.shape)}, {tuple(v.shape)}")
+    if out is None:
+        out = torch.empty(*q.shape[:-1], hd, dtype=q.dtype, device=q.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != q.dtype or out.device != q.device or tuple(out.shape) != tuple(q.shape):
+        raise ValueError(f"{op}: out must be a {q.dtype} tensor of shape {tuple(q.shape)} on {q.device}, got "
+                         f"{getattr(out, 'dtype', None)} {tuple(getattr(out, 'shape', ()))}")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not t.is_cuda:
+            raise ValueError(f"{op}: {name} must be a GPU tensor (there is no CPU path)")
+    q4, k4, v4, o4 = ((t if t.dim() == 3 else t.unsqueeze(0)).unflatten(-1, (heads, 64)) for t in (q, k, v, out))
+    return out, q4, k4, v4, o4
+
+
 def attention_d64(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float | None = None, out: torch.Tensor | None = None):
     """Stable Diffusion XL's attention, one launch: per sample and head, ``round16(softmax(scale * Q K^T) V)`` at head dimension 64, no mask.
 
@@ -267,35 +300,36 @@ def attention_d64(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
 
     Returns ``out`` in the leading shape of ``q`` with ``H*64`` columns, token-major (what ``to_out[0]``'s quantiser reads); a given ``out``
     may be a column slice of a wider buffer.  No synchronisation and no allocation beyond ``out``."""
-    for name, t in (("q", q), ("k", k), ("v", v)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"attention_d64: {name} must be a tensor")
-        if t.dtype not in (torch.bfloat16, torch.float16):
-            raise TypeError(f"attention_d64: {name} must be bfloat16 or float16, got {t.dtype}")
-    if k.dtype != q.dtype or v.dtype != q.dtype:
-        raise TypeError(f"attention_d64: k ({k.dtype}) and v ({v.dtype}) must have q's dtype {q.dtype}")
-    if q.dim() not in (2, 3) or k.dim() != q.dim() or v.dim() != q.dim():
-        raise ValueError(f"attention_d64: q, k and v must all be [B, rows, H*64] or all [rows, H*64], got {tuple(q.shape)}, {tuple(k.shape)}, "
-                         f"{tuple(v.shape)}")
-    hd = q.shape[-1]
-    if heads < 1 or hd % heads:
-        raise ValueError(f"attention_d64: {hd} columns are not a multiple of heads={heads}")
-    head_dim = hd // heads
-    if head_dim != 64:
-        raise NotImplementedError(f"attention_d64: head_dim={head_dim}: 64 is implemented ({hd} columns, {heads} heads)")
-    if k.shape[-1] != hd or tuple(v.shape) != tuple(k.shape) or k.shape[:-2] != q.shape[:-2] or q.shape[-2] < 1 or k.shape[-2] < 1:
-        raise ValueError(f"attention_d64: expected q [B, T, {hd}] and k / v [B, N, {hd}] of one batch size with T, N >= 1, got {tuple(q.shape)}, "
-                         f"{tuple(k.shape)}, {tuple(v.shape)}")
-    if out is None:
-        out = torch.empty(*q.shape[:-1], hd, dtype=q.dtype, device=q.device)
-    elif not isinstance(out, torch.Tensor) or out.dtype != q.dtype or out.device != q.device or tuple(out.shape) != tuple(q.shape):
-        raise ValueError(f"attention_d64: out must be a {q.dtype} tensor of shape {tuple(q.shape)} on {q.device}, got "
-                         f"{getattr(out, 'dtype', None)} {tuple(getattr(out, 'shape', ()))}")
-    for name, t in (("q", q), ("k", k), ("v", v)):
-        if not t.is_cuda:
-            raise ValueError(f"attention_d64: {name} must be a GPU tensor (there is no CPU path)")
-    q4, k4, v4, o4 = ((t if t.dim() == 3 else t.unsqueeze(0)).unflatten(-1, (heads, 64)) for t in (q, k, v, out))
+    out, q4, k4, v4, o4 = _d64_operands("attention_d64", q, k, v, heads, out)
     ops.attention_d64(q4, k4, v4, o4, 64 ** -0.5 if scale is None else scale)
+    return out
+
+
+def attention_d64_bias(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, rel_bias: torch.Tensor, key_bias: torch.Tensor | None = None,
+                       scale: float = 1.0, out: torch.Tensor | None = None):
+    """The T5 encoder's attention, one launch: :func:`attention_d64` with an additive score bias,
+    ``round16(softmax_n(scale * Q K^T + rel_bias[h, n - t + T - 1] + key_bias[b, n]) V)`` per sample and head at head dimension 64.
+
+    ``q`` / ``k`` / ``v`` / ``out``: as for :func:`attention_d64` (column slices of wider buffers are read in place; the same checks).
+    ``rel_bias``: float32 ``[H, T + N - 1]``, one Toeplitz vector per head, entry ``d + T - 1`` for the distance ``d = key - query`` (T5:
+    ``relative_attention_bias.weight[bucket(d), h]``) -- the ``[1, H, T, N]`` position bias is never formed.  ``key_bias``: float32 ``[B, N]`` or
+    None, a padding mask: a value at or below ``-2**100`` (``-inf``, ``torch.finfo(torch.bfloat16).min``) excludes its key exactly; a row all of
+    whose keys are excluded is zeros.  Both must be contiguous and on q's device (``ValueError`` otherwise) and are added to the fp32 scores;
+    ``rel_bias`` must be finite (not checked: that would be a synchronisation).  ``scale`` defaults to T5's 1.0."""
+    op = "attention_d64_bias"
+    out, q4, k4, v4, o4 = _d64_operands(op, q, k, v, heads, out)
+    B, T, N = q4.shape[0], q4.shape[1], k4.shape[1]
+    for name, t, shape in (("rel_bias", rel_bias, (heads, T + N - 1)), ("key_bias", key_bias, (B, N))):
+        if t is None and name == "key_bias":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise ValueError(f"{op}: {name} must be a float32 tensor of shape {shape}, got {getattr(t, 'dtype', type(t).__name__)} "
+                             f"{tuple(getattr(t, 'shape', ()))}")
+        if not t.is_contiguous():
+            raise ValueError(f"{op}: {name} must be contiguous, got strides {t.stride()}")
+        if t.device != q.device:
+            raise ValueError(f"{op}: {name} must live on q's device {q.device}, got {t.device}")
+    ops.attention_d64_bias(q4, k4, v4, o4, rel_bias, key_bias, scale)
     return out
 
 
