@@ -158,6 +158,56 @@ int svdq_quantize_w4a4_act_fuse_lora(const svdq_quantize_args *args, void *strea
 int svdq_quantize_plan(const svdq_quantize_args *args, int32_t out8[8]);
 
 /* ------------------------------------------------------------------------------------------
+ * svdq_quantize_glu_halves  (extension: Z-Image's SwiGLU, SDXL's GEGLU)
+ * The quantiser above behind a split-half gated activation: value and gate are the two column halves of one [M, 2K] projection
+ * output (gate = value + K, ld_value = ld_gate = the projection's row stride), or any two [M, K] matrices.
+ *
+ *   a = round16(act(float(gate)))     SVDQ_GLU_SILU: g * sigmoid(g);  SVDQ_GLU_GELU_ERF: g * 0.5 * (1 + erf(g * sqrt(1/2))), both fp32
+ *   x = round16(float(value) * a)     the 16-bit multiply
+ *   then exactly svdq_quantize_w4a4_act_fuse_lora on x: lora_act = x @ lora_down on the un-smoothed x, x_hat = round16(x / smooth),
+ *   scale = amax / 7 per (row, 64 channels), codes, rows >= M zero.  Same act / ascales / lora_act images and formats, same lora_down order.
+ *
+ * These are the rounding points of the 16-bit torch sequence `value * act(gate)`; the activation itself is the hardware's exp2 / rcp and
+ * the device library's erfc, within 32 * 2^-24 * max(|act|, |gate|) of the exact function.
+ * One launch plan: a workgroup quantises four 128-channel chunks of one 32-row tile; K > 512 is sliced over workgroups, whose low-rank
+ * partial sums meet in atomics (lora_act is cleared first by a small kernel unless lora_act_zeroed).
+ * Validation (no launch), SVDQ_E_INVALID: NULL args / value / gate / act / ascales, unknown dtype, act_fn or lora_act_format, M < 1,
+ * M_pad < M or not a multiple of 256, K not a positive multiple of 128, a stride below K or not a multiple of 8, R not a multiple of 16
+ * in [0, 256], R > 0 without lora_down / lora_act, a misaligned pointer.
+ * ------------------------------------------------------------------------------------------ */
+enum { SVDQ_GLU_SILU = 0, SVDQ_GLU_GELU_ERF = 1 };
+
+typedef struct svdq_quantize_glu_args {
+    const void *value;     /* [M, K] 16-bit, row stride ld_value elements                     */
+    const void *gate;      /* [M, K] 16-bit, row stride ld_gate elements                      */
+    const void *smooth;    /* [K] 16-bit, natural order; NULL = ones                          */
+    const void *lora_down; /* [K*R] 16-bit in svdq_repack_lowrank(down=1) order; NULL if R==0 */
+    void *act;             /* out: FP6 image of the int4 codes, M_pad*K*3/4 bytes            */
+    void *ascales;         /* out: (K/64)*M_pad 16-bit                                        */
+    void *lora_act;        /* out: M_pad*R fp32, or int64 (lora_act_format)                   */
+    int32_t M, M_pad, K, R;
+    int32_t ld_value, ld_gate; /* >= K, multiples of 8                                        */
+    int32_t dtype;         /* SVDQ_BF16 | SVDQ_FP16                                           */
+    int32_t act_fn;        /* SVDQ_GLU_SILU | SVDQ_GLU_GELU_ERF                               */
+    int32_t lora_act_zeroed; /* non-zero: lora_act is already zero on this stream: the clearing kernel of a K-sliced launch is skipped */
+    int32_t lora_act_format; /* SVDQ_LORA_ACT_F32 | SVDQ_LORA_ACT_Q32 (SVDQ_LORA_ACT_Q32_RUNS is treated as Q32) */
+} svdq_quantize_glu_args;
+
+/* Alignment of the operands of svdq_quantize_glu_halves ("Alignment").  A pointer or stride that is no multiple of its line is
+ * refused with SVDQ_E_INVALID before anything is launched; NULL counts as aligned.  tests/test_quantize_glu_host.py probes the lines:
+ *   value, gate, act, lora_down    16 bytes
+ *   smooth                         4 bytes
+ *   lora_act                       4 bytes in fp32, 8 in the Q31.32 formats
+ *   ascales                        2 bytes
+ *   ld_value, ld_gate              8 elements */
+/* Addressing reach ("Addressing reach"; refused on the host, never wrapped on the device):
+ *   ld_value, ld_gate   unbounded: row addresses are formed in 64 bits
+ *   R * K               lora_down is read through a buffer descriptor with 32-bit byte offsets: R * K * 2 <= 2147483647 and
+ *                       (R + 32) * K * 2 <= 4294967295 (a slab's ranks beyond R must fall outside the descriptor, not wrap); beyond: SVDQ_E_UNSUPPORTED
+ *   M_pad * K, M_pad * R  unbounded: 64-bit products; (M_pad / 32) * ceil(K / 512) workgroups must fit 2147483647 (SVDQ_E_UNSUPPORTED) */
+int svdq_quantize_glu_halves(const svdq_quantize_glu_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * svdq_gemm_w4a4
  * replaces kernels::gemm_w4a4 (zgemm.h:8-36, gemm_w4a4_launch_impl.cuh:7-424).
  *

@@ -526,6 +526,41 @@ class _Ops:
         del keep2
 
     @staticmethod
+    def quantize_glu_halves(x, output, oscales, lora_down, lora_act_out, smooth, act="silu", lora_act_zeroed=False):
+        """Extension (Z-Image's SwiGLU, SDXL's GEGLU; ``svdq_quantize_glu_halves``): quantise ``value * act(gate)`` where ``value`` / ``gate`` are the
+        two column halves of ``x`` ``[M, >= 2K]``, read in place (``K = output``'s width), with the 16-bit rounding points of the torch sequence;
+        ``act``: ``"silu"`` or ``"gelu"`` (erf form).  Buffers as for ``quantize_w4a4_act_fuse_lora``."""
+        op, lib = "quantize_glu_halves", _lib.load()
+        if x is None or output is None or oscales is None:
+            raise ValueError(f"{op}: x, output and oscales are required")
+        if x.dim() != 2 or x.stride(1) != 1 or x.dtype not in _DT:
+            raise ValueError(f"{op}: x must be a 2-D 16-bit view with unit column stride")
+        if act not in ("silu", "gelu"):
+            raise ValueError(f"{op}: act must be 'silu' or 'gelu', not {act!r}")
+        M_pad = output.numel() // output.shape[-1]
+        K = output.shape[-1] * 4 // 3
+        if x.shape[1] < 2 * K:
+            raise ValueError(f"{op}: x must hold two halves of K={K} columns")
+        R = 0 if lora_down is None else lora_down.shape[-1]
+        image = _fp6_image(output, M_pad, K, True, op)
+        smooth, lora_down = _param(smooth, "vec"), _param(lora_down, "down")
+        if oscales.numel() != (K // 64) * M_pad:
+            raise ValueError(f"{op}: oscales must hold (K/64)*M_pad scales")
+        if R and (lora_act_out is None or lora_act_out.numel() != M_pad * R or lora_act_out.dtype not in (torch.float32, torch.int64)):
+            raise ValueError(f"{op}: lora_act_out must hold M_pad*R float32 (or int64: the deterministic fixed-point format)")
+        a = _lib.ARGS["svdq_quantize_glu_args"]()
+        a.value, a.gate = x.data_ptr(), x.data_ptr() + 2 * K
+        a.smooth, a.lora_down, a.act, a.ascales, a.lora_act = _ptr(smooth), _ptr(lora_down), _ptr(image), _ptr(oscales), _ptr(lora_act_out)
+        a.M, a.M_pad, a.K, a.R = _i32(op, "M", x.shape[0]), _i32(op, "M_pad", M_pad), _i32(op, "K", K), _i32(op, "R", R)
+        a.ld_value = _i32(op, "x.stride(0)", x.stride(0))
+        a.ld_gate = a.ld_value
+        a.dtype, a.act_fn = _DT[x.dtype], _lib.GLU_SILU if act == "silu" else _lib.GLU_GELU_ERF
+        a.lora_act_zeroed = int(bool(lora_act_zeroed))
+        if R and lora_act_out.dtype == torch.int64:
+            a.lora_act_format = _lib.LORA_ACT_Q32
+        _lib.check(lib.svdq_quantize_glu_halves(C.byref(a), _stream()), op)
+
+    @staticmethod
     def gemm_w4a4(
         act, wgt, out, qout, ascales, wscales, oscales, poolout, lora_act_in, lora_up, lora_down, lora_act_out,
         norm_q, norm_k, rotary_emb, bias, smooth_factor, out_vk, out_linearattn, act_unsigned, lora_scales,

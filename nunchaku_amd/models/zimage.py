@@ -23,7 +23,8 @@ Every module is constructible from dimensions alone (no diffusers needed) under 
 * Without diffusers it is an ``nn.Module`` that builds the quantised blocks from the checkpoint's keys under the checkpoint's module paths, keeps
   the remaining tensors as ``unquantized_state_dict``, offers the three stacks (``stack("layers")``) and raises on ``forward``.
 
-Not built: SwiGLU folded into the quantiser's ``fuse_glu`` (DESIGN.md 6p prices it), Q pre-scaling for the attention's second geometry, a batched
+``model.set_fused_glu(True)`` runs ``value * silu(gate)`` inside the second projection's quantiser (one launch; off by default).
+Not built: Q pre-scaling for the attention's second geometry, a batched
 QK launch, caching the modulation across blocks, a LoRA converter, NVFP4 (``precision="fp4"`` raises), offload (raises as in the reference)."""
 
 from __future__ import annotations
@@ -39,7 +40,7 @@ from torch import nn
 
 from ..ops.attention import attention_packed, qk_norm_rope
 from ..ops.elementwise import sandwich_norm
-from .linear import SVDQW4A4Linear
+from .linear import SVDQW4A4Linear, fused_glu_feed_forward
 from .transformer_flux import NunchakuModelLoaderMixin
 
 try:  # the guarded import the reference does unconditionally (transformer_zimage.py:11-14)
@@ -204,7 +205,15 @@ class NunchakuZImageFeedForward(nn.Module):
         kw = dict(rank=rank, precision="int4", bias=False, torch_dtype=torch_dtype, device=device)
         self.net = nn.ModuleList([NunchakuZImageSwiGLU(SVDQW4A4Linear(ff, 2 * hidden, **kw)), nn.Dropout(0.0), SVDQW4A4Linear(hidden, ff, **kw)])
 
+    # True: silu, product and net[2]'s quantiser run as one launch (SVDQW4A4Linear.quantize_glu).  Off by default: that path has the 16-bit
+    # rounding points of the torch sequence but the hardware's exp2 / rcp, so it is not bit-identical to F.silu.
+    fused_glu = False
+
     def forward(self, hidden_states: torch.Tensor) -> torch.Tensor:
+        if self.fused_glu:
+            fused = fused_glu_feed_forward(self.net, hidden_states, "silu")
+            if fused is not None:
+                return fused
         for module in self.net:
             hidden_states = module(hidden_states)
         return hidden_states
@@ -338,6 +347,14 @@ _Base = _DiffusersZImage if HAVE_DIFFUSERS else nn.Module
 
 class NunchakuZImageTransformer2DModel(_Base, NunchakuModelLoaderMixin):
     """``ZImagePipeline``'s ``transformer`` with the quantised blocks (reference: transformer_zimage.py:169-269)."""
+
+    def set_fused_glu(self, flag: bool):
+        """Run every quantised feed-forward's ``value * silu(gate)`` inside ``net[2]``'s quantiser (one launch; ``NunchakuZImageFeedForward.fused_glu``),
+        in ``forward`` and in the fused block path alike.  Unquantised feed-forwards (the refiners under ``skip_refiners``) keep their path."""
+        for m in self.modules():
+            if isinstance(m, NunchakuZImageFeedForward):
+                m.fused_glu = bool(flag)
+        return self
 
     if HAVE_DIFFUSERS:
 

@@ -62,3 +62,25 @@ def svdq_quantize_w4a4_act_fuse_lora_cuda(
         ops.quantize_w4a4_act_fuse_lora(input, output, oscales, lora_down, lora_act_out, smooth, fuse_glu, fp4,
                                         ln_stats=ln[0], mod_scale=ln[1], mod_shift=ln[2], lora_act_zeroed=zeroed, second=second)
     return output, oscales, lora_act_out
+
+
+def svdq_quantize_glu_halves(x: torch.Tensor, *, lora_down: torch.Tensor | None, smooth: torch.Tensor | None, act: str = "silu", pad_size: int = 256,
+                             pool=None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """4-bit quantisation of ``value * act(gate)`` plus the low-rank down projection, where ``value, gate = x.chunk(2, -1)`` of a projection
+    output ``x`` [N, 2K]: both halves are read in place (no chunk, no copy) and the 16-bit [N, K] product is never written.  ``act``:
+    ``"silu"`` (SwiGLU) or ``"gelu"`` (GEGLU, erf form).  The 16-bit rounding points are those of the torch sequence
+    ``value * act(gate)``; returns what :func:`svdq_quantize_w4a4_act_fuse_lora_cuda` returns for that product."""
+    if x.dim() != 2 or x.shape[1] % 2:
+        raise ValueError("svdq_quantize_glu_halves: x must be [N, 2K]")
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    M, K = x.shape[0], x.shape[1] // 2
+    if K % 128:
+        raise ValueError("K must be a multiple of 128")
+    R = 0 if lora_down is None else lora_down.shape[1]
+    M_pad = ceil_divide(M, pad_size) * pad_size
+    output = torch.empty(M_pad, K * 3 // 4, dtype=torch.uint8, device=x.device)
+    oscales = torch.empty(K // 64, M_pad, dtype=x.dtype, device=x.device)
+    lora_act_out, zeroed = alloc_lora_act(M_pad, R, x.device, pool)
+    ops.quantize_glu_halves(x, output, oscales, lora_down, lora_act_out, smooth, act=act, lora_act_zeroed=zeroed)
+    return output, oscales, lora_act_out
