@@ -757,6 +757,60 @@ typedef struct svdq_dwconv3x3_args {
 int svdq_dwconv3x3(const svdq_dwconv3x3_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * svdq_quantize_dwconv_glu  (extension: the back half of SANA's GLU-MBConv in one launch; added WITHOUT a version bump: one new symbol
+ * and a new args struct, nothing existing changes, so SVDQ_ABI_VERSION stays 24)
+ * svdq_dwconv3x3, the interleaved GLU of svdq_quantize_w4a4_act_fuse_lora(fuse_glu) and that quantiser, without the 16-bit [M, 2K]
+ * convolution output in between.  x is [B][H * W, C] token rows, weight the tap-major [9, C] image, row m = b * H * W + h * W + w:
+ *
+ *   c[m, ch] = round16(acc),  acc = bias[ch] (or +0);  for ky = 0..2, for kx = 0..2:  acc = fma(weight[ky * 3 + kx, ch], x[b, h + ky - 1, w + kx - 1, ch], acc)
+ *                                        fp32, svdq_dwconv3x3's order; a tap outside the image contributes its product with a zero
+ *   a = round16(silu(c[m, 2k + 1]))      the gate: g * rcp(1 + exp2(-log2e * g)), within 32 * 2^-24 * max(|a|, |g|) of g * sigmoid(g)
+ *   v[m, k] = round16(c[m, 2k] * a)      the 16-bit multiply; conv channels C .. 2K - 1 are zero and are not loaded
+ *   then exactly svdq_quantize_w4a4_act_fuse_lora on v [M = B * H * W, K]: lora_act = v @ lora_down on the un-smoothed v,
+ *   round16(v / smooth), scale = amax / 7 per (row, 64 channels), codes; rows M .. M_pad - 1: zero codes, scales and lora_act.
+ *
+ * One launch plan: a wave produces 32 consecutive rows x 128 quantised channels from a sliding 3 x 3 window of 16-byte loads; K > 512
+ * is sliced over workgroups, whose low-rank partial sums meet in atomics (lora_act is cleared first by a small kernel unless
+ * lora_act_zeroed).  Nothing outside x[:, :H * W, :C] is read; a sample's border never reads the neighbouring sample.
+ * Validation (no launch), SVDQ_E_INVALID: NULL args / x / weight / act / ascales, unknown dtype or lora_act_format, B / H / W / C < 1,
+ * B * H * W > M_pad, M_pad not a multiple of 256, K not a positive multiple of 128, C % 8, C > 2K, ldx below C or not a multiple of 8,
+ * x_bs (B > 1) below H * W * ldx or not a multiple of 8, R not a multiple of 16 in [0, 256], R > 0 without lora_down / lora_act,
+ * a misaligned pointer.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct svdq_quantize_dwconv_glu_args {
+    const void *x;         /* [B][H * W, C] 16-bit, row stride ldx, batch stride x_bs           */
+    const void *weight;    /* [9, C] tap-major, contiguous (as for svdq_dwconv3x3)             */
+    const void *bias;      /* [C] or NULL                                                     */
+    const void *smooth;    /* [K] 16-bit, natural order; NULL = ones                          */
+    const void *lora_down; /* [K*R] 16-bit in svdq_repack_lowrank(down=1) order; NULL if R==0 */
+    void *act;             /* out: FP6 image of the int4 codes, M_pad*K*3/4 bytes            */
+    void *ascales;         /* out: (K/64)*M_pad 16-bit                                        */
+    void *lora_act;        /* out: M_pad*R fp32, or int64 (lora_act_format)                   */
+    int64_t x_bs;          /* in elements; ignored when B == 1                                */
+    int32_t ldx;           /* in elements                                                     */
+    int32_t B, H, W, C;
+    int32_t M_pad, K, R;
+    int32_t dtype;         /* SVDQ_BF16 | SVDQ_FP16                                           */
+    int32_t lora_act_zeroed; /* non-zero: lora_act is already zero on this stream: the clearing kernel of a K-sliced launch is skipped */
+    int32_t lora_act_format; /* SVDQ_LORA_ACT_F32 | SVDQ_LORA_ACT_Q32 (SVDQ_LORA_ACT_Q32_RUNS is treated as Q32) */
+    int32_t reserved;
+} svdq_quantize_dwconv_glu_args;
+
+/* Alignment of the operands of svdq_quantize_dwconv_glu ("Alignment").  A pointer or stride that is no multiple of its line is
+ * refused with SVDQ_E_INVALID before anything is launched; NULL counts as aligned.  tests/test_quantize_dwconv_glu_host.py probes the lines:
+ *   x, weight, bias, act, lora_down   16 bytes
+ *   smooth                            4 bytes
+ *   lora_act                          4 bytes in fp32, 8 in the Q31.32 formats
+ *   ascales                           2 bytes
+ *   ldx, x_bs, C                      8 elements */
+/* Addressing reach ("Addressing reach"; refused on the host, never wrapped on the device):
+ *   ldx, x_bs           unbounded: pixel addresses are formed in 64 bits
+ *   R * K               lora_down is read through a buffer descriptor with 32-bit byte offsets: R * K * 2 <= 2147483647 and
+ *                       (R + 32) * K * 2 <= 4294967295 (a slab's ranks beyond R must fall outside the descriptor, not wrap); beyond: SVDQ_E_UNSUPPORTED
+ *   M_pad * K, M_pad * R  unbounded: 64-bit products; (M_pad / 32) * ceil(K / 512) workgroups must fit 2147483647 (SVDQ_E_UNSUPPORTED) */
+int svdq_quantize_dwconv_glu(const svdq_quantize_dwconv_glu_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Variable-length cross-attention (SANA's text cross-attention; added WITHOUT a version bump: one new symbol and a new args struct,
  * nothing existing changes, so SVDQ_ABI_VERSION stays 24.  reference: MultiHeadCrossAttention::forward, src/SanaModel.cpp:147-190 ->
  * flash-attention's mha_varlen_fwd).  Per sample b < B, query t < T and head h < H:

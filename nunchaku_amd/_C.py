@@ -561,6 +561,55 @@ class _Ops:
         _lib.check(lib.svdq_quantize_glu_halves(C.byref(a), _stream()), op)
 
     @staticmethod
+    def quantize_dwconv_glu(x, weight, bias, output, oscales, lora_down, lora_act_out, smooth, lora_act_zeroed=False):
+        """Extension (SANA's GLU-MBConv; ``svdq_quantize_dwconv_glu``): ``dwconv3x3(x, weight, bias)``, the interleaved GLU
+        ``value * silu(gate)`` of its (2k, 2k + 1) channel pairs and the quantiser in one launch; the convolution output is never written.
+        ``x``: a ``[B, H, W, C]`` view of token rows as for :meth:`dwconv3x3`, ``C <= 2K`` (``K = output``'s width; the channels behind ``C`` count
+        as zeros); ``weight`` / ``bias`` as for :meth:`dwconv3x3` (the same cached tap-major image).  Buffers as for ``quantize_w4a4_act_fuse_lora``."""
+        op, lib = "quantize_dwconv_glu", _lib.load()
+        if x is None or output is None or oscales is None or weight is None:
+            raise ValueError(f"{op}: x, weight, output and oscales are required")
+        if x.dim() != 4 or x.dtype not in _DT or min(x.shape) < 1:
+            raise ValueError(f"{op}: x must be a 16-bit [B, H, W, C] view, every extent at least 1")
+        B, H, W, Cc = x.shape
+        if weight.dtype != x.dtype or (bias is not None and bias.dtype != x.dtype):
+            raise ValueError(f"{op}: x, weight and bias must share one 16-bit dtype (bfloat16 or float16)")
+        if tuple(weight.shape) != (Cc, 3, 3, 1) or (bias is not None and tuple(bias.shape) != (Cc,)):
+            raise ValueError(f"{op}: weight must be [C, 3, 3, 1] and bias [C] with C={Cc}, got {tuple(weight.shape)}"
+                             + ("" if bias is None else f" and {tuple(bias.shape)}"))
+        if x.stride(3) != 1 or (H > 1 and W > 1 and x.stride(1) != W * x.stride(2)):
+            raise ValueError(f"{op}: x must be a [B, H, W, C] view of token rows: unit channel stride and stride(1) == W * stride(2)")
+        M_pad = output.numel() // output.shape[-1]
+        K = output.shape[-1] * 4 // 3
+        if Cc % 8 or Cc > 2 * K:
+            raise ValueError(f"{op}: C={Cc} must be a multiple of 8, at most 2K = {2 * K}")
+        R = 0 if lora_down is None else lora_down.shape[-1]
+        image = _fp6_image(output, M_pad, K, True, op)
+        smooth, lora_down = _param(smooth, "vec"), _param(lora_down, "down")
+        if oscales.numel() != (K // 64) * M_pad:
+            raise ValueError(f"{op}: oscales must hold (K/64)*M_pad scales")
+        if R and (lora_act_out is None or lora_act_out.numel() != M_pad * R or lora_act_out.dtype not in (torch.float32, torch.int64)):
+            raise ValueError(f"{op}: lora_act_out must hold M_pad*R float32 (or int64: the deterministic fixed-point format)")
+        if not (x.is_cuda and weight.is_cuda and (bias is None or bias.is_cuda)):
+            raise RuntimeError("nunchaku_amd ops need GPU tensors (there is no CPU path)")
+        taps = _cached_conversion(weight, "dwconv_taps", lambda src: src.reshape(Cc, 9).t().contiguous())
+        if bias is not None and not bias.is_contiguous():
+            bias = bias.contiguous()
+        a = _lib.ARGS["svdq_quantize_dwconv_glu_args"]()
+        a.x, a.weight, a.bias = x.data_ptr(), taps.data_ptr(), _ptr(bias)
+        a.smooth, a.lora_down, a.act, a.ascales, a.lora_act = _ptr(smooth), _ptr(lora_down), _ptr(image), _ptr(oscales), _ptr(lora_act_out)
+        a.B, a.H, a.W, a.C = _i32(op, "B", B), _i32(op, "H", H), _i32(op, "W", W), _i32(op, "C", Cc)
+        a.M_pad, a.K, a.R = _i32(op, "M_pad", M_pad), _i32(op, "K", K), _i32(op, "R", R)
+        # (the strides of dimensions of size 1 are arbitrary in torch: the library gets the natural ones)
+        a.ldx = _i32(op, "x pixel stride", x.stride(2) if W > 1 else x.stride(1) if H > 1 else Cc)
+        a.x_bs = _i64(op, "x batch stride", x.stride(0) if B > 1 else 0)
+        a.dtype, a.lora_act_zeroed = _DT[x.dtype], int(bool(lora_act_zeroed))
+        if R and lora_act_out.dtype == torch.int64:
+            a.lora_act_format = _lib.LORA_ACT_Q32
+        _lib.check(lib.svdq_quantize_dwconv_glu(C.byref(a), _stream()), op)
+        del taps
+
+    @staticmethod
     def gemm_w4a4(
         act, wgt, out, qout, ascales, wscales, oscales, poolout, lora_act_in, lora_up, lora_down, lora_act_out,
         norm_q, norm_k, rotary_emb, bias, smooth_factor, out_vk, out_linearattn, act_unsigned, lora_scales,

@@ -52,6 +52,24 @@ def _quantize_glu_args():
 ARGS = {"svdq_quantize_glu_args": _quantize_glu_args()}
 
 
+def _quantize_dwconv_glu_args():
+    class QuantizeDwconvGluArgs(C.Structure):
+        """svdq_quantize_dwconv_glu_args"""
+        _fields_ = [
+            ("x", C.c_void_p), ("weight", C.c_void_p), ("bias", C.c_void_p), ("smooth", C.c_void_p), ("lora_down", C.c_void_p),
+            ("act", C.c_void_p), ("ascales", C.c_void_p), ("lora_act", C.c_void_p),
+            ("x_bs", C.c_int64), ("ldx", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32),
+            ("M_pad", C.c_int32), ("K", C.c_int32), ("R", C.c_int32), ("dtype", C.c_int32),
+            ("lora_act_zeroed", C.c_int32), ("lora_act_format", C.c_int32), ("reserved", C.c_int32),
+        ]
+
+    return QuantizeDwconvGluArgs
+
+
+# (ldx / x_bs: unbounded, 64-bit pixel addresses; classified and probed by tests/test_quantize_dwconv_glu_host.py)
+ARGS["svdq_quantize_dwconv_glu_args"] = _quantize_dwconv_glu_args()
+
+
 class ResidualArgs(C.Structure):
     _fields_ = [
         ("res", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("gate", C.c_void_p), ("out", C.c_void_p),
@@ -278,6 +296,7 @@ EXPORTS = {
     "svdq_linear_attention": (C.c_int, [C.POINTER(LinearAttentionArgs), C.c_void_p]),
     "svdq_linear_attention_workspace_bytes": (C.c_int64, [C.POINTER(LinearAttentionArgs)]),
     "svdq_dwconv3x3": (C.c_int, [C.POINTER(Dwconv3x3Args), C.c_void_p]),
+    "svdq_quantize_dwconv_glu": (C.c_int, [C.POINTER(ARGS["svdq_quantize_dwconv_glu_args"]), C.c_void_p]),
     "svdq_cross_attention": (C.c_int, [C.POINTER(CrossAttentionArgs), C.c_void_p]),
     "svdq_sana_glue": (C.c_int, [C.POINTER(SanaGlueArgs), C.c_void_p]),
     "svdq_attention_d64": (C.c_int, [C.POINTER(AttentionD64Args), C.c_void_p]),

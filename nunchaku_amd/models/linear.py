@@ -24,7 +24,7 @@ from torch import nn
 
 from .. import layout
 from ..ops.gemm import svdq_gemm_w4a4_cuda
-from ..ops.quantize import svdq_quantize_glu_halves, svdq_quantize_w4a4_act_fuse_lora_cuda
+from ..ops.quantize import svdq_quantize_dwconv_glu, svdq_quantize_glu_halves, svdq_quantize_w4a4_act_fuse_lora_cuda
 
 
 def synthetic_codes_(qweight: torch.Tensor, wscales: torch.Tensor, in_features: int, generator: torch.Generator, codes: str = "uniform"):
@@ -257,6 +257,15 @@ class SVDQW4A4Linear(nn.Module):
         (extension: ops.quantize.svdq_quantize_glu_halves)."""
         self._ensure_layout()
         return svdq_quantize_glu_halves(x, lora_down=self.proj_down, smooth=self.smooth_factor, act=act, pad_size=pad_size, pool=pool)
+
+    def quantize_dwconv_glu(self, x: torch.Tensor, conv_weight: torch.Tensor, conv_bias: torch.Tensor | None, height: int | None = None,
+                            width: int | None = None, pad_size: int = 256, pool=None):
+        """x [B, T, C] (or [B, H, W, C]), the input of SANA's depthwise convolution, ``C <= 2 * in``: quantises ``value * silu(gate)`` of the
+        interleaved (value, gate) channel pairs of ``dwconv3x3(x, conv_weight, conv_bias)`` in one launch, as :meth:`quantize` ``(fuse_glu=True)``
+        would quantise the convolution's output, which is never written (extension: ops.quantize.svdq_quantize_dwconv_glu)."""
+        self._ensure_layout()
+        return svdq_quantize_dwconv_glu(x, conv_weight, conv_bias, height, width, lora_down=self.proj_down, smooth=self.smooth_factor,
+                                        quantized_features=self.in_features, pad_size=pad_size, pool=pool)
 
     def forward_silu(self, x: torch.Tensor, output: torch.Tensor | None = None) -> torch.Tensor:
         """``silu(forward(x))`` with the SiLU in the GEMM's epilogue: one GEMM launch (reference: GEMM_W4A4::forward_silu, src/Linear.cpp:160-162).

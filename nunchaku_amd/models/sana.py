@@ -147,8 +147,23 @@ class SanaGLUMBConv(nn.Module):
         self.depth_conv(y.unflatten(1, (H, W)), out=wide[..., : self.c_gemm].unflatten(1, (H, W)))
         return wide
 
+    # True: the convolution, the GLU and point_conv's quantiser run as one launch (SVDQW4A4Linear.quantize_dwconv_glu): no [B, T, 2 * hid_pad]
+    # buffer, no zeroed tail, no dwconv3x3 launch.  Off by default (set_fused_conv on the models).
+    fused_conv = False
+
     def forward(self, x: torch.Tensor, H: int | None = None, W: int | None = None) -> torch.Tensor:
         """x [B, T, in_features] on a grid of ``H x W = T`` tokens (without the pair: a square grid; one missing side is derived) -> [B, T, in_features]"""
+        if self.fused_conv:
+            if x.dim() != 3 or x.shape[-1] not in (self.in_features, self.in_pad):
+                raise ValueError(f"SanaGLUMBConv: expected x [B, T, {self.in_features}], got {tuple(x.shape)}")
+            B, T = x.shape[:2]
+            H, W = grid_of(T, H, W)
+            if x.shape[-1] != self.in_pad:
+                x = F.pad(x, (0, self.in_pad - self.in_features))
+            y = self.inverted_conv.forward_silu(x)                           # [B, T, C_gemm]
+            qx, ascales, lora_act = self.point_conv.quantize_dwconv_glu(y, self.depth_conv.weight, self.depth_conv.bias, H, W)
+            out = torch.empty(B * T, self.in_pad, dtype=y.dtype, device=y.device)
+            return self.point_conv.forward_quant(qx, ascales, lora_act, out).view(B, T, -1)[..., : self.in_features]
         wide = self.gated_input(x, H, W)
         B, T = wide.shape[:2]
         qx, ascales, lora_act = self.point_conv.quantize(wide.view(B * T, -1), fuse_glu=True)
@@ -379,6 +394,13 @@ class SanaModel(nn.Module):
         self.transformer_blocks = nn.ModuleList(
             SanaLinearTransformerBlock(self.inner_dim, self.intermediate_size, int(_config_get(config, "num_cross_attention_heads")),
                                        pag=i in self.pag_layers, rank=rank, torch_dtype=torch_dtype, device=device) for i in range(self.num_layers))
+
+    def set_fused_conv(self, flag: bool):
+        """Run every feed-forward's depthwise convolution and GLU inside ``point_conv``'s quantiser (one launch; ``SanaGLUMBConv.fused_conv``)."""
+        for m in self.modules():
+            if isinstance(m, SanaGLUMBConv):
+                m.fused_conv = bool(flag)
+        return self
 
     def _run(self, hidden_states, timestep, make_cross, H, W, pag, cfg, skip_first_layer):
         first = 1 if skip_first_layer else 0

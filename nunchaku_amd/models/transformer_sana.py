@@ -205,6 +205,10 @@ class NunchakuSanaTransformer2DModel(_Base, NunchakuModelLoaderMixin):
             transformer.unquantized_state_dict = unquantized
         return (transformer, meta) if kwargs.get("return_metadata", False) else transformer
 
+    def set_fused_conv(self, flag: bool):
+        """Run every feed-forward's depthwise convolution and GLU inside ``point_conv``'s quantiser (:meth:`SanaModel.set_fused_conv`)."""
+        return SanaModel.set_fused_conv(self, flag)
+
     def inject_quantized_module(self, m: SanaModel, device: str | torch.device = "cuda"):
         """reference :288-305"""
         self.transformer_blocks = nn.ModuleList([NunchakuSanaTransformerBlocks(m, self.dtype, device)])

@@ -7,6 +7,7 @@ import torch
 from .._C import ops
 from ..mode import alloc_lora_act
 from ..utils import ceil_divide
+from .conv import grid_of
 from .elementwise import ln_pool
 
 
@@ -83,4 +84,37 @@ def svdq_quantize_glu_halves(x: torch.Tensor, *, lora_down: torch.Tensor | None,
     oscales = torch.empty(K // 64, M_pad, dtype=x.dtype, device=x.device)
     lora_act_out, zeroed = alloc_lora_act(M_pad, R, x.device, pool)
     ops.quantize_glu_halves(x, output, oscales, lora_down, lora_act_out, smooth, act=act, lora_act_zeroed=zeroed)
+    return output, oscales, lora_act_out
+
+
+def svdq_quantize_dwconv_glu(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, height: int | None = None, width: int | None = None,
+                             lora_down: torch.Tensor | None = None, smooth: torch.Tensor | None = None, quantized_features: int | None = None,
+                             pad_size: int = 256, pool=None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The back half of SANA's GLU-MBConv in one launch (``svdq_quantize_dwconv_glu``): ``c = dwconv3x3(x, weight, bias)`` in that kernel's
+    arithmetic, ``value, gate = c[..., 0::2], c[..., 1::2]``, then the 4-bit quantisation of ``value * silu(gate)`` plus the low-rank down
+    projection -- what ``dwconv3x3`` followed by :func:`svdq_quantize_w4a4_act_fuse_lora_cuda` ``(fuse_glu=True)`` computes, without the 16-bit
+    convolution output in between.  ``x``: ``[B, H, W, C]``, or ``[B, T, C]`` with ``height`` / ``width`` (as for ``dwconv3x3``; it may be a
+    column slice of a wider buffer); ``weight``: ``[C, 3, 3, 1]``, ``bias``: ``[C]`` or None.  ``quantized_features`` ``K`` (default ``C / 2``):
+    the quantised width, a multiple of 128 with ``C <= 2K`` -- the conv channels behind ``C`` count as zeros and are not read.  Row
+    ``b * H * W + h * W + w`` of the result is pixel ``(b, h, w)``; returns ``(qx, ascales, lora_act)`` as the other quantisers do."""
+    if x.dim() == 4:
+        B, H, W, C = x.shape
+        if (height is not None and int(height) != H) or (width is not None and int(width) != W):
+            raise ValueError(f"svdq_quantize_dwconv_glu: height / width ({height}, {width}) contradict x {tuple(x.shape)}")
+        x4 = x
+    elif x.dim() == 3:
+        B, T, C = x.shape
+        H, W = grid_of(T, height, width)
+        x4 = x.unflatten(1, (H, W))
+    else:
+        raise ValueError("svdq_quantize_dwconv_glu: expected x [B, H, W, C], or [B, T, C] with height / width")
+    K = C // 2 if quantized_features is None else int(quantized_features)
+    if K < 1 or K % 128 or C > 2 * K:
+        raise ValueError(f"svdq_quantize_dwconv_glu: the quantised width {K} must be a multiple of 128 with C={C} <= 2K")
+    R = 0 if lora_down is None else lora_down.shape[1]
+    M_pad = ceil_divide(B * H * W, pad_size) * pad_size
+    output = torch.empty(M_pad, K * 3 // 4, dtype=torch.uint8, device=x.device)
+    oscales = torch.empty(K // 64, M_pad, dtype=x.dtype, device=x.device)
+    lora_act_out, zeroed = alloc_lora_act(M_pad, R, x.device, pool)
+    ops.quantize_dwconv_glu(x4, weight, bias, output, oscales, lora_down, lora_act_out, smooth, lora_act_zeroed=zeroed)
     return output, oscales, lora_act_out
