@@ -1053,6 +1053,44 @@ typedef struct svdq_sandwich_norm_args {
 int svdq_sandwich_norm(const svdq_sandwich_norm_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * T5 encoder glue: residual add + T5LayerNorm as one row pass (added WITHOUT a version bump: one new symbol and a new args struct, nothing
+ * existing changes, so SVDQ_ABI_VERSION stays 24.  reference: transformers' T5LayerSelfAttention / T5LayerFF / T5LayerNorm under the
+ * reference's NunchakuT5EncoderModel -- an add and six small 16-bit / fp32 torch operations per norm).  The sandwich norm's pass with a
+ * plain add; every part is optional.  round16 = round to nearest even to `dtype`; every operation between two roundings is ONE plain fp32
+ * multiply or add (no fused multiply-add):
+ *   y[c]        = res[c]  |  round16(res[c] + a[c])                        (a NULL | given)        -> out[r]       (if out)
+ *   rstd        = 1 / sqrt(sum_c(float(y[c])^2) / C + eps)                                          -> stats[r]     (if stats; one fp32 per row)
+ *   out_norm[c] = round16(weight[c] * round16(float(y[c]) * rstd))                                  -> out_norm[r]  (if out_norm)
+ * T5LayerNorm.forward's rounding points (16-bit tensor times fp32 rsqrt = fp32, one cast, the weight multiply).  The sum of squares runs in
+ * svdq_sandwich_norm's fixed order, so two calls are bit-identical.  Every tensor of rows has its own row stride.  C % 8 == 0, ceil(C / 512)
+ * in {1..8, 12, 16, 24, 32} (else SVDQ_E_UNSUPPORTED).  out may alias res or a, out_norm may alias a, where the strides agree.  One launch, no
+ * workspace, no LDS, no atomics: the call can be captured.
+ * Validation (no launch), SVDQ_E_INVALID: NULL args or res, none of out / out_norm / stats, out_norm without weight, M or C < 1, C % 8, a
+ * row stride below C or not a multiple of 8, pointers not 16-byte aligned (stats: 4-byte), unknown dtype, an eps that is negative or not finite.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct svdq_t5_residual_norm_args {
+    const void *res;    /* [M, C] 16-bit, row stride ld_res */
+    const void *a;      /* [M, C], row stride ld_a: the sub-layer's output, or NULL */
+    const void *weight; /* [C]: the T5LayerNorm weight (with out_norm) */
+    void *out;          /* [M, C], row stride ld_out, or NULL */
+    void *out_norm;     /* [M, C], row stride ld_norm, or NULL */
+    float *stats;       /* [M] fp32 or NULL */
+    int32_t ld_res, ld_a, ld_out, ld_norm; /* in elements */
+    int32_t M, C, dtype;
+    float eps;
+} svdq_t5_residual_norm_args;
+
+/* Alignment of the operands of svdq_t5_residual_norm.  A pointer or stride that is no multiple of its line is refused with SVDQ_E_INVALID before
+ * anything is launched; NULL counts as aligned:
+ *   res, a, weight, out, out_norm    16 bytes
+ *   stats                            4 bytes
+ *   ld_res, ld_a, ld_out, ld_norm    8 elements */
+/* Addressing reach:
+ *   ld_res, ld_a, ld_out, ld_norm   the field's width: (size_t)row * ld
+ *   M, M * ld                       int32 rows; 64-bit product */
+int svdq_t5_residual_norm(const svdq_t5_residual_norm_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Z-Image block glue, part 2: per-head RMSNorm of Q and K, RoPE and V^T (added WITHOUT a version bump, as above.  reference:
  * NunchakuZSingleStreamAttnProcessor, nunchaku/models/attention_processors/zimage.py:35-88 -- two RMSNorms over head_dim, a rotation
  * through fp32 complex tensors, three unflatten / transpose copies into SDPA).  One sample per launch.  qkv is the packed
@@ -1304,6 +1342,69 @@ typedef struct svdq_gemm_awq_args {
 int svdq_gemm_awq(const svdq_gemm_awq_args *args, void *stream);
 /* workspace bytes a launch of this shape uses (0: it does not split K) */
 int64_t svdq_gemm_awq_workspace_bytes(int32_t M, int32_t N, int32_t K);
+
+/* ------------------------------------------------------------------------------------------
+ * AWQ W4A16 GEMM with one x operand and 1 to 3 weight sets in one launch (added WITHOUT a version bump: two new symbols and a new args
+ * struct, nothing existing changes, so SVDQ_ABI_VERSION stays 24).  The T5 encoder's q / k / v projections of one normed input, and its
+ * gated-GELU feed-forward (T5DenseGatedActDense: act(wi_0(x)) * wi_1(x)).  Set i is a checkpoint's qweight [N_i/4, K], scales /
+ * scaled_zeros [>= K/128, N_i] and an optional bias [N_i], exactly svdq_gemm_awq's operands and dequantisation:
+ *   w16_i[n, k] = round16( fma(q_i[n,k], scales_i[k/128, n], scaled_zeros_i[k/128, n]) )
+ *   y_i[m, n]   = round16( sum_k w16_i[n,k] * x[m,k] )  (+ bias_i[n]: one more 16-bit rounding)      fp32 sums, K-steps ascending
+ * mode SVDQ_AWQ_MULTI_CONCAT (1 to 3 sets):   out[m, off_i + n] = y_i[m, n],  off_i = sum_{j<i} N_j;  out is [M, sum N_i], row stride ldo.
+ *   Where neither launch splits K this is svdq_gemm_awq's result per set bit for bit.  K-split as svdq_gemm_awq's: slices of K-steps store
+ *   fp32 tiles into `workspace`, a second kernel adds them in slice order.  workspace = NULL: no split.
+ * mode SVDQ_AWQ_MULTI_GATED_GELU_NEW (exactly 2 sets, N_0 == N_1 == N):   out[m, n] = round16( round16(gelu_new(g)) * u ),
+ *   g = y_0[m, n], u = y_1[m, n];  out is [M, N].  gelu_new(g) = 0.5 g (1 + tanh(sqrt(2/pi) (g + 0.044715 g^3))) is evaluated in fp32 from
+ *   the rounded g as g * rcp(1 + exp2(a')), a = -2 sqrt(2/pi) (g + 0.044715 g^3), a' = log2(e) a (hardware exp2 / rcp), within
+ *       |gelu_new(g)| * (6 + 5 max(0.54, a')) * 2^-24 + |g| * 2^-126
+ *   of the exact value; where that bound could move the 16-bit rounding (a one-ulp move of the activation moves the product by up to
+ *   two ulps) the element is evaluated again in fp64.  The product of the two 16-bit factors is exact in fp32 and rounded once.  The
+ *   activation is round16(v) for a v within
+ *       |gelu_new(g)| * (8 + 8 max(1, a)) * 2^-53 + |g| * 2^-126
+ *   of the exact gelu_new(g).  Large |g| gives g (g > 0) or -0 (g < 0) exactly; no NaN for finite g.  GATED never splits K (the
+ *   activation is not linear in the partial sums); its workspace query returns 0 and a workspace is ignored.
+ * The plan (tile rows, K-split) is made on the host from (M, sum N_i, K, mode) alone, not from the device.  Results are bit-identical
+ * from launch to launch: no atomics, no workgroup waits for another.  fp16 values beyond the range go to +-inf, as in svdq_gemm_awq.
+ * Validation (no launch), SVDQ_E_INVALID: NULL args, x or out, a set's qweight / scales / scaled_zeros NULL, unknown dtype or mode, reserved
+ * != 0, count outside 1..3, M < 1, K or an N_i not a positive multiple of 128 / 64, GATED with count != 2 or N_0 != N_1, ldx < K or ldx % 8,
+ * ldo below out's width or ldo % 4, a misaligned pointer, a workspace smaller than svdq_gemm_awq_multi_workspace_bytes.
+ * SVDQ_E_UNSUPPORTED: group_size != 128.
+ * ------------------------------------------------------------------------------------------ */
+#define SVDQ_AWQ_MULTI_MAX_SETS 3
+#define SVDQ_AWQ_MULTI_CONCAT 0
+#define SVDQ_AWQ_MULTI_GATED_GELU_NEW 1
+typedef struct svdq_gemm_awq_multi_args {
+    const void *x;                                     /* [M, K] 16-bit, row stride ldx */
+    const void *qweight[SVDQ_AWQ_MULTI_MAX_SETS];      /* set i: [N_i/4, K] int16 */
+    const void *scales[SVDQ_AWQ_MULTI_MAX_SETS];       /* set i: [G_pad, N_i] 16-bit */
+    const void *scaled_zeros[SVDQ_AWQ_MULTI_MAX_SETS]; /* set i: [G_pad, N_i] 16-bit */
+    const void *bias[SVDQ_AWQ_MULTI_MAX_SETS];         /* set i: [N_i] 16-bit or NULL */
+    void *out;                                         /* [M, sum N_i] (CONCAT) / [M, N] (GATED) 16-bit, row stride ldo */
+    void *workspace;                                   /* fp32 partial tiles of CONCAT's K-split, or NULL */
+    int64_t workspace_bytes;
+    int32_t N[SVDQ_AWQ_MULTI_MAX_SETS];                /* entries from `count` on are not read */
+    int32_t count;                                     /* weight sets: 1..3 */
+    int32_t M, K, ldx, ldo;
+    int32_t group_size;                                /* must be 128 */
+    int32_t dtype;                                     /* SVDQ_BF16 | SVDQ_FP16 */
+    int32_t mode;                                      /* SVDQ_AWQ_MULTI_CONCAT | SVDQ_AWQ_MULTI_GATED_GELU_NEW */
+    int32_t reserved;                                  /* must be 0 */
+} svdq_gemm_awq_multi_args;
+
+/* Alignment of the operands of svdq_gemm_awq_multi.  A pointer or stride that is no multiple of its line is refused with SVDQ_E_INVALID before
+ * anything is launched; NULL counts as aligned:
+ *   x, qweight[i], workspace             16 bytes
+ *   out                                  8 bytes: the K-split's second kernel stores four elements at a time
+ *   scales[i], scaled_zeros[i], bias[i]  2 bytes
+ *   ldx                                  8 elements
+ *   ldo                                  4 elements */
+/* Addressing reach:
+ *   ldx, ldo                 the field's width: (size_t)row * ld
+ *   M, M * ld, M * sum N_i   int32 rows; 64-bit products
+ *   sum N_i                  must fit int32 (else SVDQ_E_INVALID) */
+int svdq_gemm_awq_multi(const svdq_gemm_awq_multi_args *args, void *stream);
+/* workspace bytes a launch of this shape uses (0: it does not split K; always 0 for GATED).  N_total = sum N_i */
+int64_t svdq_gemm_awq_multi_workspace_bytes(int32_t M, int32_t N_total, int32_t K, int32_t mode);
 
 /* ------------------------------------------------------------------------------------------
  * Load-time re-layout of reference checkpoint tensors (NVIDIA fragment order -> CDNA4 order).

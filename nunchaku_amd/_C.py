@@ -949,6 +949,63 @@ class _Ops:
         return out
 
     @staticmethod
+    def gemm_awq_multi(in_feats, sets, gated=False, out=None):
+        """Extension (T5 encoder): ``svdq_gemm_awq_multi`` -- one ``in_feats`` against 1 to 3 weight sets in one launch.  ``sets``: tuples
+        ``(kernel, scaling_factors, zeros, bias or None)`` of :meth:`gemm_awq` operands (group 128).  ``gated`` False: the sets' outputs side by
+        side, ``[..., sum N_i]``, each what :meth:`gemm_awq` gives; True (two sets of equal N): ``gelu_new(set 0) * set 1``, ``[..., N]``, the
+        two projections never written.  ``out``: None (allocated) or a 16-bit tensor of that shape with unit column stride and uniformly strided
+        rows -- a column slice of a wider buffer will do.  Every check is made, by this wrapper or the library, before anything is launched."""
+        op, lib = "gemm_awq_multi", _lib.load()
+        sets = list(sets)
+        if not 1 <= len(sets) <= _lib.AWQ_MULTI_MAX_SETS:
+            raise ValueError(f"{op}: {len(sets)} weight sets (1 to {_lib.AWQ_MULTI_MAX_SETS})")
+        if in_feats.dtype not in _DT or in_feats.dim() < 1:
+            raise ValueError(f"{op}: in_feats must be a 16-bit tensor")
+        K, dtype = in_feats.shape[-1], in_feats.dtype
+        a, Ns = _lib.ARGS["svdq_gemm_awq_multi_args"](), []
+        for i, (kernel, scaling_factors, zeros, bias) in enumerate(sets):
+            if kernel.dim() != 2 or kernel.dtype not in (torch.int16, torch.int32) or kernel.shape[1] * kernel.element_size() != 2 * K:
+                raise ValueError(f"{op}: set {i}: kernel must be the [N/4, K] int16 (or [N/4, K/2] int32) qweight for K={K}")
+            N = kernel.shape[0] * 4
+            if (scaling_factors.dtype != dtype or scaling_factors.dim() != 2 or scaling_factors.shape[1] != N or scaling_factors.shape[0] < K // 128
+                    or zeros.shape != scaling_factors.shape or zeros.dtype != dtype):
+                raise ValueError(f"{op}: set {i}: scaling_factors / zeros must be [>= K/128, N] in the dtype of in_feats")
+            if bias is not None and (bias.dtype != dtype or bias.numel() != N):
+                raise ValueError(f"{op}: set {i}: bias must be [N] in the dtype of in_feats")
+            a.qweight[i], a.scales[i], a.scaled_zeros[i], a.bias[i] = _ptr(kernel), _ptr(scaling_factors), _ptr(zeros), _ptr(bias)
+            a.N[i] = _i32(op, f"N of set {i}", N)
+            Ns.append(N)
+        if gated and (len(Ns) != 2 or Ns[0] != Ns[1]):
+            raise ValueError(f"{op}: the gated mode takes exactly two sets of equal N, got N = {Ns}")
+        width = Ns[0] if gated else sum(Ns)
+        M = in_feats.numel() // K if K else 0
+        if out is None:
+            out = torch.empty(*in_feats.shape[:-1], width, dtype=dtype, device=in_feats.device)
+        elif (out.dtype != dtype or out.device != in_feats.device or tuple(out.shape) != (*in_feats.shape[:-1], width) or out.stride(-1) != 1
+              or any(out.shape[i + 1] > 1 and out.shape[i] > 1 and out.stride(i) != out.stride(i + 1) * out.shape[i + 1] for i in range(out.dim() - 2))):
+            raise ValueError(f"{op}: out must be {(*in_feats.shape[:-1], width)} {dtype} with unit column stride and uniformly strided rows")
+        if M == 0:
+            return out
+        x2 = in_feats.reshape(M, K)
+        if x2.stride(1) != 1 or (M > 1 and x2.stride(0) % 8) or x2.data_ptr() % 16:
+            x2 = x2.contiguous()
+        # (the strides of dimensions of size 1 are arbitrary in torch: the library gets the natural ones)
+        row_strides = [out.stride(i) for i in range(out.dim() - 1) if out.shape[i] > 1]
+        a.x, a.out = _ptr(x2, True), _ptr(out, True)
+        a.M, a.K, a.count = _i32(op, "M", M), _i32(op, "K", K), len(Ns)
+        a.ldx = _i32(op, "in_feats row stride", x2.stride(0) if M > 1 else K)
+        a.ldo = _i32(op, "out row stride", row_strides[-1] if row_strides else width)
+        a.group_size, a.dtype, a.mode = 128, _DT[dtype], _lib.AWQ_MULTI_GATED_GELU_NEW if gated else _lib.AWQ_MULTI_CONCAT
+        if K % 128 == 0 and all(N % 64 == 0 for N in Ns):  # (otherwise the library reports the shape)
+            need = int(lib.svdq_gemm_awq_multi_workspace_bytes(M, _i32(op, "sum of N", sum(Ns)), K, a.mode))
+            if need:
+                ws = _workspace(in_feats.device, "awq", min_bytes=need)
+                if ws.buf.numel() >= need:  # (a capture cannot grow the buffer: that launch runs without the K-split)
+                    a.workspace, a.workspace_bytes = ws.buf.data_ptr(), ws.buf.numel()
+        _lib.check(lib.svdq_gemm_awq_multi(C.byref(a), _stream()), op)
+        return out
+
+    @staticmethod
     def gemv_awq_batched(in_feats, layers):
         """Extension: the AWQ GEMVs of ``layers`` (``AWQW4A16Linear``-like objects: ``qweight, wscales, wzeros, bias,
         out_features, in_features, group_size, out_chunks``) on the same single-row ``in_feats`` in ONE launch per 80
@@ -1450,6 +1507,28 @@ class _Ops:
         args.scale_bs = _i64(op, "scale.stride(0)", 0 if scale is None else scale.stride(0) if B > 1 else C_feat)
         args.M, args.T, args.C, args.dtype, args.eps = _i32(op, "M", M), _i32(op, "T", T), _i32(op, "C", C_feat), _DT[dtype], float(eps)
         _lib.check(lib.svdq_sandwich_norm(C.byref(args), _stream()), op)
+
+    @staticmethod
+    def t5_residual_norm(res, a, weight, out, out_norm, stats, eps=1e-6):
+        """Extension (T5 encoder): ``svdq_t5_residual_norm`` -- ``y = res + a`` (``a`` None: ``y = res``) to ``out``, T5LayerNorm
+        ``weight * (y * rstd(y))`` to ``out_norm``, ``rstd(y)`` to ``stats`` (float32 ``[M]``), each where given.  ``res`` / ``a`` / ``out`` /
+        ``out_norm``: 2-D 16-bit row views with unit column stride, each with its own row stride; ``weight``: contiguous ``[C]``.  What is
+        None here and required there the library judges."""
+        op, lib, args = "t5_residual_norm", _lib.load(), _lib.ARGS["svdq_t5_residual_norm_args"]()
+        M, C_feat, ld_res, dt = _row_view(op, "res", res)
+        lds = [ld_res if M > 1 else C_feat]  # (the stride of a dimension of size 1 is arbitrary in torch)
+        for name, t in (("a", a), ("out", out), ("out_norm", out_norm)):
+            if t is not None and (t.dim() != 2 or tuple(t.shape) != (M, C_feat) or t.dtype != res.dtype or t.stride(1) != 1):
+                raise ValueError(f"{op}: {name} must be a [{M}, {C_feat}] view in the dtype of res with unit column stride")
+            lds.append(0 if t is None else _i32(op, f"{name}.stride(0)", t.stride(0) if M > 1 else C_feat))
+        _vector(op, "res", res, weight=weight)
+        if stats is not None and (stats.dtype != torch.float32 or stats.numel() != M or not stats.is_contiguous()):
+            raise ValueError(f"{op}: stats must be contiguous float32 [{M}]")
+        args.res, args.a, args.out, args.out_norm = _ptr(res, True), _ptr(a, True), _ptr(out, True), _ptr(out_norm, True)
+        args.weight, args.stats = _ptr(weight), _ptr(stats)
+        args.ld_res, args.ld_a, args.ld_out, args.ld_norm = (_i32(op, "row stride", ld) for ld in lds)
+        args.M, args.C, args.dtype, args.eps = _i32(op, "M", M), _i32(op, "C", C_feat), dt, float(eps)
+        _lib.check(lib.svdq_t5_residual_norm(C.byref(args), _stream()), op)
 
     @staticmethod
     def qk_norm_rope(qkv, norm_q, norm_k, freqs, vt, rstd, T, L_pad, H, eps=1e-5):

@@ -70,6 +70,42 @@ def _quantize_dwconv_glu_args():
 ARGS["svdq_quantize_dwconv_glu_args"] = _quantize_dwconv_glu_args()
 
 
+AWQ_MULTI_MAX_SETS, AWQ_MULTI_CONCAT, AWQ_MULTI_GATED_GELU_NEW = 3, 0, 1
+
+
+def _gemm_awq_multi_args():
+    class GemmAwqMultiArgs(C.Structure):
+        """svdq_gemm_awq_multi_args"""
+        _fields_ = [
+            ("x", C.c_void_p), ("qweight", C.c_void_p * AWQ_MULTI_MAX_SETS), ("scales", C.c_void_p * AWQ_MULTI_MAX_SETS),
+            ("scaled_zeros", C.c_void_p * AWQ_MULTI_MAX_SETS), ("bias", C.c_void_p * AWQ_MULTI_MAX_SETS),
+            ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+            ("N", C.c_int32 * AWQ_MULTI_MAX_SETS), ("count", C.c_int32),
+            ("M", C.c_int32), ("K", C.c_int32), ("ldx", C.c_int32), ("ldo", C.c_int32),
+            ("group_size", C.c_int32), ("dtype", C.c_int32), ("mode", C.c_int32), ("reserved", C.c_int32),
+        ]
+
+    return GemmAwqMultiArgs
+
+
+def _t5_residual_norm_args():
+    class T5ResidualNormArgs(C.Structure):
+        """svdq_t5_residual_norm_args"""
+        _fields_ = [
+            ("res", C.c_void_p), ("a", C.c_void_p), ("weight", C.c_void_p), ("out", C.c_void_p), ("out_norm", C.c_void_p), ("stats", C.c_void_p),
+            ("ld_res", C.c_int32), ("ld_a", C.c_int32), ("ld_out", C.c_int32), ("ld_norm", C.c_int32),
+            ("M", C.c_int32), ("C", C.c_int32), ("dtype", C.c_int32), ("eps", C.c_float),
+        ]
+
+    return T5ResidualNormArgs
+
+
+# (ldx / ldo and ld_res / ld_a / ld_out / ld_norm: unbounded, 64-bit row addresses -- as svdq_gemm_awq's and svdq_sandwich_norm's; reached
+# through the table like the structs above)
+ARGS["svdq_gemm_awq_multi_args"] = _gemm_awq_multi_args()
+ARGS["svdq_t5_residual_norm_args"] = _t5_residual_norm_args()
+
+
 class ResidualArgs(C.Structure):
     _fields_ = [
         ("res", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("gate", C.c_void_p), ("out", C.c_void_p),
@@ -289,6 +325,9 @@ EXPORTS = {
     "svdq_gemv_awq_lora_batched": (C.c_int, [C.POINTER(GemvLoraArgs), C.c_int32, C.c_void_p]),
     "svdq_gemm_awq": (C.c_int, [C.POINTER(GemmAwqArgs), C.c_void_p]),
     "svdq_gemm_awq_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "svdq_gemm_awq_multi": (C.c_int, [C.POINTER(ARGS["svdq_gemm_awq_multi_args"]), C.c_void_p]),
+    "svdq_gemm_awq_multi_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "svdq_t5_residual_norm": (C.c_int, [C.POINTER(ARGS["svdq_t5_residual_norm_args"]), C.c_void_p]),
     "svdq_residual_gate_stats": (C.c_int, [C.POINTER(ResidualArgs), C.c_void_p]),
     "svdq_residual_diff": (C.c_int, [C.POINTER(ResidualDiffArgs), C.c_void_p]),
     "svdq_modulated_diff": (C.c_int, [C.POINTER(ModulatedDiffArgs), C.c_void_p]),

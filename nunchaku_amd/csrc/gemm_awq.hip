@@ -302,3 +302,332 @@ extern "C" int svdq_gemm_awq(const svdq_gemm_awq_args *a, void *stream) {
     else launch_gemm_awq<SVDQ_FP16>(a, p, st);
     return hip_check(hipGetLastError(), "svdq_gemm_awq launch");
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// svdq_gemm_awq_multi: ONE x operand, 1 to 3 weight sets, one launch (the T5 encoder's q / k / v over the same normed input, and its
+// gated-GELU feed-forward wi_0 / wi_1).  A second kernel family on the dequantisation, the LDS images and the fragment reads above; the
+// kernels above are not touched.  The x tile is staged as there; what changes is where a workgroup's 128 rows of the B image come from.
+//
+// CONCAT: the column tiles of the sets are laid side by side (set i: ceil(N_i / 128) tiles from tile0[i]); a workgroup's column tile selects
+//   its set (workgroup-uniform) and it writes columns [off_i + n0, off_i + n0 + 128) of out [M, sum N_i] (row stride ldo).  Per element the MFMA
+//   sequence is gemm_awq_kernel's -- K-steps ascending, slices ascending -- so without a K-split the result is that of separate launches bit
+//   for bit.  The K-split stores fp32 tiles into ws [splits][M][sum N_i]; awq_multi_reduce_kernel adds, rounds, adds the set's bias.
+// GATED (gelu_new): a workgroup owns 64 output channels and its B image holds BOTH projections of them:
+//   rows [0, 32) gate n0 .. n0+31 | [32, 64) value n0 .. n0+31 | [64, 96) gate n0+32 .. n0+63 | [96, 128) value n0+32 .. n0+63
+//   Waves are 2 x 2 (rows x channel halves): wave column wn reads B rows [64 wn, 64 wn + 64), so its accumulator tile j = 0 holds g and
+//   j = 1 holds u of the SAME (row, channel) in the same lane and register: the two 16-bit roundings, the activation and the product happen
+//   in registers and the [M, 2N] intermediate never exists.  N % 64 == 0 leaves no ragged tile (d_ff = 640: ten workgroups per row block).
+//   BM is 64 or 128 (a 32-row tile would leave a wave half a MFMA tile).  GATED never splits K: the activation is not linear, a reduction
+//   kernel would have to carry it and the [M, 2N] fp32 partials; at N = 10240 even M = 8 launches 160 workgroups.
+//
+// gelu_new(g) = 0.5 g (1 + tanh(z)), z = sqrt(2/pi) (g + 0.044715 g^3), is evaluated in fp32 as g * rcp(1 + exp2(a)), a = -2 log2(e) z: 1 + tanh(z) =
+// 2 / (1 + e^(-2z)), no difference of exponentials and no inf / inf.  a -> -inf gives g * rcp(1) = g, a -> +inf gives g * rcp(inf) = -0.
+// Error of the fp32 activation against the exact gelu_new of the same (16-bit) g, with u = 2^-24, v_exp_f32 and v_rcp_f32 at 1 ulp = 2u:
+//   a carries 7 roundings, so exp2(a) a relative error of 7 ln2 |a| u + 2u; 1 + e, rcp and the product add 4u; the error of e reaches the
+//   result times e / (1 + e), and |a| e / (1 + e) <= max(0.54, a).  v_rcp_f32 flushes subnormal results: below |g| 2^-126 the result is -0.
+//   |act32 - gelu_new(g)| <= b32 = |gelu_new(g)| * (6 + 5 max(0.54, a)) * 2^-24 + |g| * 2^-126
+// A one-ulp move of the activation's 16-bit rounding moves the product act * u by up to TWO of its ulps, so the rounding is not left to the
+// fp32 value where that value cannot decide it (Ziv's test): if round16(act32 - b32) != round16(act32 + b32) -- 0.03 % (bf16) to 0.3 % (fp16)
+// of the elements -- or a >= 120 (the flush above), the element is evaluated again in fp64 (g^3 is exact there; five roundings in the
+// exponent, the device library's exp at 1 ulp, the sum and the quotient), rounded to odd into fp32 and from there once to 16 bits:
+//   the activation is round16(v) for a v within  |gelu_new(g)| * (8 + 8 max(1, a)) * 2^-53 + |g| * 2^-126  of the exact gelu_new(g)
+// (the second term: a subnormal fp32 on the way to bf16 may be flushed).
+namespace svdq {
+
+constexpr int AWQ_MULTI_SETS = SVDQ_AWQ_MULTI_MAX_SETS;
+
+struct AwqMultiSets {
+    const uint8_t *qw[AWQ_MULTI_SETS];
+    const uint16_t *sc[AWQ_MULTI_SETS], *zr[AWQ_MULTI_SETS], *bias[AWQ_MULTI_SETS];
+    int N[AWQ_MULTI_SETS], off[AWQ_MULTI_SETS], tile0[AWQ_MULTI_SETS]; // off / tile0 of an unused set: INT_MAX (never selected)
+};
+// (explicit selects: a dynamic index into the by-value struct could send it to scratch)
+template <typename P> __device__ __forceinline__ P awq_pick(const P (&arr)[AWQ_MULTI_SETS], int set) {
+    return set == 0 ? arr[0] : set == 1 ? arr[1] : arr[2];
+}
+
+// the fp64 evaluation, rounded to odd into fp32: 13 or more bits below a 16-bit mantissa, so the round-to-nearest-even that follows is the
+// one rounding of the fp64 value
+__device__ __forceinline__ float awq_gelu_new_f64(float g) {
+    const double x = (double)g;
+    const double d = x / (1.0 + exp(-1.5957691216057308 * (x + 0.044715 * (x * x * x)))); // 2 sqrt(2 / pi)
+    float f = (float)d;
+    if ((double)f != d) {
+        unsigned bits = __builtin_bit_cast(unsigned, f);
+        if (fabs((double)f) > fabs(d)) bits -= 1; // towards zero
+        f = __builtin_bit_cast(float, bits | 1u);
+    }
+    return f;
+}
+
+// round16(gelu_new(g)) as a float: fp32 where its error bound cannot move the 16-bit rounding, fp64 elsewhere (NaN takes the second path)
+template <typename T> __device__ __forceinline__ float awq_gelu_new16(float g) {
+    const float a = -2.3022082137f * (g + (0.044715f * (g * g)) * g); // -2 * sqrt(2 / pi) * log2(e)
+    const float act = g * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(a));
+    const float b = fabsf(act) * ((6.0f + 5.0f * fmaxf(0.54f, a)) * 0x1p-24f) + fabsf(g) * 0x1p-126f;
+    const float lo = round16<T>(act - b), hi = round16<T>(act + b);
+    if (lo == hi && a < 120.0f) return lo;
+    return round16<T>(awq_gelu_new_f64(g));
+}
+
+template <int DT, int BM, bool GATED>
+__global__ __launch_bounds__(256, 2) void awq_multi_gemm_kernel(const uint16_t *__restrict__ x, const AwqMultiSets P, uint16_t *__restrict__ out,
+                                                                 float *__restrict__ ws, int M, int Ntot, int K, int ldx, int ldo, int tiles_n,
+                                                                 int splits) {
+    using T = typename Half<DT>::T;
+    using V8 = typename Half<DT>::V8;
+    constexpr int WM = (GATED || BM == 128) ? 2 : 1, WN = 4 / WM, TM = BM / WM, TN = AWQ_BN / WN, RM = TM / 32, RN = TN / 32;
+    static_assert(!GATED || (BM >= 64 && RN == 2), "GATED: a wave holds the gate tile and the value tile of its 32 channels");
+    constexpr int XL = BM / 16;
+    __shared__ __attribute__((aligned(16))) uint16_t lds[(BM + AWQ_BN) * AWQ_ROW];
+    uint16_t *As = lds, *Bs = lds + BM * AWQ_ROW;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int bn = (int)blockIdx.x % tiles_n, bm = (int)blockIdx.x / tiles_n, sl = blockIdx.z;
+    const int m0 = bm * BM;
+    const int KS = K / AWQ_GEMM_GROUP;
+    const int kb0 = (int)((long long)sl * KS / splits), kb1 = (int)((long long)(sl + 1) * KS / splits);
+
+    // code loader as in gemm_awq_kernel: this thread dequantises row 4 qrg + qr of the B image, 64 channels (chunk qc) per K-step
+    const int qrg = tid >> 3, qc = (tid >> 2) & 1, qr = tid & 3;
+    int set, n0, ch; // the set this thread (CONCAT: this workgroup) reads, the tile's first channel in it, this thread's channel
+    if constexpr (GATED) {
+        set = (qrg >> 3) & 1;
+        n0 = bn * 64;
+        ch = n0 + (qrg >> 4) * 32 + 4 * (qrg & 7) + qr;
+    } else {
+        set = (bn >= P.tile0[1]) + (bn >= P.tile0[2]);
+        n0 = (bn - awq_pick(P.tile0, set)) * AWQ_BN;
+        // a row group beyond N_i (N_i % 128 == 64) reads channel 0: it only reaches accumulator columns that are never stored
+        ch = n0 + 4 * qrg < awq_pick(P.N, set) ? n0 + 4 * qrg + qr : 0;
+    }
+    const int Nset = awq_pick(P.N, set);
+    const uint8_t *qsrc = awq_pick(P.qw, set) + (size_t)(ch >> 2) * K * 2 + qc * 128 + (ch & 3) * 32;
+    const uint16_t *ssrc = awq_pick(P.sc, set) + ch, *zsrc = awq_pick(P.zr, set) + ch;
+
+    v4i xr[XL], q0, q1;
+    unsigned sb, zb;
+    auto load = [&](int kb) {
+        const int k0 = kb * AWQ_GEMM_GROUP;
+#pragma unroll
+        for (int i = 0; i < XL; i++) {
+            const int p = i * 256 + tid, row = p >> 4, col = p & 15;
+            xr[i] = *reinterpret_cast<const v4i *>(x + (size_t)(m0 + row < M ? m0 + row : 0) * ldx + k0 + col * 8);
+        }
+        q0 = *reinterpret_cast<const v4i *>(qsrc + (size_t)k0 * 2);
+        q1 = *reinterpret_cast<const v4i *>(qsrc + (size_t)k0 * 2 + 16);
+        sb = ssrc[(size_t)kb * Nset];
+        zb = zsrc[(size_t)kb * Nset];
+    };
+    unsigned magic = 0x64006400u;
+    asm volatile("" : "+v"(magic));
+
+    v16f acc[RM][RN];
+#pragma unroll
+    for (int i = 0; i < RM; i++)
+#pragma unroll
+        for (int j = 0; j < RN; j++)
+#pragma unroll
+            for (int v = 0; v < 16; v++) acc[i][j][v] = 0.f;
+
+    const int wm = wave / WN, wn = wave % WN;
+    const uint16_t *afrag = As + (wm * TM + (lane & 31)) * AWQ_ROW + 8 * (lane >> 5);
+    const uint16_t *bfrag = Bs + (wn * TN + (lane & 31)) * AWQ_ROW + 8 * (lane >> 5);
+
+    if (kb0 < kb1) load(kb0);
+    for (int kb = kb0; kb < kb1; kb++) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < XL; i++) {
+            const int p = i * 256 + tid, row = p >> 4, col = p & 15;
+            *reinterpret_cast<v4i *>(As + row * AWQ_ROW + col * 8) = xr[i];
+        }
+        awq_dequant64<DT>(Bs + (4 * qrg + qr) * AWQ_ROW + 64 * qc, q0, q1, sb, zb, magic);
+        __syncthreads();
+        if (kb + 1 < kb1) load(kb + 1);
+#pragma unroll
+        for (int kk = 0; kk < AWQ_GEMM_GROUP / 16; kk++) {
+            V8 a[RM], b[RN];
+#pragma unroll
+            for (int i = 0; i < RM; i++) a[i] = *reinterpret_cast<const V8 *>(afrag + i * 32 * AWQ_ROW + kk * 16);
+#pragma unroll
+            for (int j = 0; j < RN; j++) b[j] = *reinterpret_cast<const V8 *>(bfrag + j * 32 * AWQ_ROW + kk * 16);
+#pragma unroll
+            for (int i = 0; i < RM; i++)
+#pragma unroll
+                for (int j = 0; j < RN; j++) acc[i][j] = Half<DT>::mfma32(a[i], b[j], acc[i][j]);
+        }
+    }
+
+    // accumulator register v of tile (i, j): row (v & 3) + 8 (v >> 2) + 4 (lane >> 5), column lane & 31
+    if constexpr (GATED) {
+        const int n = n0 + wn * 32 + (lane & 31); // < N: N % 64 == 0
+        const float bg = P.bias[0] ? h2f(hfrom<T>(P.bias[0][n])) : 0.f, bu = P.bias[1] ? h2f(hfrom<T>(P.bias[1][n])) : 0.f;
+#pragma unroll
+        for (int i = 0; i < RM; i++)
+#pragma unroll
+            for (int v = 0; v < 16; v++) {
+                const int m = m0 + wm * TM + i * 32 + (v & 3) + 8 * (v >> 2) + 4 * (lane >> 5);
+                if (m >= M) continue;
+                float g = round16<T>(acc[i][0][v]), u = round16<T>(acc[i][1][v]);
+                if (P.bias[0]) g = round16<T>(g + bg);
+                if (P.bias[1]) u = round16<T>(u + bu);
+                const float act = awq_gelu_new16<T>(g);
+                out[(size_t)m * ldo + n] = hbits(f2h<T>(act * u)); // (two 16-bit factors: the fp32 product is exact, one rounding)
+            }
+    } else {
+        const uint16_t *bias = awq_pick(P.bias, set);
+        const int off = awq_pick(P.off, set);
+#pragma unroll
+        for (int i = 0; i < RM; i++)
+#pragma unroll
+            for (int j = 0; j < RN; j++) {
+                const int n = n0 + wn * TN + j * 32 + (lane & 31);
+                if (n >= Nset) continue;
+                float bv = 0.f;
+                if (splits == 1 && bias) bv = h2f(hfrom<T>(bias[n]));
+#pragma unroll
+                for (int v = 0; v < 16; v++) {
+                    const int m = m0 + wm * TM + i * 32 + (v & 3) + 8 * (v >> 2) + 4 * (lane >> 5);
+                    if (m >= M) continue;
+                    if (splits > 1) {
+                        ws[((size_t)sl * M + m) * Ntot + off + n] = acc[i][j][v];
+                    } else {
+                        float y = round16<T>(acc[i][j][v]);
+                        if (bias) y = round16<T>(y + bv);
+                        out[(size_t)m * ldo + off + n] = hbits(f2h<T>(y));
+                    }
+                }
+            }
+    }
+}
+
+// CONCAT's K-split, second kernel: as gemm_awq_reduce_kernel over [M, sum N_i], with the bias of the set a column belongs to and out's
+// row stride.  Four columns per thread: sum N_i and every off_i are multiples of 64, so a quad lies in one row and one set.
+template <int DT>
+__global__ __launch_bounds__(256) void awq_multi_reduce_kernel(const float *__restrict__ ws, const AwqMultiSets P, uint16_t *__restrict__ out, int M,
+                                                                     int Ntot, int ldo, int splits) {
+    using T = typename Half<DT>::T;
+    const size_t MN = (size_t)M * Ntot, idx = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (idx >= MN) return;
+    v4f a = *reinterpret_cast<const v4f *>(ws + idx);
+    for (int s = 1; s < splits; s++) a += *reinterpret_cast<const v4f *>(ws + (size_t)s * MN + idx);
+    const size_t m = idx / Ntot;
+    const int n = (int)(idx % Ntot);
+    const int set = (n >= P.off[1]) + (n >= P.off[2]);
+    const uint16_t *bias = awq_pick(P.bias, set);
+    const int nl = n - awq_pick(P.off, set);
+    u16x4 o;
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        float y = round16<T>(a[t]);
+        if (bias) y = round16<T>(y + h2f(hfrom<T>(bias[nl + t])));
+        o[t] = hbits(f2h<T>(y));
+    }
+    *reinterpret_cast<u16x4 *>(out + m * ldo + n) = o;
+}
+
+// host-only, from (M, sum N_i, K, mode): the tile rows, and for CONCAT awq_plan's K-split rule on ceil(sum N_i / 128) column tiles (the
+// launch itself has sum ceil(N_i / 128) of them: never fewer)
+static AwqPlan awq_multi_plan(int M, int Ntot, int K, int mode, bool with_workspace) {
+    AwqPlan p = awq_plan(M, Ntot, K, with_workspace && mode == SVDQ_AWQ_MULTI_CONCAT);
+    if (mode == SVDQ_AWQ_MULTI_GATED_GELU_NEW) {
+        p.bm = M <= 64 ? 64 : 128;
+        p.tiles_m = (M + p.bm - 1) / p.bm;
+        p.tiles_n = Ntot / 128; // Ntot = 2 N: one workgroup per 64 output channels
+    }
+    return p;
+}
+
+template <int DT> static void launch_gemm_awq_multi(const svdq_gemm_awq_multi_args *a, AwqPlan p, int Ntot, hipStream_t st) {
+    const bool gated = a->mode == SVDQ_AWQ_MULTI_GATED_GELU_NEW;
+    AwqMultiSets P;
+    int off = 0, tile = 0;
+    for (int i = 0; i < AWQ_MULTI_SETS; i++) {
+        const bool used = i < a->count;
+        P.qw[i] = used ? (const uint8_t *)a->qweight[i] : nullptr;
+        P.sc[i] = used ? (const uint16_t *)a->scales[i] : nullptr;
+        P.zr[i] = used ? (const uint16_t *)a->scaled_zeros[i] : nullptr;
+        P.bias[i] = used ? (const uint16_t *)a->bias[i] : nullptr;
+        P.N[i] = used ? a->N[i] : 0;
+        P.off[i] = used ? off : INT32_MAX;
+        P.tile0[i] = used ? tile : INT32_MAX;
+        if (used) { off += a->N[i]; tile += (a->N[i] + AWQ_BN - 1) / AWQ_BN; }
+    }
+    if (!gated) p.tiles_n = tile;
+    const dim3 grid(p.tiles_m * p.tiles_n, 1, p.splits), block(256);
+    const uint16_t *x = (const uint16_t *)a->x;
+    uint16_t *out = (uint16_t *)a->out;
+    float *ws = (float *)a->workspace;
+#define SVDQ_AWQ_MULTI_CASE(BMV, G)                                                                                                            \
+    hipLaunchKernelGGL((awq_multi_gemm_kernel<DT, BMV, G>), grid, block, 0, st, x, P, out, ws, a->M, Ntot, a->K, a->ldx, a->ldo, p.tiles_n, p.splits)
+    if (gated) {
+        if (p.bm == 64) SVDQ_AWQ_MULTI_CASE(64, true);
+        else SVDQ_AWQ_MULTI_CASE(128, true);
+    } else {
+        if (p.bm == 32) SVDQ_AWQ_MULTI_CASE(32, false);
+        else if (p.bm == 64) SVDQ_AWQ_MULTI_CASE(64, false);
+        else SVDQ_AWQ_MULTI_CASE(128, false);
+    }
+#undef SVDQ_AWQ_MULTI_CASE
+    if (p.splits > 1) {
+        const size_t quads = (size_t)a->M * Ntot / 4;
+        hipLaunchKernelGGL((awq_multi_reduce_kernel<DT>), dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, ws, P, out, a->M, Ntot, a->ldo,
+                           p.splits);
+    }
+}
+
+} // namespace svdq
+
+extern "C" int64_t svdq_gemm_awq_multi_workspace_bytes(int32_t M, int32_t N_total, int32_t K, int32_t mode) {
+    if (M < 1 || N_total < 1 || K < AWQ_GEMM_GROUP || (mode != SVDQ_AWQ_MULTI_CONCAT && mode != SVDQ_AWQ_MULTI_GATED_GELU_NEW)) return 0;
+    return awq_workspace_bytes(awq_multi_plan(M, N_total, K, mode, true), M, N_total);
+}
+
+extern "C" int svdq_gemm_awq_multi(const svdq_gemm_awq_multi_args *a, void *stream) {
+    const char *op = "svdq_gemm_awq_multi";
+    if (!a) { set_error("%s: args is NULL", op); return SVDQ_E_INVALID; }
+    if (!a->x || !a->out) { set_error("%s: x and out are required", op); return SVDQ_E_INVALID; }
+    if (a->dtype != SVDQ_BF16 && a->dtype != SVDQ_FP16) { set_error("%s: unknown dtype %d", op, a->dtype); return SVDQ_E_INVALID; }
+    if (a->mode != SVDQ_AWQ_MULTI_CONCAT && a->mode != SVDQ_AWQ_MULTI_GATED_GELU_NEW) { set_error("%s: unknown mode %d", op, a->mode); return SVDQ_E_INVALID; }
+    if (a->reserved) { set_error("%s: reserved must be 0", op); return SVDQ_E_INVALID; }
+    if (a->count < 1 || a->count > AWQ_MULTI_SETS) { set_error("%s: count=%d weight sets (1 to %d)", op, a->count, AWQ_MULTI_SETS); return SVDQ_E_INVALID; }
+    if (a->group_size != AWQ_GEMM_GROUP) {
+        set_error("%s: group_size=%d (only 128 is implemented)", op, a->group_size);
+        return SVDQ_E_UNSUPPORTED;
+    }
+    if (a->M < 1) { set_error("%s: M=%d must be >= 1", op, a->M); return SVDQ_E_INVALID; }
+    if (a->K <= 0 || a->K % AWQ_GEMM_GROUP) { set_error("%s: K=%d must be a positive multiple of 128", op, a->K); return SVDQ_E_INVALID; }
+    int64_t total = 0;
+    uintptr_t bits16 = (uintptr_t)a->x | (uintptr_t)a->workspace, bits2 = 0;
+    for (int i = 0; i < a->count; i++) {
+        if (!a->qweight[i] || !a->scales[i] || !a->scaled_zeros[i]) { set_error("%s: set %d: qweight, scales and scaled_zeros are required", op, i); return SVDQ_E_INVALID; }
+        if (a->N[i] <= 0 || a->N[i] % 64) { set_error("%s: N[%d]=%d must be a positive multiple of 64", op, i, a->N[i]); return SVDQ_E_INVALID; }
+        total += a->N[i];
+        bits16 |= (uintptr_t)a->qweight[i];
+        bits2 |= (uintptr_t)a->scales[i] | (uintptr_t)a->scaled_zeros[i] | (uintptr_t)a->bias[i];
+    }
+    if (total > INT32_MAX) { set_error("%s: the sets' %lld columns do not fit 32 bits", op, (long long)total); return SVDQ_E_INVALID; }
+    const bool gated = a->mode == SVDQ_AWQ_MULTI_GATED_GELU_NEW;
+    if (gated && (a->count != 2 || a->N[0] != a->N[1])) {
+        set_error("%s: GATED takes exactly two sets of equal N (count=%d, N = %d, %d)", op, a->count, a->N[0], a->count > 1 ? a->N[1] : 0);
+        return SVDQ_E_INVALID;
+    }
+    const int width = gated ? a->N[0] : (int)total; // columns of out
+    if (a->ldx < a->K || a->ldx % 8) { set_error("%s: ldx=%d must be >= K and a multiple of 8", op, a->ldx); return SVDQ_E_INVALID; }
+    if (a->ldo < width || a->ldo % 4) { set_error("%s: ldo=%d must be >= %d columns and a multiple of 4", op, a->ldo, width); return SVDQ_E_INVALID; }
+    if (bits16 & 15) { set_error("%s: x, qweight and workspace must be 16-byte aligned", op); return SVDQ_E_INVALID; }
+    if ((uintptr_t)a->out & 7) { set_error("%s: out must be 8-byte aligned", op); return SVDQ_E_INVALID; }
+    if (bits2 & 1) { set_error("%s: scales, scaled_zeros and bias must be 2-byte aligned", op); return SVDQ_E_INVALID; }
+    const AwqPlan p = awq_multi_plan(a->M, (int)total, a->K, a->mode, a->workspace != nullptr);
+    const int64_t need = awq_workspace_bytes(p, a->M, (int)total);
+    if (a->workspace && a->workspace_bytes < need) {
+        set_error("%s: workspace of %lld bytes; this launch needs %lld (svdq_gemm_awq_multi_workspace_bytes), 16-byte aligned", op,
+                  (long long)a->workspace_bytes, (long long)need);
+        return SVDQ_E_INVALID;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (a->dtype == SVDQ_BF16) launch_gemm_awq_multi<SVDQ_BF16>(a, p, (int)total, st);
+    else launch_gemm_awq_multi<SVDQ_FP16>(a, p, (int)total, st);
+    return hip_check(hipGetLastError(), "svdq_gemm_awq_multi launch");
+}

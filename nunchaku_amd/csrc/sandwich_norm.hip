@@ -151,3 +151,77 @@ extern "C" int svdq_sandwich_norm(const svdq_sandwich_norm_args *a, void *stream
     if (!launch_sandwich_norm(a, (hipStream_t)stream)) return row_class_unsupported(op, a->C);
     return hip_check(hipGetLastError(), "svdq_sandwich_norm launch");
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// svdq_t5_residual_norm: the T5 encoder's residual add and T5LayerNorm as one row pass, on the helpers above (row_rstd, mul16, op32) -- the
+// same wave-per-row, row-in-registers pass, with a plain 16-bit add where the sandwich has a normed and gated one:
+//
+//   y    = a ? round16(res + a) : res                                  -> out       (optional)
+//   rstd = 1 / sqrt(mean_c(float(y[c])^2) + eps)                       -> stats     (optional, one fp32 per row)
+//   n    = round16(w[c] * round16(float(y[c]) * rstd))                 -> out_norm  (with w)
+//
+// T5LayerNorm.forward's rounding points: the 16-bit tensor times the fp32 rsqrt is an fp32 product, one cast, then the 16-bit weight
+// multiply.  HBM-bound: at most 2 reads + 2 writes of 2 bytes per element.  No LDS, no atomics.
+namespace svdq {
+
+template <int DT, int NV>
+__global__ __launch_bounds__(256) void t5_residual_norm_kernel(const uint16_t *res, const uint16_t *a, const uint16_t *__restrict__ w, uint16_t *out,
+                                                                uint16_t *out_norm, float *__restrict__ stats, int ld_res, int ld_a, int ld_out,
+                                                                int ld_norm, int M, int C, float eps) {
+    using T16 = typename Half<DT>::T;
+    const int lane = threadIdx.x & 63;
+    const int row = wave_row();
+    if (row >= M) return; // (wave-uniform)
+    const size_t o_res = (size_t)row * ld_res, o_a = (size_t)row * ld_a, o_out = (size_t)row * ld_out, o_norm = (size_t)row * ld_norm;
+    const u16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    u16x8 yv[NV];
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+        const int c = (v * 64 + lane) * 8; // piece v of this lane (row_pass.h)
+        yv[v] = c < C ? ld8(res + o_res + c) : zero;
+        if (c >= C) continue;
+        if (a) {
+            const u16x8 av = ld8(a + o_a + c);
+#pragma unroll
+            for (int e = 0; e < 8; e++) yv[v][e] = hbits(f2h<T16>(op32<T16>(h2f(hfrom<T16>(yv[v][e])) + h2f(hfrom<T16>(av[e])))));
+        }
+        if (out) st8(out + o_out + c, yv[v]);
+    }
+    if (!stats && !out_norm) return;
+    const float rstd = row_rstd<T16, NV>(yv, C, eps);
+    if (stats && lane == 0) stats[row] = rstd;
+    if (!out_norm) return;
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+        const int c = (v * 64 + lane) * 8;
+        if (c >= C) continue;
+        const u16x8 wv = ld8(w + c);
+        u16x8 nv;
+#pragma unroll
+        for (int e = 0; e < 8; e++) nv[e] = hbits(f2h<T16>(mul16<T16>(h2f(hfrom<T16>(wv[e])), mul16<T16>(h2f(hfrom<T16>(yv[v][e])), rstd))));
+        st8(out_norm + o_norm + c, nv);
+    }
+}
+
+} // namespace svdq
+
+extern "C" int svdq_t5_residual_norm(const svdq_t5_residual_norm_args *a, void *stream) {
+    const char *op = "svdq_t5_residual_norm";
+    if (!a) { set_error("%s: args is NULL", op); return SVDQ_E_INVALID; }
+    if (!a->res || (!a->out && !a->out_norm && !a->stats)) { set_error("%s: res and one of out / out_norm / stats are required", op); return SVDQ_E_INVALID; }
+    if (a->out_norm && !a->weight) { set_error("%s: out_norm needs weight", op); return SVDQ_E_INVALID; }
+    if (int rc = check_row_args(op, a->M, a->C, a->ld_res, a->dtype, {a->res, a->a, a->weight, a->out, a->out_norm}, {})) return rc;
+    if (a->a) if (int rc = check_row_args(op, a->M, a->C, a->ld_a, a->dtype, {}, {})) return rc;
+    if (a->out) if (int rc = check_row_args(op, a->M, a->C, a->ld_out, a->dtype, {}, {})) return rc;
+    if (a->out_norm) if (int rc = check_row_args(op, a->M, a->C, a->ld_norm, a->dtype, {}, {})) return rc;
+    if ((uintptr_t)a->stats & 3) { set_error("%s: stats must be 4-byte aligned", op); return SVDQ_E_INVALID; }
+    if (!(a->eps >= 0.f) || !std::isfinite(a->eps)) { set_error("%s: eps must be finite and not negative", op); return SVDQ_E_INVALID; }
+    const dim3 grid((a->M + 3) / 4), block(256);
+    const bool known = for_row_class(a->dtype, a->C, [&](auto dt, auto nv) {
+        hipLaunchKernelGGL((t5_residual_norm_kernel<decltype(dt)::value, decltype(nv)::value>), grid, block, 0, (hipStream_t)stream,
+                           (const uint16_t *)a->res, (const uint16_t *)a->a, (const uint16_t *)a->weight, (uint16_t *)a->out, (uint16_t *)a->out_norm,
+                           a->stats, a->ld_res, a->ld_a, a->ld_out, a->ld_norm, a->M, a->C, a->eps);
+    });
+    if (!known) return row_class_unsupported(op, a->C);
+    return hip_check(hipGetLastError(), "svdq_t5_residual_norm launch");
+}

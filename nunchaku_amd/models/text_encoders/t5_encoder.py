@@ -11,10 +11,11 @@ import os
 import torch
 from torch import nn
 from transformers import T5Config, T5EncoderModel
+from transformers.models.t5.modeling_t5 import T5Block, T5LayerNorm
 
 from .linear import W4Linear
 
-__all__ = ["NunchakuT5EncoderModel", "ATTENTION_NAME", "fused_t5_attention", "toeplitz_rel_bias"]
+__all__ = ["NunchakuT5EncoderModel", "ATTENTION_NAME", "fused_t5_attention", "toeplitz_rel_bias", "FusedT5Block", "FusedT5LayerNorm"]
 
 ATTENTION_NAME = "nunchaku_amd_t5_d64"  # the name ``config._attn_implementation`` carries when the fused attention is selected
 
@@ -129,6 +130,132 @@ def register_fused_attention() -> bool:
     return True
 
 
+class FusedT5LayerNorm(T5LayerNorm):
+    """``T5LayerNorm`` as one ``ops.t5_residual_norm`` launch (the stack's ``final_layer_norm`` under ``set_fused_layers``); same parameter,
+    same rounding points.  What the kernel does not serve goes to the parent's forward."""
+
+    def forward(self, hidden_states):
+        w = self.weight
+        if not (hidden_states.is_cuda and hidden_states.dtype in (torch.bfloat16, torch.float16) and w.dtype == hidden_states.dtype
+                and hidden_states.shape[-1] % 8 == 0 and hidden_states.is_contiguous() and not (torch.is_grad_enabled() and (hidden_states.requires_grad or w.requires_grad))):
+            return super().forward(hidden_states)
+        from ...ops.elementwise import t5_residual_norm
+
+        return t5_residual_norm(hidden_states, None, w.data, self.variance_epsilon)[1]
+
+
+class FusedT5Block(T5Block):
+    """A ``T5Block`` of the 4-bit encoder on the fused kernels (``set_fused_layers``): the class of an existing block is swapped, its children
+    -- and with them the ``state_dict()`` keys -- stay.  One layer is
+
+        norm (first layer only) -> q / k / v as ONE ``gemm_awq_multi`` launch into ``[B, T, 3 * inner]`` -> ``attention_d64_bias`` on its column
+        thirds in place -> o -> ``y = hidden + o`` and the feed-forward norm in one ``t5_residual_norm`` pass -> ``gelu_new(wi_0) * wi_1`` as ONE
+        gated ``gemm_awq_multi`` launch -> wo -> the closing add, with the NEXT layer's norm in the same pass (handed over through
+        ``_next`` / ``_handed``; the last layer hands nothing, the stack's final norm is a :class:`FusedT5LayerNorm`).
+
+    In float16 ``T5Block``'s inf-clamp sits between an add and the norm behind it: it stays the torch operations it is, and add and norm run as
+    two passes.  Whatever :meth:`_serves` does not admit -- a CPU tensor, training, gradients, a decoder, ``d_kv != 64``, a feed-forward that
+    is not gated-GELU on group-128 ``W4Linear`` children, a mask or position bias the attention kernel does not take -- goes to the parent's
+    forward, per call."""
+
+    _next = None    # the following block when it is fused too (a plain attribute set by set_fused_layers, not a registered child)
+    _handed = None  # (hidden_states, its norm for this block) from the previous block's closing pass
+
+    def _serves(self, hidden_states, attention_mask, position_bias, encoder_hidden_states, past_key_values) -> bool:
+        from transformers.activations import NewGELUActivation
+        from transformers.models.t5.modeling_t5 import T5DenseGatedActDense
+
+        att, dense = self.layer[0].SelfAttention, self.layer[-1].DenseReluDense
+        if not (hidden_states.is_cuda and hidden_states.dim() == 3 and hidden_states.dtype in (torch.bfloat16, torch.float16)
+                and not self.is_decoder and not self.training and encoder_hidden_states is None and past_key_values is None
+                and not (torch.is_grad_enabled() and hidden_states.requires_grad)
+                and att.key_value_proj_dim == 64 and hidden_states.shape[-1] % 8 == 0
+                and isinstance(dense, T5DenseGatedActDense) and isinstance(dense.act, NewGELUActivation)):
+            return False
+        linears = (att.q, att.k, att.v, att.o, dense.wi_0, dense.wi_1, dense.wo)
+        if not all(isinstance(m, W4Linear) and m.group_size == 128 and m.scales.dtype == hidden_states.dtype for m in linears):
+            return False
+        B, T, _ = hidden_states.shape
+        if position_bias is not None and not (isinstance(position_bias, torch.Tensor) and tuple(position_bias.shape) == (1, att.n_heads, T, T)):
+            return False
+        return _key_bias(attention_mask, B, T)[0]
+
+    def forward(self, hidden_states, attention_mask=None, position_bias=None, encoder_hidden_states=None, encoder_attention_mask=None,
+                encoder_decoder_position_bias=None, past_key_values=None, **kwargs):
+        handed, self._handed = self._handed, None
+        if not self._serves(hidden_states, attention_mask, position_bias, encoder_hidden_states, past_key_values):
+            return super().forward(hidden_states, attention_mask, position_bias, encoder_hidden_states, encoder_attention_mask,
+                                   encoder_decoder_position_bias, past_key_values=past_key_values, **kwargs)
+        from ...ops.attention import attention_d64_bias
+        from ...ops.elementwise import t5_residual_norm
+        from ...ops.gemm import gemm_awq_multi
+
+        sa, ff = self.layer[0], self.layer[-1]
+        att, dense = sa.SelfAttention, ff.DenseReluDense
+        B, T, _ = hidden_states.shape
+        H, inner = att.n_heads, att.n_heads * 64
+        fp16 = hidden_states.dtype == torch.float16
+        if handed is not None and handed[0] is hidden_states:
+            normed = handed[1]
+        else:
+            normed = t5_residual_norm(hidden_states, None, sa.layer_norm.weight.data, sa.layer_norm.variance_epsilon)[1]
+        qkv = gemm_awq_multi(normed, (att.q, att.k, att.v), "concat")
+        if position_bias is None:  # (T5Attention.forward: the first layer computes it, the stack shares it)
+            if att.has_relative_attention_bias:
+                position_bias = att.compute_bias(T, T, device=hidden_states.device, past_seen_tokens=0)
+            else:
+                position_bias = torch.zeros((1, H, T, T), device=hidden_states.device, dtype=hidden_states.dtype)
+        ctx = attention_d64_bias(qkv[..., :inner], qkv[..., inner:2 * inner], qkv[..., 2 * inner:], H, toeplitz_rel_bias(position_bias),
+                                 _key_bias(attention_mask, B, T)[1], scale=1.0 if att.scaling is None else att.scaling)
+        o = att.o(ctx)
+        w_ff, eps_ff = ff.layer_norm.weight.data, ff.layer_norm.variance_epsilon
+        if fp16:
+            y = self._clamp(t5_residual_norm(hidden_states, o)[0])
+            n2 = t5_residual_norm(y, None, w_ff, eps_ff)[1]
+        else:
+            y, n2, _ = t5_residual_norm(hidden_states, o, w_ff, eps_ff)
+        f = dense.wo(gemm_awq_multi(n2, (dense.wi_0, dense.wi_1), "gated_gelu_new"))
+        nxt = self._next
+        if fp16 or nxt is None:
+            out = t5_residual_norm(y, f)[0]
+            if fp16:
+                out = self._clamp(out)
+        else:
+            norm = nxt.layer[0].layer_norm
+            out, n_next, _ = t5_residual_norm(y, f, norm.weight.data, norm.variance_epsilon)
+            nxt._handed = (out, n_next)
+        return out, position_bias, None
+
+    @staticmethod
+    def _clamp(hidden_states):
+        """T5Block.forward's "clamp inf values" step, the same torch operations"""
+        clamp_value = torch.where(torch.isinf(hidden_states).any(), torch.finfo(hidden_states.dtype).max - 1000, torch.finfo(hidden_states.dtype).max)
+        return torch.clamp(hidden_states, min=-clamp_value, max=clamp_value)
+
+
+def set_fused_layers(model, enabled: bool = True):
+    """Swap the classes of ``model.encoder``'s blocks and final norm between transformers' and the fused ones (:class:`FusedT5Block`,
+    :class:`FusedT5LayerNorm`).  Modules, parameters, buffers and ``state_dict()`` keys are untouched; off restores the parent's path exactly."""
+    blocks = list(model.encoder.block)
+    for i, blk in enumerate(blocks):
+        if enabled and type(blk) is T5Block:
+            blk.__class__ = FusedT5Block
+        elif not enabled and type(blk) is FusedT5Block:
+            blk.__class__ = T5Block
+        blk.__dict__.pop("_next", None)
+        blk.__dict__.pop("_handed", None)
+    if enabled:
+        for blk, nxt in zip(blocks, blocks[1:]):
+            if type(blk) is FusedT5Block and type(nxt) is FusedT5Block:
+                object.__setattr__(blk, "_next", nxt)
+    norm = model.encoder.final_layer_norm
+    if enabled and type(norm) is T5LayerNorm:
+        norm.__class__ = FusedT5LayerNorm
+    elif not enabled and type(norm) is FusedT5LayerNorm:
+        norm.__class__ = T5LayerNorm
+    return model
+
+
 class NunchakuT5EncoderModel(T5EncoderModel):
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path: str | os.PathLike, **kwargs) -> T5EncoderModel:
@@ -137,7 +264,9 @@ class NunchakuT5EncoderModel(T5EncoderModel):
         ``"cuda"``) where the model is materialised.  The model is built on the meta device, its quantised linears swapped
         for W4Linear (group 128), then materialised and loaded with ``strict=True``.  ``fused_attention`` (default True) selects
         :func:`fused_t5_attention` on the model's config when the device is a GPU, ``d_kv == 64`` and the model is an encoder; False keeps
-        transformers' eager attention."""
+        transformers' eager attention.  ``fused_layers`` (default False) puts the encoder's layers on the fused kernels
+        (:func:`set_fused_layers`: q / k / v and the gated-GELU feed-forward as one ``gemm_awq_multi`` launch each, residual adds and norms as
+        ``t5_residual_norm`` passes); the returned model has ``set_fused_layers(bool)`` to switch at any time."""
         path = os.fspath(pretrained_model_name_or_path)
         if not os.path.isfile(path):
             raise FileNotFoundError(f"NunchakuT5EncoderModel.from_pretrained: {path!r} is not a local .safetensors file "
@@ -165,4 +294,11 @@ class NunchakuT5EncoderModel(T5EncoderModel):
         if (kwargs.get("fused_attention", True) and device.type == "cuda" and config.d_kv == 64 and not config.is_decoder
                 and register_fused_attention()):
             model.config._attn_implementation = ATTENTION_NAME
+        model.__class__ = cls  # (T5EncoderModel plus set_fused_layers: no other attribute or method differs)
+        if kwargs.get("fused_layers", False):
+            set_fused_layers(model, True)
         return model
+
+    def set_fused_layers(self, enabled: bool = True):
+        """see :func:`set_fused_layers`"""
+        return set_fused_layers(self, enabled)

@@ -348,3 +348,45 @@ def sandwich_norm(res: torch.Tensor, a: torch.Tensor | None = None, *, w_post: t
     ops.sandwich_norm(res, a, w_post if a is not None else None, gate, w_pre if out_mod is not None else None, scale, out, out_mod, stats, T, C,
                       lds=lds, eps=eps)
     return out, out_mod, stats
+
+
+def t5_residual_norm(res: torch.Tensor, a: torch.Tensor | None = None, weight: torch.Tensor | None = None, eps: float = 1e-6, *,
+                     out: torch.Tensor | bool | None = None, out_norm: torch.Tensor | bool | None = None, want_stats: bool = False):
+    """The T5 encoder's residual add and ``T5LayerNorm`` as one row pass (``svdq_t5_residual_norm``), one 16-bit rounding per torch operation
+    of ``T5LayerNorm.forward``::
+
+        y = res  |  res + a                                        (no a | a)        -> out
+        out_norm = weight * (y * rstd(y)),  rstd(y) = rsqrt(mean(y^2) + eps)         -> out_norm, stats
+
+    ``res`` / ``a``: ``[..., C]`` 16-bit with unit stride on the last axis and uniformly strided rows; ``weight``: ``[C]``.  ``out`` /
+    ``out_norm``: a tensor to write into, True to allocate one, None / False for none; ``out`` defaults to "when ``a`` is given", ``out_norm``
+    to "when ``weight`` is given".  Returns ``(out, out_norm, stats)`` with None for what was not asked for; ``stats``: float32 ``rstd`` per row."""
+    op = "t5_residual_norm"
+    if not isinstance(res, torch.Tensor) or res.dim() < 1 or res.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"{op}: res must be a bfloat16 or float16 tensor")
+    C = res.shape[-1]
+    if out is None:
+        out = a is not None
+    if out_norm is None:
+        out_norm = weight is not None
+    out = torch.empty(res.shape, dtype=res.dtype, device=res.device) if out is True else None if out is False else out
+    out_norm = torch.empty(res.shape, dtype=res.dtype, device=res.device) if out_norm is True else None if out_norm is False else out_norm
+    if out is None and out_norm is None and not want_stats:
+        raise ValueError(f"{op}: nothing to do: none of out, out_norm and stats is asked for")
+    if out_norm is not None and weight is None:
+        raise ValueError(f"{op}: out_norm needs weight")
+
+    def rows(name, t):
+        """the [M, C] row view of a [..., C] tensor whose rows are uniformly strided (None for None)"""
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor) or t.dtype != res.dtype or t.shape != res.shape or t.device != res.device:
+            raise ValueError(f"{op}: {name} must be a {res.dtype} tensor of res's shape {tuple(res.shape)} on its device")
+        if t.stride(-1) != 1 or any(t.shape[i] > 1 and t.shape[i + 1] > 1 and t.stride(i) != t.stride(i + 1) * t.shape[i + 1] for i in range(t.dim() - 2)):
+            raise ValueError(f"{op}: {name} must have unit stride on its last axis and uniformly strided rows")
+        strides = [t.stride(i) for i in range(t.dim() - 1) if t.shape[i] > 1]
+        return t.as_strided((t.numel() // C, C), (strides[-1] if strides else C, 1))
+
+    stats = torch.empty(res.numel() // C, dtype=torch.float32, device=res.device) if want_stats else None
+    ops.t5_residual_norm(rows("res", res), rows("a", a), weight if out_norm is not None else None, rows("out", out), rows("out_norm", out_norm), stats, eps)
+    return out, out_norm, stats

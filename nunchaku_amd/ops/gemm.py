@@ -39,3 +39,31 @@ def svdq_gemm_w4a4_cuda(
         fuse_silu, fp4, 1.0 if alpha is None else alpha, wcscales, out_q, out_k, out_v, attn_tokens,
         out_vt, lora_act_zeroed, second, split_rows, q_scale,
     )
+
+
+AWQ_MULTI_MODES = {"concat": False, "gated_gelu_new": True}
+
+
+def gemm_awq_multi(x: T, weights, mode: str = "concat", out: T | None = None) -> T:
+    """One 16-bit ``x [..., K]`` against 1 to 3 AWQ W4A16 weight sets (group 128) in ONE launch (``svdq_gemm_awq_multi``).  ``weights``: a
+    sequence of ``W4Linear`` modules or ``(qweight, scales, scaled_zeros, bias or None)`` tuples.
+
+    * ``mode="concat"``: ``[..., sum N_i]``, set i in columns ``[sum_{j<i} N_j, ...)``, every element what ``ops.gemm_awq`` writes for its
+      set (bit for bit where neither launch splits K) -- the T5 encoder's q / k / v as one buffer whose column thirds the attention reads.
+    * ``mode="gated_gelu_new"`` (two sets of equal N): ``[..., N] = round16(round16(gelu_new(y_0)) * y_1)`` with ``y_i`` the two 16-bit GEMM
+      results -- T5's gated-GELU feed-forward; the ``[..., 2N]`` intermediate is never written.
+
+    ``out``: None, or a tensor of the result's shape to write into (unit column stride, uniformly strided rows: a column slice will do)."""
+    if mode not in AWQ_MULTI_MODES:
+        raise ValueError(f"gemm_awq_multi: mode={mode!r} (one of {sorted(AWQ_MULTI_MODES)})")
+    sets = []
+    for w in weights:
+        if isinstance(w, (tuple, list)):
+            if len(w) != 4:
+                raise ValueError("gemm_awq_multi: a weight set is (qweight, scales, scaled_zeros, bias or None)")
+            sets.append(tuple(w))
+        else:
+            if getattr(w, "group_size", None) != 128:
+                raise NotImplementedError(f"gemm_awq_multi: group_size={getattr(w, 'group_size', None)} (the AWQ GEMM kernels implement 128)")
+            sets.append((w.qweight, w.scales, w.scaled_zeros, w.bias))
+    return ops.gemm_awq_multi(x, sets, AWQ_MULTI_MODES[mode], out)
