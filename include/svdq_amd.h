@@ -1407,6 +1407,60 @@ int svdq_gemm_awq_multi(const svdq_gemm_awq_multi_args *args, void *stream);
 int64_t svdq_gemm_awq_multi_workspace_bytes(int32_t M, int32_t N_total, int32_t K, int32_t mode);
 
 /* ------------------------------------------------------------------------------------------
+ * MXFP4 W4A4 (added WITHOUT a version bump: two new symbols and two new args structs, nothing existing changes, so SVDQ_ABI_VERSION
+ * stays 24).  OCP MXFP4 on both operands: e2m1 codes (4 bits s e e m: +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}), two a byte with the even channel in
+ * the low nibble, rows natural [rows][K / 2]; one E8M0 scale byte 2^(e - 127) per 32 consecutive K channels, never 255.  The scale operand of
+ * both kernels packs the four blocks of a 128-channel K-step into one dword: uint32 [K / 128][rows], byte b of dword (kp, row) = block 4 kp + b.
+ *
+ * svdq_quantize_mxfp4:  v = round16(x * rcp(smooth)) (the INT4 quantiser's smoothing division); per (row, block): amax = max |v| over the
+ *   finite elements with +-inf counted as the dtype's largest finite value and NaN ignored; byte = clamp(floor(log2 amax) - 2 + 127, 0, 254),
+ *   0 for amax = 0; code = RNE_e2m1(v * 2^-(byte - 127)), ties to the even mantissa, saturated to +-6, NaN -> 0, a zero result is code 0 (no -0).
+ *   lora_act = x @ lora_down on the un-smoothed x, fp32, natural [M_pad][R].  Rows M .. M_pad - 1 of act, ascales and lora_act are written as zeros.
+ *   K > 512 is sliced over workgroups whose low-rank partial sums meet in fp32 atomics (lora_act is cleared first by a small kernel unless
+ *   lora_act_zeroed); codes and scales never depend on the launch.
+ * svdq_gemm_mxfp4:  out[m, n] = round16( sum_blocks 2^(sa - 127) 2^(sw - 127) sum_{k in block} a[m, k] w[n, k]
+ *                                        + sum_r round16(lora_act_in[m, r] * lora_scales[r / 16]) * lora_up[n, r] + bias[n] ),
+ *   fp32 accumulation in ascending K inside one workgroup (no split-K, no atomics: two launches are bit-equal), the multiply by a
+ *   lora_scale of exactly 1 skipped as in svdq_gemm_w4a4.  ceil(M / 256) * N / 128 workgroups.
+ * Validation (no launch), SVDQ_E_INVALID: NULL args or a required pointer, unknown dtype, M < 1, M_pad < M or not a multiple of 256, K or N not a
+ * positive multiple of 128, ldx < K or ldx % 8, ldo < N or ldo % 4, R not a multiple of 16 in [0, 256], R > 0 without the low-rank operands,
+ * a misaligned pointer.  Alignment: x, act, wgt, lora_down, lora_up, lora_act_in 16 bytes; out, bias 8 bytes; smooth, ascales, wscales, lora_act 4 bytes.
+ * Addressing reach (SVDQ_E_UNSUPPORTED beyond): M_pad * K / 2 and N * K / 2 <= 2147483647 (the GEMM's tile loads are 32-bit byte offsets into
+ * buffer descriptors); R * K * 2 <= 2147483647 and (R + 32) * K * 2 <= 4294967295 (the quantiser's lora_down slabs); grids must fit 2147483647.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct svdq_quantize_mxfp4_args {
+    const void *x;         /* [M, K] 16-bit, row stride ldx elements                          */
+    const void *smooth;    /* [K] 16-bit, natural order; NULL = ones                          */
+    const void *lora_down; /* [R][K] 16-bit, rank-major; NULL if R == 0                       */
+    void *act;             /* out: [M_pad][K/2] bytes                                         */
+    void *ascales;         /* out: uint32 [K/128][M_pad]                                      */
+    void *lora_act;        /* out: [M_pad][R] fp32 (SVDQ_LORA_ACT_F32)                        */
+    int32_t M, M_pad, K, R;
+    int32_t ldx;           /* >= K, a multiple of 8                                           */
+    int32_t dtype;         /* SVDQ_BF16 | SVDQ_FP16                                           */
+    int32_t lora_act_zeroed; /* non-zero: lora_act is already zero on this stream             */
+    int32_t reserved;
+} svdq_quantize_mxfp4_args;
+int svdq_quantize_mxfp4(const svdq_quantize_mxfp4_args *args, void *stream);
+
+typedef struct svdq_gemm_mxfp4_args {
+    const void *act;          /* [M_pad][K/2] bytes (svdq_quantize_mxfp4)                     */
+    const void *wgt;          /* [N][K/2] bytes                                               */
+    const void *ascales;      /* uint32 [K/128][M_pad]                                        */
+    const void *wscales;      /* uint32 [K/128][N]                                            */
+    const void *bias;         /* [N] 16-bit or NULL                                           */
+    const void *lora_act_in;  /* [M_pad][R] fp32 or NULL                                      */
+    const void *lora_up;      /* [N][R] 16-bit or NULL                                        */
+    const float *lora_scales; /* HOST pointer, R/16 floats, or NULL (= all 1.0)               */
+    void *out;                /* [M, N] 16-bit, row stride ldo elements                       */
+    int32_t M, M_pad, N, K, R;
+    int32_t ldo;              /* >= N, a multiple of 4                                        */
+    int32_t dtype;            /* SVDQ_BF16 | SVDQ_FP16                                        */
+    int32_t reserved;
+} svdq_gemm_mxfp4_args;
+int svdq_gemm_mxfp4(const svdq_gemm_mxfp4_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Load-time re-layout of reference checkpoint tensors (NVIDIA fragment order -> CDNA4 order).
  * src and dst must not alias.  All but svdq_repack_qweight (4 -> 6 bits per code) and svdq_repack_wscales (x 32) are pure permutations of equal size.
  * ------------------------------------------------------------------------------------------ */

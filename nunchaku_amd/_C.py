@@ -610,6 +610,90 @@ class _Ops:
         del taps
 
     @staticmethod
+    def quantize_mxfp4(x, output, oscales, lora_down, lora_act_out, smooth, lora_act_zeroed=False):
+        """MXFP4 activation quantiser (``svdq_quantize_mxfp4``): ``x [M, K]`` 16-bit -> ``output`` uint8 ``[M_pad, K/2]`` e2m1 codes in natural rows,
+        ``oscales`` uint8 ``[K/128, M_pad, 4]`` E8M0 bytes (four blocks a dword), ``lora_act_out`` fp32 ``[M_pad, R]``.  ``smooth`` ``[K]`` in natural
+        order; ``lora_down`` the logical ``[K, R]`` factor (transposed once per parameter), or a tensor marked as kernel layout: rank-major
+        ``[R][K]`` behind the ``[K, R]`` shape."""
+        op, lib = "quantize_mxfp4", _lib.load()
+        if x is None or output is None or oscales is None:
+            raise ValueError(f"{op}: x, output and oscales are required")
+        if x.dim() != 2 or x.stride(1) != 1 or x.dtype not in _DT:
+            raise ValueError(f"{op}: x must be a 2-D 16-bit view with unit column stride")
+        M, K = x.shape
+        if K % 128:
+            raise ValueError(f"{op}: K={K} must be a multiple of 128")
+        M_pad = output.numel() // max(output.shape[-1], 1)
+        if output.dtype != torch.uint8 or output.shape[-1] * 2 != K:
+            raise ValueError(f"{op}: output must be uint8 [M_pad, K/2]")
+        if oscales.dtype != torch.uint8 or oscales.numel() != (K // 32) * M_pad:
+            raise ValueError(f"{op}: oscales must hold (K/32)*M_pad bytes")
+        R = 0 if lora_down is None else lora_down.shape[-1]
+        if R and (lora_down.dtype != x.dtype or lora_down.numel() != K * R):
+            raise ValueError(f"{op}: lora_down must be [K, R] in the dtype of x")
+        if R and (lora_act_out is None or lora_act_out.numel() != M_pad * R or lora_act_out.dtype != torch.float32):
+            raise ValueError(f"{op}: lora_act_out must hold M_pad*R float32")
+        if smooth is not None and (smooth.numel() != K or smooth.dtype != x.dtype):
+            raise ValueError(f"{op}: smooth must be [K] in the dtype of x")
+        if R and not getattr(lora_down, "_svdq_amd", False):
+            lora_down = _cached_conversion(lora_down, "mxfp4_down", lambda src: src.t().contiguous())
+        a = _lib.ARGS["svdq_quantize_mxfp4_args"]()
+        a.x, a.smooth, a.lora_down = _ptr(x, laid_out=True), _ptr(smooth), _ptr(lora_down) if R else None
+        a.act, a.ascales, a.lora_act = _ptr(output), _ptr(oscales), _ptr(lora_act_out) if R else None
+        a.M, a.M_pad, a.K, a.R = _i32(op, "M", M), _i32(op, "M_pad", M_pad), _i32(op, "K", K), _i32(op, "R", R)
+        a.ldx = _i32(op, "x.stride(0)", x.stride(0))
+        a.dtype, a.lora_act_zeroed = _DT[x.dtype], int(bool(lora_act_zeroed))
+        _lib.check(lib.svdq_quantize_mxfp4(C.byref(a), _stream()), op)
+
+    @staticmethod
+    def gemm_mxfp4(act, wgt, out, ascales, wscales, lora_act_in=None, lora_up=None, bias=None, lora_scales=None, rows=None):
+        """MXFP4 W4A4 GEMM with the plain epilogue (``svdq_gemm_mxfp4``): ``act`` uint8 ``[M_pad, K/2]`` and ``ascales`` ``[K/128, M_pad, 4]`` as
+        :meth:`quantize_mxfp4` writes them; ``wgt`` uint8 / int8 ``[N, K/2]``; ``wscales`` uint8 ``[K/32, N]`` (checkpoint layout, packed once per
+        parameter) or marked as kernel layout (``[K/128, N, 4]`` behind the same shape); ``out`` 16-bit ``[M, N]`` with any row stride that is a
+        multiple of 4; ``rows``: M (default: ``out``'s rows).  ``lora_up`` / ``bias`` in natural order."""
+        op, lib = "gemm_mxfp4", _lib.load()
+        if act is None or wgt is None or out is None or ascales is None or wscales is None:
+            raise ValueError(f"{op}: act, wgt, out, ascales and wscales are required")
+        if out.dim() != 2 or out.stride(1) != 1 or out.dtype not in _DT:
+            raise ValueError(f"{op}: out must be a 2-D 16-bit view with unit column stride")
+        if act.dim() != 2 or wgt.dim() != 2 or act.dtype != torch.uint8 or wgt.dtype not in (torch.uint8, torch.int8) or act.shape[1] != wgt.shape[1]:
+            raise ValueError(f"{op}: act must be uint8 [M_pad, K/2] and wgt uint8 / int8 [N, K/2]")
+        M_pad, K, N = act.shape[0], act.shape[1] * 2, wgt.shape[0]
+        M = out.shape[0] if rows is None else int(rows)
+        if K % 128 or N % 128:
+            raise ValueError(f"{op}: K={K} and N={N} must be multiples of 128")
+        if out.shape[0] < M or out.shape[1] != N:
+            raise ValueError(f"{op}: out must be [>= M, N]")
+        if ascales.dtype != torch.uint8 or ascales.numel() != (K // 32) * M_pad:
+            raise ValueError(f"{op}: ascales must hold (K/32)*M_pad bytes")
+        if wscales.dtype != torch.uint8 or wscales.numel() != (K // 32) * N:
+            raise ValueError(f"{op}: wscales must hold (K/32)*N bytes")
+        R = 0 if lora_up is None else lora_up.shape[-1]
+        if R and (lora_act_in is None or lora_act_in.dtype != torch.float32 or lora_act_in.numel() != M_pad * R or lora_up.dtype != out.dtype
+                  or lora_up.shape[0] != N):
+            raise ValueError(f"{op}: the low-rank branch needs lora_act_in float32 [M_pad, R] and lora_up [N, R] in the dtype of out")
+        if bias is not None and (bias.numel() != N or bias.dtype != out.dtype):
+            raise ValueError(f"{op}: bias must be [N] in the dtype of out")
+        if lora_scales is not None and len(lora_scales) < R // 16:
+            raise ValueError(f"{op}: lora_scales must hold one scale per 16 ranks")
+        if not getattr(wscales, "_svdq_amd", False):
+            wscales = _cached_conversion(wscales, "mxfp4_wscales", lambda src: src.reshape(K // 128, 4, N).permute(0, 2, 1).contiguous())
+        a = _lib.ARGS["svdq_gemm_mxfp4_args"]()
+        a.act, a.wgt, a.ascales, a.wscales, a.bias = _ptr(act), _ptr(wgt), _ptr(ascales), _ptr(wscales), _ptr(bias)
+        a.out = _ptr(out, laid_out=True)
+        if R:
+            a.lora_act_in, a.lora_up = _ptr(lora_act_in), _ptr(lora_up)
+        scales = None
+        if R and lora_scales is not None:
+            scales = (C.c_float * (R // 16))(*[float(v) for v in lora_scales[:R // 16]])
+            a.lora_scales = scales
+        a.M, a.M_pad, a.N, a.K, a.R = _i32(op, "M", M), _i32(op, "M_pad", M_pad), _i32(op, "N", N), _i32(op, "K", K), _i32(op, "R", R)
+        a.ldo = _i32(op, "out.stride(0)", out.stride(0))
+        a.dtype = _DT[out.dtype]
+        _lib.check(lib.svdq_gemm_mxfp4(C.byref(a), _stream()), op)
+        del scales
+
+    @staticmethod
     def gemm_w4a4(
         act, wgt, out, qout, ascales, wscales, oscales, poolout, lora_act_in, lora_up, lora_down, lora_act_out,
         norm_q, norm_k, rotary_emb, bias, smooth_factor, out_vk, out_linearattn, act_unsigned, lora_scales,

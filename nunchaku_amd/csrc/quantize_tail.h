@@ -7,7 +7,8 @@
 // quantize_tail.inc is a fragment of a kernel body, included three times with QUANT_TAIL_PART set (a function the steps were moved into changed
 // quantize_glu_kernel's register allocation: 100 bytes of scratch at the same 168 VGPRs; the included text compiles to the instructions it had):
 //   1  declarations, ahead of the kernel's own loads: the record xv, the slab offsets, lora_down's descriptor, slab_dma
-//   2  steps 3 and 4, inside `if (active)`, behind the tile's last write
+//   2  steps 3 and 4, inside `if (active)`, behind the tile's last write (with QUANT_TAIL_READBACK_ONLY defined: step 3 alone, for a kernel whose
+//      quantiser is its own text -- quantize_mxfp4.hip)
 //   3  step 5, outside it: it holds the workgroup's barriers
 // It expects in scope: DT, SMOOTH, T, V8, `lds` (the workgroup's 4 * QG_WAVE_BYTES), W (the wave's region), wave, lane, r = lane & 31, h = lane >> 5,
 // K, KP, rt (the 32-row tile), kp (the chunk), active, and `p` with lora_down, act, ascales, lora_act, R and mode (lora_act_add's).

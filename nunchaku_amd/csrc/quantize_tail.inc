@@ -32,6 +32,7 @@
             slab_dma(0);
         }
 
+#ifndef QUANT_TAIL_READBACK_ONLY // (a kernel with a block quantiser of its own takes step 3 alone)
         // ---- 4. the two groups of the chunk: the quantiser of quantize.hip, expression for expression
         uint8_t *dst = p.act + ((size_t)rt * KP + kp) * F6_CHUNK + (size_t)lane * 16;
 #pragma unroll
@@ -71,6 +72,7 @@
             // S image: [rt][kp][grp][32]; lane (r, h) writes group h
             if (h == grp) ((T *)p.ascales)[(((size_t)rt * KP + kp) * 2 + grp) * 32 + r] = f2h<T>(scale);
         }
+#endif
 
 #elif QUANT_TAIL_PART == 3
     // ---- 5. low rank, one 32-rank slab at a time: 8 MFMAs per wave (pieces 2q, 2q + 1 of every lane are k-slots 8h .. 8h + 7), the four waves' tiles

@@ -23,8 +23,9 @@ import torch
 from torch import nn
 
 from .. import layout
-from ..ops.gemm import svdq_gemm_w4a4_cuda
-from ..ops.quantize import svdq_quantize_dwconv_glu, svdq_quantize_glu_halves, svdq_quantize_w4a4_act_fuse_lora_cuda
+from ..ops.gemm import svdq_gemm_mxfp4, svdq_gemm_w4a4_cuda
+from ..ops.quantize import svdq_quantize_dwconv_glu, svdq_quantize_glu_halves, svdq_quantize_mxfp4, svdq_quantize_w4a4_act_fuse_lora_cuda
+from ..quantization.mxfp4 import quantize_weight_mxfp4
 
 
 def synthetic_codes_(qweight: torch.Tensor, wscales: torch.Tensor, in_features: int, generator: torch.Generator, codes: str = "uniform"):
@@ -48,12 +49,22 @@ def synthetic_codes_(qweight: torch.Tensor, wscales: torch.Tensor, in_features: 
     wscales.copy_((torch.rand(wscales.shape, generator=generator, device=dev) * 0.5 + 0.75) * (1.0 / (std * math.sqrt(in_features))))
 
 
+def _mxfp4_layout(name: str, t: torch.Tensor, inverse: bool) -> torch.Tensor:
+    """The two MXFP4 parameters whose kernel layout differs from the checkpoint's, converted (``inverse``: back) behind the parameter's own shape:
+    ``wscales`` [in/32, out] <-> the four blocks of a K-step in one dword, [in/128][out][4]; ``proj_down`` [in, rank] <-> rank-major [rank][in]."""
+    a, b = t.shape
+    if name == "wscales":
+        return (t.reshape(a // 4, b, 4) if inverse else t.reshape(a // 4, 4, b)).permute(0, 2, 1).reshape(a, b)
+    return t.reshape(b, a).t().contiguous() if inverse else t.t().contiguous().view(a, b)
+
+
 class SVDQW4A4Linear(nn.Module):
-    """y = W4A4(x) + (x @ proj_down) @ proj_up^T + bias, SVDQuant INT4 (group size 64).
+    """y = W4A4(x) + (x @ proj_down) @ proj_up^T + bias, SVDQuant INT4 (group size 64) or, with ``precision="mxfp4"``, OCP MXFP4 (e2m1 codes,
+    one E8M0 scale per 32 channels on both operands: ``wscales`` uint8 [in/32, out], every 16-bit parameter in natural order).
 
     Parameters: ``qweight`` int8 [out, in/2]; ``wscales`` [in/64, out]; ``bias`` [out] or None;
     ``smooth_factor`` / ``smooth_factor_orig`` [in]; ``proj_down`` [in, rank]; ``proj_up`` [out, rank].
-    ``precision`` must be "int4" on MI355X ("nvfp4" needs Blackwell's block-scaled mma).
+    ``precision``: "int4" (default) or "mxfp4"; "nvfp4" needs Blackwell's block-scaled mma and is refused.
     """
 
     def __init__(
@@ -70,8 +81,12 @@ class SVDQW4A4Linear(nn.Module):
         super().__init__()
         if precision == "nvfp4":
             raise NotImplementedError("nvfp4 checkpoints are Blackwell-only; use the int4 checkpoint on MI355X")
-        if precision != "int4":
+        if precision not in ("int4", "mxfp4"):
             raise ValueError(f"Invalid precision: {precision}")
+        if precision == "mxfp4" and act_unsigned:
+            raise ValueError("MXFP4 activations are signed: act_unsigned=True does not combine with precision='mxfp4'")
+        if precision == "mxfp4" and (in_features % 128 or out_features % 128 or rank % 16 or not 0 <= rank <= 160):
+            raise ValueError("precision='mxfp4' needs in_features and out_features in multiples of 128 and a rank in multiples of 16 up to 160")
         if device is None:
             device = torch.device("cpu")
         self.in_features = in_features
@@ -79,14 +94,14 @@ class SVDQW4A4Linear(nn.Module):
         self.rank = rank
         self.precision = precision
         self.torch_dtype = torch_dtype
-        self.group_size = 64
+        self.group_size = 32 if precision == "mxfp4" else 64
 
         def p(*shape, dtype=torch_dtype, grad=False):
             return nn.Parameter(torch.empty(*shape, dtype=dtype, device=device), requires_grad=grad)
 
         self.qweight = p(out_features, in_features // 2, dtype=torch.int8)
         self.bias = p(out_features, grad=True) if bias else None
-        self.wscales = p(in_features // self.group_size, out_features)
+        self.wscales = p(in_features // self.group_size, out_features, **({"dtype": torch.uint8} if precision == "mxfp4" else {}))
         self.smooth_factor = p(in_features)
         self.smooth_factor_orig = p(in_features)
         self.proj_down = p(in_features, rank, grad=True)
@@ -113,6 +128,8 @@ class SVDQW4A4Linear(nn.Module):
     _LAYOUT_PARAMS = ("qweight", "wscales", "smooth_factor", "bias", "proj_down", "proj_up")
 
     def _layout_params(self):
+        if self.precision == "mxfp4":  # everything else is natural order in the checkpoint and in the kernels
+            return [n for n in ("wscales", "proj_down") if not (n == "proj_down" and self.rank == 0)]
         return [n for n in self._LAYOUT_PARAMS if getattr(self, n, None) is not None and not (n.startswith("proj_") and self.rank == 0)]
 
     @property
@@ -167,6 +184,9 @@ class SVDQW4A4Linear(nn.Module):
                 t = getattr(module, n).data
                 if n.startswith("proj_") and module._base_lowrank is not None:
                     t = module._base_lowrank[0 if n == "proj_down" else 1]
+                if module.precision == "mxfp4":
+                    state_dict[key] = _mxfp4_layout(n, t, inverse=True)
+                    continue
                 dev = t.device
                 if not t.is_cuda:  # a host-resident copy in the kernel layout (offloaded block): convert on the GPU, hand back on the host
                     if not torch.cuda.is_available():
@@ -196,7 +216,9 @@ class SVDQW4A4Linear(nn.Module):
             getattr(self, n)._svdq_amd = True
         for n in todo:
             t = getattr(self, n)
-            if n == "qweight":
+            if self.precision == "mxfp4":
+                t.data.copy_(_mxfp4_layout(n, t.data, inverse=False))
+            elif n == "qweight":
                 t.data = layout.repack_qweight(t.data)
             elif n == "wscales":
                 t.data.copy_(layout.repack_wscales(t.data))
@@ -232,13 +254,43 @@ class SVDQW4A4Linear(nn.Module):
 
     def forward(self, x: torch.Tensor, output: torch.Tensor | None = None, ln=None, pool=None) -> torch.Tensor:
         """x [B, S, in] 16-bit -> [B, S, out]: quantise (+ low-rank down) then the fused GEMM."""
-        B, S, C_in = x.shape
-        x2 = x.reshape(B * S, C_in)
+        if self.precision != "mxfp4":
+            B, S, C_in = x.shape  # the INT4 path takes [B, S, in] only, as before
+        lead = x.shape[:-1]
+        x2 = x.reshape(-1, x.shape[-1])
         if output is None:
-            output = torch.empty(B * S, self.out_features, dtype=x.dtype, device=x.device)
+            output = torch.empty(x2.shape[0], self.out_features, dtype=x.dtype, device=x.device)
         qx, ascales, lora_act = self.quantize(x2, ln=ln, pool=pool)
         output = self.forward_quant(qx, ascales, lora_act, output)
-        return output.reshape(B, S, -1)
+        return output.reshape(*lead, -1)
+
+    def _int4_only(self, what: str):
+        if self.precision == "mxfp4":
+            raise NotImplementedError(f"{what}: not implemented for MXFP4 layers (precision='mxfp4' runs the plain quantise + GEMM pair only)")
+
+    @classmethod
+    def from_float(cls, weight: torch.Tensor, bias: torch.Tensor | None = None, smooth: torch.Tensor | None = None,
+                   proj_down: torch.Tensor | None = None, proj_up: torch.Tensor | None = None, precision: str = "mxfp4"):
+        """A layer whose 4-bit branch encodes ``weight`` [out, in] -- the residual ``W diag(smooth) - proj_up proj_down^T`` the caller has formed --
+        with the host encoder (``quantization.mxfp4``); ``proj_down`` [in, rank] / ``proj_up`` [out, rank], ``smooth`` [in] (default ones) and
+        ``bias`` are taken as given.  No SVD, no calibration: producing the factors is the caller's business."""
+        if precision != "mxfp4":
+            raise NotImplementedError("from_float encodes MXFP4 only")
+        rank = 0 if proj_down is None else proj_down.shape[1]
+        dt = weight.dtype if weight.dtype in (torch.bfloat16, torch.float16) else torch.bfloat16
+        m = cls(weight.shape[1], weight.shape[0], rank=rank, bias=bias is not None, precision=precision, torch_dtype=dt, device=weight.device)
+        with torch.no_grad():
+            codes, scales = quantize_weight_mxfp4(weight)
+            m.qweight.copy_(codes.view(torch.int8))
+            m.wscales.copy_(scales)
+            if bias is not None:
+                m.bias.copy_(bias)
+            m.smooth_factor.copy_(torch.ones_like(m.smooth_factor) if smooth is None else smooth)
+            m.smooth_factor_orig.copy_(m.smooth_factor)
+            if rank:
+                m.proj_down.copy_(proj_down)
+                m.proj_up.copy_(proj_up)
+        return m
 
     def quantize(self, x: torch.Tensor, pad_size: int = 256, ln=None, pool=None, fuse_glu: bool = False):
         """x [N, in] -> (FP6 code image [N_pad, 3*in/4] uint8, ascales [in/64, N_pad], lora_act [N_pad, rank] f32).
@@ -246,7 +298,13 @@ class SVDQW4A4Linear(nn.Module):
         ``pool``: a ``ZeroPool`` of pre-cleared fp32 scratch for the low-rank accumulator (ops/elementwise.py);
         ``fuse_glu``: x is [N, 2 * in] interleaved (value, gate) pairs, quantised as ``value * silu(gate)`` (reference: GEMM_W4A4::quantize(x, true),
         src/Linear.cpp:444-470 -- SANA's GLU-MBConv)."""
+        if self.precision == "mxfp4":
+            for what, given in (("ln=", ln is not None), ("pool=", pool is not None), ("fuse_glu", fuse_glu)):
+                if given:
+                    self._int4_only(f"quantize({what})")
         self._ensure_layout()
+        if self.precision == "mxfp4":
+            return svdq_quantize_mxfp4(x, lora_down=self.proj_down if self.rank else None, smooth=self.smooth_factor, pad_size=pad_size)
         return svdq_quantize_w4a4_act_fuse_lora_cuda(
             x, lora_down=self.proj_down, smooth=self.smooth_factor, fuse_glu=fuse_glu, fp4=False, pad_size=pad_size, ln=ln, pool=pool
         )
@@ -255,6 +313,7 @@ class SVDQW4A4Linear(nn.Module):
         """x [N, 2 * in], the output of a gated projection whose two column halves are (value, gate): quantises ``value * act(gate)`` -- ``act`` "silu"
         (SwiGLU) or "gelu" (erf GEGLU) -- in one launch, as :meth:`quantize` would quantise the 16-bit product, which is never written
         (extension: ops.quantize.svdq_quantize_glu_halves)."""
+        self._int4_only("quantize_glu")
         self._ensure_layout()
         return svdq_quantize_glu_halves(x, lora_down=self.proj_down, smooth=self.smooth_factor, act=act, pad_size=pad_size, pool=pool)
 
@@ -263,6 +322,7 @@ class SVDQW4A4Linear(nn.Module):
         """x [B, T, C] (or [B, H, W, C]), the input of SANA's depthwise convolution, ``C <= 2 * in``: quantises ``value * silu(gate)`` of the
         interleaved (value, gate) channel pairs of ``dwconv3x3(x, conv_weight, conv_bias)`` in one launch, as :meth:`quantize` ``(fuse_glu=True)``
         would quantise the convolution's output, which is never written (extension: ops.quantize.svdq_quantize_dwconv_glu)."""
+        self._int4_only("quantize_dwconv_glu")
         self._ensure_layout()
         return svdq_quantize_dwconv_glu(x, conv_weight, conv_bias, height, width, lora_down=self.proj_down, smooth=self.smooth_factor,
                                         quantized_features=self.in_features, pad_size=pad_size, pool=pool)
@@ -270,6 +330,7 @@ class SVDQW4A4Linear(nn.Module):
     def forward_silu(self, x: torch.Tensor, output: torch.Tensor | None = None) -> torch.Tensor:
         """``silu(forward(x))`` with the SiLU in the GEMM's epilogue: one GEMM launch (reference: GEMM_W4A4::forward_silu, src/Linear.cpp:160-162).
         ``output``: a [B * S, out] buffer (any row stride the GEMM takes) to write into."""
+        self._int4_only("forward_silu")
         B, S, C_in = x.shape
         if output is None:
             output = torch.empty(B * S, self.out_features, dtype=x.dtype, device=x.device)
@@ -283,6 +344,11 @@ class SVDQW4A4Linear(nn.Module):
             output = torch.empty(
                 quantized_x.shape[0], self.out_features, dtype=self.proj_up.dtype, device=quantized_x.device
             )
+        if self.precision == "mxfp4":
+            if fuse_silu:
+                self._int4_only("forward_quant(fuse_silu=True)")
+            return svdq_gemm_mxfp4(quantized_x, self.qweight, ascales, self.wscales, out=output, lora_act_in=lora_act if self.rank else None,
+                                   lora_up=self.proj_up if self.rank else None, bias=self.bias, lora_scales=self.lora_scales, rows=output.shape[0])
         svdq_gemm_w4a4_cuda(
             act=quantized_x, wgt=self.qweight, out=output, ascales=ascales, wscales=self.wscales,
             lora_act_in=lora_act, lora_up=self.proj_up, bias=self.bias, fp4=False, alpha=self.wtscale,

@@ -4,6 +4,6 @@ exported here; every other operator is imported from its own module."""
 from .attention import attention_d64, attention_d64_bias, cross_attention, pulid_ca, qk_norm_rope  # noqa: F401
 from .conv import dwconv3x3  # noqa: F401
 from .elementwise import sana_glue, sandwich_norm, t5_residual_norm  # noqa: F401
-from .gemm import gemm_awq_multi  # noqa: F401
-from .quantize import svdq_quantize_dwconv_glu, svdq_quantize_glu_halves  # noqa: F401
+from .gemm import gemm_awq_multi, svdq_gemm_mxfp4  # noqa: F401
+from .quantize import svdq_quantize_dwconv_glu, svdq_quantize_glu_halves, svdq_quantize_mxfp4  # noqa: F401
 from .rotary import qwen_rotary  # noqa: F401

@@ -10,10 +10,18 @@ from .elementwise import ln_pool
 from .gemm import svdq_gemm_w4a4_cuda
 
 
+def _int4_only(what: str, *layers) -> None:
+    """the fused front ends and epilogues exist for the INT4 kernels only: refuse an MXFP4 layer before anything is launched"""
+    for lin in layers:
+        if getattr(lin, "precision", "int4") == "mxfp4":
+            raise NotImplementedError(f"{what}: not implemented for MXFP4 layers (precision='mxfp4' runs the plain quantise + GEMM pair only)")
+
+
 def fused_gelu_mlp(x: torch.Tensor, fc1, fc2, pad_size: int = 256, ln=None, quantized=None) -> torch.Tensor:
     """MLP ``fc2(gelu(fc1(x)))`` in three launches: quantise, fc1 GEMM whose epilogue applies GELU,
     re-quantises to unsigned 4-bit (shift 0.171875) and computes fc2's low-rank down projection,
     then the fc2 GEMM on those codes."""
+    _int4_only("fused_gelu_mlp", fc1, fc2)
     B, S, C_in = x.shape
     M = B * S
     x2 = x.reshape(M, C_in)
@@ -46,6 +54,7 @@ def fused_qkv_norm_rottary(x: torch.Tensor, proj, norm_q=None, norm_k=None, rota
     ``out_vt`` ([out_features/3, tokens] view): V is written transposed there for ``ops.attention`` instead of
     into ``output`` (this library's form of the reference's ``output=(q, k, v)`` packed mode).  ``q_scale``: Q is emitted times this
     factor (``ops.attention.q_prescale()``) for ``attention_packed(..., q_prescaled=True)``."""
+    _int4_only("fused_qkv_norm_rottary", proj)
     B, S, C_in = x.shape
     M = B * S
     x2 = x.reshape(M, C_in)
@@ -95,6 +104,7 @@ def _pair_ok(la, lb, xa, xb) -> bool:
 
 def _quantize_pair(xa, la, xb, lb, ln_a=None, ln_b=None, pool=None):
     """Both streams quantised into one set of row-side buffers (stream a first).  Returns (act, ascales, lora_act, Ma)."""
+    _int4_only("grouped two-stream launch", la, lb)
     la._ensure_layout()
     lb._ensure_layout()
     Ma, Mb, K, R = xa.shape[1], xb.shape[1], la.in_features, la.rank
@@ -134,6 +144,7 @@ def linear_pair(xa, la, xb, lb, pool=None):
 
 def linear_pair_quantized(act, asc, lact, la, lb, Ma):
     """The GEMM half of :func:`linear_pair` on an already quantised joint activation (rows < Ma: layer la)."""
+    _int4_only("linear_pair_quantized", la, lb)
     la._ensure_layout()
     lb._ensure_layout()
     Mt = act.shape[0]
@@ -190,6 +201,7 @@ def quantize_two(x, lin_a, lin_b, ln=None):
     """The SAME input quantised for two layers (different smoothing / low-rank factors) in one launch: the grouped
     quantiser with both streams reading ``x``; returns ``((codes, scales, lora_act) for lin_a, ... for lin_b)`` as views
     of one set of buffers, or None when the shapes do not allow it (rows not a multiple of 256, different ranks)."""
+    _int4_only("quantize_two", lin_a, lin_b)
     M, K = x.shape[-2], x.shape[-1]
     if x.numel() != M * K or M % 256 or lin_a.in_features != lin_b.in_features or lin_a.rank != lin_b.rank:
         return None

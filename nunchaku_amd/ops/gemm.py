@@ -67,3 +67,17 @@ def gemm_awq_multi(x: T, weights, mode: str = "concat", out: T | None = None) ->
                 raise NotImplementedError(f"gemm_awq_multi: group_size={getattr(w, 'group_size', None)} (the AWQ GEMM kernels implement 128)")
             sets.append((w.qweight, w.scales, w.scaled_zeros, w.bias))
     return ops.gemm_awq_multi(x, sets, AWQ_MULTI_MODES[mode], out)
+
+
+def svdq_gemm_mxfp4(act: T, wgt: T, ascales: T, wscales: T, out: T | None = None, lora_act_in: T | None = None, lora_up: T | None = None,
+                    bias: T | None = None, lora_scales: list[float] | None = None, rows: int | None = None) -> T:
+    """MXFP4 W4A4 GEMM, plain epilogue: ``out[:rows] = A4 W4^T`` with both E8M0 block scales ``+ round16(lora_act_in * lora_scales) lora_up^T + bias``,
+    one rounding to the 16-bit dtype of ``lora_up`` / ``bias`` / ``out`` (bfloat16 when none is given).  ``act`` / ``ascales`` as
+    :func:`ops.quantize.svdq_quantize_mxfp4` returns them, ``wgt`` ``[N, K/2]``, ``wscales`` uint8 ``[K/32, N]``; ``rows``: the valid rows M
+    (default: all of ``act``'s).  Deterministic: two calls are bit-equal."""
+    M = act.shape[0] if rows is None else int(rows)
+    if out is None:
+        ref = lora_up if lora_up is not None else bias
+        out = torch.empty(M, wgt.shape[0], dtype=torch.bfloat16 if ref is None else ref.dtype, device=act.device)
+    ops.gemm_mxfp4(act, wgt, out, ascales, wscales, lora_act_in, lora_up, bias, lora_scales, M)
+    return out

@@ -118,3 +118,27 @@ def svdq_quantize_dwconv_glu(x: torch.Tensor, weight: torch.Tensor, bias: torch.
     lora_act_out, zeroed = alloc_lora_act(M_pad, R, x.device, pool)
     ops.quantize_dwconv_glu(x4, weight, bias, output, oscales, lora_down, lora_act_out, smooth, lora_act_zeroed=zeroed)
     return output, oscales, lora_act_out
+
+
+def svdq_quantize_mxfp4(x: torch.Tensor, lora_down: torch.Tensor | None = None, smooth: torch.Tensor | None = None,
+                        pad_size: int = 256) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """OCP MXFP4 quantisation of ``x`` [M, K] (after the smoothing division) plus the low-rank down projection ``x @ lora_down`` (``lora_down``:
+    the logical ``[K, R]`` factor).  Returns ``(act uint8 [M_pad, K/2]`` e2m1 codes in natural rows, ``ascales uint8 [K/128, M_pad, 4]`` E8M0 bytes
+    with the four 32-channel blocks of a K-step in one dword, ``lora_act float32 [M_pad, R])``; rows from M on are zeros.
+    ``quantization.mxfp4.unpack_scales_mxfp4`` turns ``ascales`` into ``[K/32, M_pad]``."""
+    if x.dim() != 2:
+        raise ValueError("svdq_quantize_mxfp4: x must be [M, K]")
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    M, K = x.shape
+    if K % 128:
+        raise ValueError(f"svdq_quantize_mxfp4: K={K} must be a multiple of 128")
+    if pad_size < 1 or pad_size % 256:
+        raise ValueError("svdq_quantize_mxfp4: pad_size must be a multiple of 256")
+    R = 0 if lora_down is None else lora_down.shape[1]
+    M_pad = ceil_divide(M, pad_size) * pad_size
+    act = torch.empty(M_pad, K // 2, dtype=torch.uint8, device=x.device)
+    ascales = torch.empty(K // 128, M_pad, 4, dtype=torch.uint8, device=x.device)
+    lora_act = torch.empty(M_pad, R, dtype=torch.float32, device=x.device)
+    ops.quantize_mxfp4(x, act, ascales, lora_down, lora_act, smooth)
+    return act, ascales, lora_act
