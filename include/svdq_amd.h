@@ -1460,6 +1460,43 @@ typedef struct svdq_gemm_mxfp4_args {
 } svdq_gemm_mxfp4_args;
 int svdq_gemm_mxfp4(const svdq_gemm_mxfp4_args *args, void *stream);
 
+/* svdq_gemm_mxfp4_gelu_quant (appended like the two above: no version bump): fc1 of an MLP whose fc2 is MXFP4 too.  With
+ *   h32 = the fp32 sum svdq_gemm_mxfp4 rounds (product + low-rank term + bias), no intermediate rounding,
+ *   g   = round16(gelu_tanh(h32)), the function and rounding point of svdq_gemm_w4a4's GELU_QUANT epilogue; rows M .. M_pad - 1 count as zeros,
+ * it writes what svdq_quantize_mxfp4(g, smooth_next, lora_down) would, bit for bit in the codes and scales:
+ *   qout / oscales   the block rule above on round16(g * rcp(smooth_next)): the act / ascales operands of the next svdq_gemm_mxfp4 (K = this N)
+ *   lora_act_out     += g @ lora_down (un-smoothed g, fp32).  The N / 128 column tiles of a row block meet in fp32 atomics: the buffer must be
+ *                    zero before the launch -- cleared here by a small kernel unless lora_act_zeroed -- and for N > 128 the sums (and through
+ *                    them the next GEMM's output) depend on the order of the adds.  Codes, scales and out never do.
+ *   out              optional: g itself, 16-bit [M, ldo] (only columns < N of rows < M are written).
+ * M_pad / 256 * N / 128 workgroups (the padding rows of qout / oscales are written, as zeros).  Validation as for svdq_gemm_mxfp4 (out and
+ * ldo only when out is given), and: qout and oscales required; R_next a multiple of 16 in [0, 256]; lora_down and lora_act_out both or neither,
+ * and exactly when R_next > 0.  Alignment: qout, lora_down 16 bytes; smooth_next 8; oscales, lora_act_out 4.  Addressing reach: that of
+ * svdq_gemm_mxfp4 (the outputs are addressed in 64 bits). */
+typedef struct svdq_gemm_mxfp4_gelu_quant_args {
+    const void *act;          /* as svdq_gemm_mxfp4_args, through lora_scales                 */
+    const void *wgt;
+    const void *ascales;
+    const void *wscales;
+    const void *bias;
+    const void *lora_act_in;
+    const void *lora_up;
+    const float *lora_scales;
+    void *out;                /* [M, N] 16-bit g, row stride ldo elements, or NULL            */
+    void *qout;               /* out: [M_pad][N/2] bytes                                      */
+    void *oscales;            /* out: uint32 [N/128][M_pad]                                   */
+    const void *smooth_next;  /* [N] 16-bit, natural order; NULL = ones                       */
+    const void *lora_down;    /* next layer: [R_next][N] 16-bit, rank-major; NULL if R_next == 0 */
+    void *lora_act_out;       /* [M_pad][R_next] fp32; NULL if R_next == 0                    */
+    int32_t M, M_pad, N, K, R;
+    int32_t R_next;
+    int32_t ldo;              /* with out: >= N, a multiple of 4                              */
+    int32_t dtype;            /* SVDQ_BF16 | SVDQ_FP16                                        */
+    int32_t lora_act_zeroed;  /* non-zero: lora_act_out is already zero on this stream        */
+    int32_t reserved;
+} svdq_gemm_mxfp4_gelu_quant_args;
+int svdq_gemm_mxfp4_gelu_quant(const svdq_gemm_mxfp4_gelu_quant_args *args, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Load-time re-layout of reference checkpoint tensors (NVIDIA fragment order -> CDNA4 order).
  * src and dst must not alias.  All but svdq_repack_qweight (4 -> 6 bits per code) and svdq_repack_wscales (x 32) are pure permutations of equal size.

@@ -646,41 +646,78 @@ class _Ops:
         _lib.check(lib.svdq_quantize_mxfp4(C.byref(a), _stream()), op)
 
     @staticmethod
-    def gemm_mxfp4(act, wgt, out, ascales, wscales, lora_act_in=None, lora_up=None, bias=None, lora_scales=None, rows=None):
+    def gemm_mxfp4(act, wgt, out, ascales, wscales, lora_act_in=None, lora_up=None, bias=None, lora_scales=None, rows=None,
+                   qout=None, oscales=None, lora_down=None, lora_act_out=None, smooth_factor=None, lora_act_zeroed=False):
         """MXFP4 W4A4 GEMM with the plain epilogue (``svdq_gemm_mxfp4``): ``act`` uint8 ``[M_pad, K/2]`` and ``ascales`` ``[K/128, M_pad, 4]`` as
         :meth:`quantize_mxfp4` writes them; ``wgt`` uint8 / int8 ``[N, K/2]``; ``wscales`` uint8 ``[K/32, N]`` (checkpoint layout, packed once per
         parameter) or marked as kernel layout (``[K/128, N, 4]`` behind the same shape); ``out`` 16-bit ``[M, N]`` with any row stride that is a
-        multiple of 4; ``rows``: M (default: ``out``'s rows).  ``lora_up`` / ``bias`` in natural order."""
+        multiple of 4; ``rows``: M (default: ``out``'s rows).  ``lora_up`` / ``bias`` in natural order.
+
+        With ``qout`` the GELU_QUANT epilogue runs instead (``svdq_gemm_mxfp4_gelu_quant``): ``qout`` uint8 ``[M_pad, N/2]`` and ``oscales`` uint8
+        ``[N/128, M_pad, 4]`` receive what :meth:`quantize_mxfp4` would make of ``g = gelu_tanh(...)`` with ``smooth_factor`` ``[N]`` and
+        ``lora_down`` (the next layer's logical ``[N, R_next]`` factor, or marked as kernel layout), ``lora_act_out`` fp32 ``[M_pad, R_next]`` its
+        low-rank activations (cleared first unless ``lora_act_zeroed``); ``out`` is then optional and receives ``g``; without it ``rows`` is required."""
         op, lib = "gemm_mxfp4", _lib.load()
-        if act is None or wgt is None or out is None or ascales is None or wscales is None:
+        fused = qout is not None
+        if fused:
+            ref = next((t for t in (out, lora_up, bias, smooth_factor, lora_down) if t is not None), None)
+            dtype = torch.bfloat16 if ref is None else ref.dtype
+        if act is None or wgt is None or ascales is None or wscales is None or (out is None and not fused):
             raise ValueError(f"{op}: act, wgt, out, ascales and wscales are required")
-        if out.dim() != 2 or out.stride(1) != 1 or out.dtype not in _DT:
+        if not fused and (oscales is not None or lora_down is not None or lora_act_out is not None or smooth_factor is not None):
+            raise ValueError(f"{op}: oscales, lora_down, lora_act_out and smooth_factor belong to the GELU_QUANT epilogue: give qout")
+        if out is not None and (out.dim() != 2 or out.stride(1) != 1 or out.dtype not in _DT):
             raise ValueError(f"{op}: out must be a 2-D 16-bit view with unit column stride")
+        if out is not None:
+            dtype = out.dtype
         if act.dim() != 2 or wgt.dim() != 2 or act.dtype != torch.uint8 or wgt.dtype not in (torch.uint8, torch.int8) or act.shape[1] != wgt.shape[1]:
             raise ValueError(f"{op}: act must be uint8 [M_pad, K/2] and wgt uint8 / int8 [N, K/2]")
         M_pad, K, N = act.shape[0], act.shape[1] * 2, wgt.shape[0]
+        if out is None and rows is None:
+            raise ValueError(f"{op}: without out, rows (the valid rows M) is required")
         M = out.shape[0] if rows is None else int(rows)
         if K % 128 or N % 128:
             raise ValueError(f"{op}: K={K} and N={N} must be multiples of 128")
-        if out.shape[0] < M or out.shape[1] != N:
+        if out is not None and (out.shape[0] < M or out.shape[1] != N):
             raise ValueError(f"{op}: out must be [>= M, N]")
         if ascales.dtype != torch.uint8 or ascales.numel() != (K // 32) * M_pad:
             raise ValueError(f"{op}: ascales must hold (K/32)*M_pad bytes")
         if wscales.dtype != torch.uint8 or wscales.numel() != (K // 32) * N:
             raise ValueError(f"{op}: wscales must hold (K/32)*N bytes")
         R = 0 if lora_up is None else lora_up.shape[-1]
-        if R and (lora_act_in is None or lora_act_in.dtype != torch.float32 or lora_act_in.numel() != M_pad * R or lora_up.dtype != out.dtype
+        if R and (lora_act_in is None or lora_act_in.dtype != torch.float32 or lora_act_in.numel() != M_pad * R or lora_up.dtype != dtype
                   or lora_up.shape[0] != N):
             raise ValueError(f"{op}: the low-rank branch needs lora_act_in float32 [M_pad, R] and lora_up [N, R] in the dtype of out")
-        if bias is not None and (bias.numel() != N or bias.dtype != out.dtype):
+        if bias is not None and (bias.numel() != N or bias.dtype != dtype):
             raise ValueError(f"{op}: bias must be [N] in the dtype of out")
         if lora_scales is not None and len(lora_scales) < R // 16:
             raise ValueError(f"{op}: lora_scales must hold one scale per 16 ranks")
+        R_next = 0
+        if fused:
+            if oscales is None:
+                raise ValueError(f"{op}: qout needs oscales")
+            if qout.dtype != torch.uint8 or qout.dim() != 2 or tuple(qout.shape) != (M_pad, N // 2) or not qout.is_contiguous():
+                raise ValueError(f"{op}: qout must be contiguous uint8 [M_pad, N/2] = [{M_pad}, {N // 2}]")
+            if oscales.dtype != torch.uint8 or oscales.numel() != (N // 32) * M_pad or not oscales.is_contiguous():
+                raise ValueError(f"{op}: oscales must hold (N/32)*M_pad bytes")
+            if (lora_down is None) != (lora_act_out is None):
+                raise ValueError(f"{op}: lora_down and lora_act_out come together or not at all")
+            R_next = 0 if lora_down is None else lora_down.shape[-1]
+            if R_next % 16 or R_next > 256:
+                raise ValueError(f"{op}: the next layer's rank R_next={R_next} must be a multiple of 16 up to 256")
+            if R_next and (lora_down.dtype != dtype or lora_down.numel() != N * R_next):
+                raise ValueError(f"{op}: lora_down must be [N, R_next] in the 16-bit dtype of the launch")
+            if R_next and (lora_act_out.dtype != torch.float32 or lora_act_out.numel() != M_pad * R_next or not lora_act_out.is_contiguous()):
+                raise ValueError(f"{op}: lora_act_out must hold M_pad*R_next float32")
+            if smooth_factor is not None and (smooth_factor.numel() != N or smooth_factor.dtype != dtype):
+                raise ValueError(f"{op}: smooth_factor must be [N] in the 16-bit dtype of the launch")
+            if R_next and not getattr(lora_down, "_svdq_amd", False):
+                lora_down = _cached_conversion(lora_down, "mxfp4_down", lambda src: src.t().contiguous())
         if not getattr(wscales, "_svdq_amd", False):
             wscales = _cached_conversion(wscales, "mxfp4_wscales", lambda src: src.reshape(K // 128, 4, N).permute(0, 2, 1).contiguous())
-        a = _lib.ARGS["svdq_gemm_mxfp4_args"]()
+        a = _lib.ARGS["svdq_gemm_mxfp4_gelu_quant_args" if fused else "svdq_gemm_mxfp4_args"]()
         a.act, a.wgt, a.ascales, a.wscales, a.bias = _ptr(act), _ptr(wgt), _ptr(ascales), _ptr(wscales), _ptr(bias)
-        a.out = _ptr(out, laid_out=True)
+        a.out = None if out is None else _ptr(out, laid_out=True)
         if R:
             a.lora_act_in, a.lora_up = _ptr(lora_act_in), _ptr(lora_up)
         scales = None
@@ -688,9 +725,16 @@ class _Ops:
             scales = (C.c_float * (R // 16))(*[float(v) for v in lora_scales[:R // 16]])
             a.lora_scales = scales
         a.M, a.M_pad, a.N, a.K, a.R = _i32(op, "M", M), _i32(op, "M_pad", M_pad), _i32(op, "N", N), _i32(op, "K", K), _i32(op, "R", R)
-        a.ldo = _i32(op, "out.stride(0)", out.stride(0))
-        a.dtype = _DT[out.dtype]
-        _lib.check(lib.svdq_gemm_mxfp4(C.byref(a), _stream()), op)
+        a.ldo = _i32(op, "out.stride(0)", N if out is None else out.stride(0))
+        a.dtype = _DT[dtype]
+        if fused:
+            a.qout, a.oscales, a.smooth_next = _ptr(qout), _ptr(oscales), _ptr(smooth_factor)
+            if R_next:
+                a.lora_down, a.lora_act_out = _ptr(lora_down), _ptr(lora_act_out)
+            a.R_next, a.lora_act_zeroed = _i32(op, "R_next", R_next), int(bool(lora_act_zeroed))
+            _lib.check(lib.svdq_gemm_mxfp4_gelu_quant(C.byref(a), _stream()), op)
+        else:
+            _lib.check(lib.svdq_gemm_mxfp4(C.byref(a), _stream()), op)
         del scales
 
     @staticmethod

@@ -170,15 +170,15 @@ struct GemmParams {
     SVDQ_PROBE_PARAMS
 };
 
-__device__ __forceinline__ float gelu_tanh_f(float x) {
-    // reference: gemm_utils.cuh:305-312: x * (0.5 + 0.5 * tanh.approx(u)), u = 0.79788456 * (x + 0.044715 x^3).
-    // 0.5 + 0.5 tanh(u) = 1 / (1 + exp(-2u)): one hardware exp2 and one rcp (|error| ~1e-6, the class of
-    // tanh.approx), 7 VALU operations per element; -2 u log2(e) = x * (A + B x^2).  exp2 overflow gives
-    // x * rcp(inf) = 0 for very negative x, underflow gives x * 1 for very positive x.
-    constexpr float A = -2.0f * 0.79788456f * 1.4426950408889634f, B = A * 0.044715f;
-    const float t = x * __builtin_fmaf(x * x, B, A);
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t));
-}
+// gelu_tanh_f: svdq_common.h (shared with the MXFP4 GEMM's GELU_QUANT epilogue, gemm_mxfp4.hip).  What it reproduces of the reference:
+//   gemm_utils.cuh:305-312: x * (0.5 + 0.5 * tanh.approx(u)), u = 0.79788456 * (x + 0.044715 x^3), applied by EpilogueGelu
+//   (epilogues.cuh:22-44) to the fp32 accumulator, one rounding to 16 bits behind it.
+//   0.5 + 0.5 tanh(u) = 1 / (1 + exp(-2u)): one hardware exp2 and one rcp (|error| ~1e-6, the class of tanh.approx),
+//   7 VALU operations per element; -2 u log2(e) = x * (A + B x^2).
+//   exp2 overflow gives x * rcp(inf) = 0 for very negative x, underflow gives x * 1 for very positive x.
+//   Defined once, so that both GEMMs make the same bits of the same fp32 input (the MXFP4 tests hold the fused launch's codes to the
+//   stand-alone quantiser run on its 16-bit output).
+
 // reference: gemm_utils.cuh:290-303 (silu = x * rcp.approx(1 + ex2.approx(-x * log2 e))), applied by EpilogueSilu (gemm_base.cuh:783-792).  The same two hardware
 // approximations here (v_exp_f32, v_rcp_f32: 1 ulp each), held to oracle.silu_envelope; rounds 1-5 computed an exact expf and an IEEE divide:
 // 2.5-2.7 k static VALU per wave-tile against ~0.9 k for the default epilogue.

@@ -10,9 +10,8 @@
 //
 // The tile handling is the tile quantisers' shared back end (quantize_tail.h): a wave owns 32 rows x 128 channels in a swizzled 8 KiB LDS tile, read
 // back in record layout; the lora_down slab lands in the dead tile by LDS-DMA, the low-rank MFMAs and the fixed-order combine of the four waves
-// are quantize_tail.inc parts 1 and 3.  The block quantiser between them is this file's own: the rule is written out in VALU integer / fp32
-// operations that are exact for every 16-bit input (a multiply by a power of two, a 1-bit mantissa rounding on the bit pattern), because a
-// block of bf16 subnormals needs 2^-X = 2^127 and scales below 2^-126, which the v_cvt_scalef32_pk_fp4 converters take as fp32 scale operands.
+// are quantize_tail.inc parts 1 and 3.  The block quantiser between them is mxfp4_block.h, which the GEMM's GELU_QUANT epilogue shares.
+#include "mxfp4_block.h"
 #include "quantize_tail.h"
 
 namespace svdq {
@@ -25,29 +24,6 @@ struct Mxfp4QuantParams {
     long long ldx;
     int M, M_pad, K, R, mode;
 };
-
-// E8M0 byte of a block whose largest finite magnitude is amax (>= 0, finite): floor(log2 amax) - 2 + 127, clamped; 0 for an all-zero block
-__device__ __forceinline__ unsigned mx_scale_byte(float amax) {
-    const unsigned bits = __builtin_bit_cast(unsigned, amax);
-    const int ef = (int)(bits >> 23);
-    const int e = ef ? ef - 127 : (31 - __builtin_clz(bits | 1u)) - 149; // fp32 subnormals (the bf16 subnormals) by their leading bit
-    const int sb = e + 125;
-    return bits == 0u ? 0u : (unsigned)(sb < 0 ? 0 : sb > 254 ? 254 : sb);
-}
-// e2m1 code of y (already divided by the block scale): round to nearest, ties to the even mantissa, saturated to 6; NaN -> 0; a zero result is +0
-__device__ __forceinline__ unsigned mx_code(float y) {
-    const float ay = __builtin_fminf(nan_to_zero(__builtin_fabsf(y)), 6.0f);
-    const unsigned lo = (unsigned)__builtin_rintf(ay * 2.0f); // below 1: the subnormal step 0.5 (0, 0.5, and 1.0 = code 2)
-    unsigned u = __builtin_bit_cast(unsigned, ay);
-    u += 0x1fffffu + ((u >> 22) & 1u);                         // RNE to one mantissa bit, the carry runs into the exponent
-    const unsigned hi = (u >> 22) - 252u;                      // (exponent field - 127) * 2 + mantissa bit + 2
-    const unsigned c = ay < 1.0f ? lo : hi;
-    return c == 0u ? 0u : c | (y < 0.f ? 8u : 0u);
-}
-template <typename T> __device__ __forceinline__ float max_finite() {
-    if constexpr (__is_same(T, _Float16)) return 65504.0f;
-    else return __builtin_bit_cast(float, 0x7f7f0000u);
-}
 
 template <int DT, bool SMOOTH>
 __global__ __launch_bounds__(256, 3) void quantize_mxfp4_kernel(Mxfp4QuantParams p) {
@@ -111,30 +87,15 @@ __global__ __launch_bounds__(256, 3) void quantize_mxfp4_kernel(Mxfp4QuantParams
                     float xf = h2f(hfrom<T>((unsigned short)((unsigned)xv[grp][tc][e >> 1] >> (16 * (e & 1)))));
                     if constexpr (SMOOTH) xf = smooth_div16<T>(xf, rs[e]);
                     v[4 * q + e] = xf;
-                    amax = __builtin_fmaxf(amax, nan_to_zero(__builtin_fabsf(xf))); // NaN is no part of amax
+                    amax = mx_amax_acc(amax, xf);
                 }
             }
-            amax = __builtin_fminf(amax, max_finite<T>()); // inf counts as the largest finite value
-            amax = __builtin_fmaxf(amax, __shfl_xor(amax, 32));
-            const unsigned sb = mx_scale_byte(amax);
-            const float inv = __builtin_bit_cast(float, (254u - sb) << 23); // 2^-(sb - 127), exponent field 0 .. 254 -> [2^-127 .. 2^127]: sb = 254 never occurs (amax <= 2^128)
-            pc[b][0] = pc[b][1] = 0;
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-#pragma unroll
-                for (int e = 0; e < 4; e++) pc[b][q >> 1] |= mx_code(v[4 * q + e] * inv) << (16 * (q & 1) + 4 * e);
+            const unsigned sb = mx_block_byte<T>(amax);
+            MX_BLOCK_CODES(v, sb, pc[b]);
             sdw |= sb << (8 * b);
         }
-        // ---- the halves trade pieces: lane h keeps blocks 2h, 2h + 1 (32 contiguous bytes of the row), dword q of a block = piece q of half 0 | piece q of half 1 << 16
         unsigned dw[8];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const unsigned own = h ? pc[2 + (j >> 1)][j & 1] : pc[j >> 1][j & 1];
-            const unsigned oth = (unsigned)__shfl_xor((int)(h ? pc[j >> 1][j & 1] : pc[2 + (j >> 1)][j & 1]), 32);
-            const unsigned a = h ? oth : own, bq = h ? own : oth; // a: half 0's pieces, bq: half 1's
-            dw[2 * j] = (a & 0xffffu) | (bq << 16);
-            dw[2 * j + 1] = (a >> 16) | (bq & 0xffff0000u);
-        }
+        mx_trade_halves(pc, h, dw);
         uint8_t *dst = p.act + (size_t)(rt * 32 + r) * (K / 2) + kp * 64 + 32 * h;
         *reinterpret_cast<uint4 *>(dst) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
         *reinterpret_cast<uint4 *>(dst + 16) = make_uint4(dw[4], dw[5], dw[6], dw[7]);

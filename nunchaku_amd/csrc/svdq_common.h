@@ -127,6 +127,14 @@ __device__ __forceinline__ void lora_act_add(void *base, size_t idx, float v, in
     }
 }
 
+// ---- the GELU of the GELU_QUANT epilogues (gemm_w4a4.hip, which says what it reproduces of the reference, and gemm_mxfp4.hip) ----
+// x / (1 + exp(-2u)), u = 0.79788456 (x + 0.044715 x^3): one hardware exp2 and one rcp; -2 u log2(e) = x (A + B x^2)
+__device__ __forceinline__ float gelu_tanh_f(float x) {
+    constexpr float A = -2.0f * 0.79788456f * 1.4426950408889634f, B = A * 0.044715f;
+    const float t = x * __builtin_fmaf(x * x, B, A);
+    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t));
+}
+
 // ---- F6 / S image addressing ----------------------------------------------------------------
 constexpr int F6_CHUNK = 3072; // bytes of one (32 rows x 128 k) chunk
 constexpr int F6_PLANE = 1024;

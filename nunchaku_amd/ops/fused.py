@@ -7,21 +7,26 @@ import torch
 from ..mode import alloc_lora_act
 from ..utils import ceil_divide
 from .elementwise import ln_pool
-from .gemm import svdq_gemm_w4a4_cuda
+from .gemm import svdq_gemm_mxfp4, svdq_gemm_w4a4_cuda
 
 
 def _int4_only(what: str, *layers) -> None:
-    """the fused front ends and epilogues exist for the INT4 kernels only: refuse an MXFP4 layer before anything is launched"""
+    """the fused front ends and epilogues but fused_gelu_mlp exist for the INT4 kernels only: refuse an MXFP4 layer before anything is launched"""
     for lin in layers:
         if getattr(lin, "precision", "int4") == "mxfp4":
-            raise NotImplementedError(f"{what}: not implemented for MXFP4 layers (precision='mxfp4' runs the plain quantise + GEMM pair only)")
+            raise NotImplementedError(f"{what}: not implemented for MXFP4 layers (precision='mxfp4' runs the plain quantise + GEMM pair and fused_gelu_mlp)")
 
 
 def fused_gelu_mlp(x: torch.Tensor, fc1, fc2, pad_size: int = 256, ln=None, quantized=None) -> torch.Tensor:
     """MLP ``fc2(gelu(fc1(x)))`` in three launches: quantise, fc1 GEMM whose epilogue applies GELU,
     re-quantises to unsigned 4-bit (shift 0.171875) and computes fc2's low-rank down projection,
-    then the fc2 GEMM on those codes."""
-    _int4_only("fused_gelu_mlp", fc1, fc2)
+    then the fc2 GEMM on those codes.  Two MXFP4 layers take the same three launches on the MXFP4 kernels (signed e2m1 codes, no shift);
+    one MXFP4 and one INT4 layer do not combine."""
+    mx = [getattr(lin, "precision", "int4") == "mxfp4" for lin in (fc1, fc2)]
+    if mx[0] != mx[1]:
+        raise ValueError("fused_gelu_mlp: fc1 and fc2 must share one precision (an MXFP4 layer next to an INT4 layer)")
+    if all(mx):
+        return _fused_gelu_mlp_mxfp4(x, fc1, fc2, pad_size, ln, quantized)
     B, S, C_in = x.shape
     M = B * S
     x2 = x.reshape(M, C_in)
@@ -44,6 +49,25 @@ def fused_gelu_mlp(x: torch.Tensor, fc1, fc2, pad_size: int = 256, ln=None, quan
     out = torch.empty(M, fc2.out_features, dtype=x.dtype, device=dev)
     out = fc2.forward_quant(q_hidden, s_hidden, l_hidden, output=out)
     return out.view(B, S, -1)
+
+
+def _fused_gelu_mlp_mxfp4(x, fc1, fc2, pad_size, ln, quantized):
+    """:func:`fused_gelu_mlp` on two MXFP4 layers: ``svdq_quantize_mxfp4``, the fc1 GEMM under the GELU_QUANT epilogue, ``fc2.forward_quant``"""
+    if ln is not None:
+        _int4_only("fused_gelu_mlp(ln=)", fc1)
+    lead, M = x.shape[:-1], x.numel() // x.shape[-1]
+    qx, ascales, lora_act = fc1.quantize(x.reshape(M, x.shape[-1]), pad_size=pad_size) if quantized is None else quantized
+    M_pad, N, dev = qx.shape[0], fc1.out_features, x.device
+    fc1._ensure_layout()
+    fc2._ensure_layout()
+    q_hidden = torch.empty(M_pad, N // 2, dtype=torch.uint8, device=dev)
+    s_hidden = torch.empty(N // 128, M_pad, 4, dtype=torch.uint8, device=dev)
+    l_hidden = torch.empty(M_pad, fc2.rank, dtype=torch.float32, device=dev)
+    svdq_gemm_mxfp4(qx, fc1.qweight, ascales, fc1.wscales, lora_act_in=lora_act if fc1.rank else None, lora_up=fc1.proj_up if fc1.rank else None,
+                    bias=fc1.bias, lora_scales=fc1.lora_scales, rows=M, qout=q_hidden, oscales=s_hidden,
+                    lora_down=fc2.proj_down if fc2.rank else None, lora_act_out=l_hidden if fc2.rank else None, smooth_factor=fc2.smooth_factor)
+    out = torch.empty(M, fc2.out_features, dtype=x.dtype, device=dev)
+    return fc2.forward_quant(q_hidden, s_hidden, l_hidden, output=out).view(*lead, -1)
 
 
 def fused_qkv_norm_rottary(x: torch.Tensor, proj, norm_q=None, norm_k=None, rotary_emb: torch.Tensor | None = None,
@@ -157,6 +181,7 @@ def linear_pair_quantized(act, asc, lact, la, lb, Ma):
 
 def fused_gelu_mlp_pair(xa, fc1a, fc2a, xb, fc1b, fc2b, ln_a=None, ln_b=None):
     """``(fc2a(gelu(fc1a(xa))), fc2b(gelu(fc1b(xb))))`` with two GEMM launches instead of four."""
+    _int4_only("fused_gelu_mlp_pair", fc1a, fc2a, fc1b, fc2b)
     if not (_pair_ok(fc1a, fc1b, xa, xb) and _pair_ok(fc2a, fc2b, xa, xb)):
         return fused_gelu_mlp(xa, fc1a, fc2a, ln=ln_a), fused_gelu_mlp(xb, fc1b, fc2b, ln=ln_b)
     pool = ln_pool(ln_a)  # stream a's pool must hold both streams' scratch

@@ -1,10 +1,13 @@
 """Time the MXFP4 GEMM and quantiser against their INT4 counterparts: svdq_gemm_mxfp4 vs svdq_gemm_w4a4 (plain epilogue, rank 32, bf16) and
 svdq_quantize_mxfp4 vs svdq_quantize_w4a4_act_fuse_lora.  One process on one device; every arm is captured into a graph of `--launches`
-launches and replayed (a timed window is 2 to 17 ms), the arms alternate, the figure is the median over `--rounds` replays per launch.  At every
+launches and replayed (a timed window is 2 to 17 ms), the arms alternate, the figure is the median over `--rounds` replays per launch.  `--mlp`
+times fc1 of an MLP instead (M 4608, K 3072, N 12288): (a) the MXFP4 GELU_QUANT launch, (b) what produces the same operands without it -- plain
+svdq_gemm_mxfp4, torch's tanh GELU, svdq_quantize_mxfp4 with fc2's lora_down and smooth -- and (c) the INT4 GELU_QUANT launch.  At every
 timed GEMM shape the MXFP4 output is also compared with the fp32 product of the dequantised operands (`mxfp4_max_err_over_max_ref`; the INT4 arm
 is only checked to be finite: its operands are another format, its result another number).  Prints one JSON line per row.
 
     python tools/bench_mxfp4_gemm.py [--rounds 15] [--launches 100] > profiles/mxfp4_gemm.txt
+    python tools/bench_mxfp4_gemm.py --mlp > profiles/mxfp4_gelu_quant.txt
 
 Not measured here: hardware counters (a run of their own), end-to-end models (no model class runs MXFP4).
 """
@@ -71,12 +74,60 @@ def alternate(arms, rounds, launches):
     return {k: statistics.median(v) for k, v in times.items()}, {k: (min(v), max(v)) for k, v in times.items()}
 
 
+MLP_SHAPE = (4608, 3072, 12288)  # (M, K, N) of fc1
+
+
+def mlp(a):
+    from nunchaku_amd.ops import svdq_gemm_mxfp4, svdq_quantize_mxfp4
+    from nunchaku_amd.mode import alloc_lora_act
+    from nunchaku_amd.ops.gemm import svdq_gemm_w4a4_cuda
+
+    M, K, N = MLP_SHAPE
+    (i1, m1), (i2, m2) = layers(K, N), layers(N, K)
+    for lin in (i1, i2, m1, m2):
+        lin._ensure_layout()
+    x = torch.randn(M, K, device="cuda").bfloat16()
+    qi, qm = i1.quantize(x), m1.quantize(x)
+    dev = x.device
+    qh, sh, lh = torch.empty(M, N // 2, dtype=torch.uint8, device=dev), torch.empty(N // 128, M, 4, dtype=torch.uint8, device=dev), torch.empty(M, RANK, device=dev)
+    hid = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
+    qh_i, sh_i = torch.empty(M, N * 3 // 4, dtype=torch.uint8, device=dev), torch.empty(N // 64, M, dtype=torch.bfloat16, device=dev)
+    common = dict(lora_act_in=qm[2], lora_up=m1.proj_up, bias=m1.bias, rows=M)
+
+    def fused():
+        svdq_gemm_mxfp4(qm[0], m1.qweight, qm[1], m1.wscales, qout=qh, oscales=sh, lora_down=m2.proj_down, lora_act_out=lh, smooth_factor=m2.smooth_factor, **common)
+
+    def unfused():
+        svdq_gemm_mxfp4(qm[0], m1.qweight, qm[1], m1.wscales, out=hid, **common)
+        return svdq_quantize_mxfp4(torch.nn.functional.gelu(hid, approximate="tanh"), lora_down=m2.proj_down, smooth=m2.smooth_factor)
+
+    def int4():  # as ops.fused.fused_gelu_mlp launches it
+        lh_i, zeroed = alloc_lora_act(M, RANK, dev, None)
+        svdq_gemm_w4a4_cuda(act=qi[0], wgt=i1.qweight, qout=qh_i, ascales=qi[1], wscales=i1.wscales, oscales=sh_i, lora_act_in=qi[2], lora_up=i1.proj_up,
+                            lora_down=i2.proj_down, lora_act_out=lh_i, bias=i1.bias, smooth_factor=i2.smooth_factor, lora_scales=getattr(i1, "lora_scales", None), lora_act_zeroed=zeroed)
+
+    fused()
+    ref = unfused()  # the fused launch rounds gelu once from fp32, this path twice: the codes agree except next to a rounding boundary
+    agree = float((qh == ref[0]).float().mean())
+    assert agree > 0.98 and bool(lh.isfinite().all()), agree
+    arms = {"mxfp4_fused": captured(fused, a.launches), "mxfp4_gemm_gelu_quantize": captured(unfused, a.launches), "int4_fused": captured(int4, a.launches)}
+    med, span = alternate(arms, a.rounds, a.launches)
+    row = {"op": "fc1_gelu_quant", "M": M, "K": K, "N": N, "code_bytes_equal_to_unfused": round(agree, 4)}
+    for k in arms:
+        row[k + "_us"], row[k + "_min_max_us"] = round(med[k], 2), [round(v, 2) for v in span[k]]
+    row["fused_over_unfused"], row["fused_over_int4"] = round(med["mxfp4_fused"] / med["mxfp4_gemm_gelu_quantize"], 3), round(med["mxfp4_fused"] / med["int4_fused"], 3)
+    print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--launches", type=int, default=100)
+    ap.add_argument("--mlp", action="store_true")
     a = ap.parse_args()
     print(json.dumps({"device": torch.cuda.get_device_name(0), "rounds": a.rounds, "launches_per_replay": a.launches, "rank": RANK, "dtype": "bf16"}))
+    if a.mlp:
+        return mlp(a)
     for M, K, N in GEMM_SHAPES:
         int4, mx = layers(K, N)
         x = torch.randn(M, K, device="cuda").bfloat16()
