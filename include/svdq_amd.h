@@ -1497,6 +1497,47 @@ typedef struct svdq_gemm_mxfp4_gelu_quant_args {
 } svdq_gemm_mxfp4_gelu_quant_args;
 int svdq_gemm_mxfp4_gelu_quant(const svdq_gemm_mxfp4_gelu_quant_args *args, void *stream);
 
+/* svdq_gemm_mxfp4_qkv (appended like the three above: no version bump): the QKV projection of an attention block, N = 3 * H * 128, with the
+ * per-head RMSNorm and the rotary embedding in the epilogue.  Column tile bn = n / 128 is a head of Q for bn < H, of K for bn < 2 H, of V
+ * otherwise.  With
+ *   h32 = the fp32 sum svdq_gemm_mxfp4 rounds (product, then the low-rank term, then bias), no intermediate rounding,
+ * a Q or K tile is, per row m and in fp32,
+ *   coef = rsqrt(sum_c h32_c^2 / 128 + 1e-6)                       (the hardware reciprocal square root; the order of the sum is the kernel's)
+ *   y_c  = h32_c * ((coef * q_scale) * w_c)                        w = norm_q or norm_k; q_scale on Q tiles only, 0 = off, 1.0 bit-identical to off
+ *   (out_2j, out_2j+1) = round16(y_2j cos - y_2j+1 sin, y_2j sin + y_2j+1 cos)     one rounding; the products y_2j+1 sin / y_2j+1 cos are rounded
+ *                                                                  to fp32, the other product is fused into the add
+ * with (sin, cos) of (row m, pair j) at float (m >> 4) * 2048 + (j >> 2) * 128 + (m & 7) * 16 + (j & 3) * 4 + ((m >> 3) & 1) * 2 of rotary_emb:
+ * models.embeddings.pack_rotemb's order, the tensor svdq_gemm_w4a4's RMSNORM_ROPE epilogue reads.  A V tile is round16(h32), bit-equal to what
+ * svdq_gemm_mxfp4 writes for those columns; with out_vt it goes TRANSPOSED to out_vt[(n - 2N/3) * ldvt + m] and NOT to `out`.  Rows m >= M are
+ * written nowhere.  No atomics: two launches are bit-equal.  ceil(M / 256) * N / 128 workgroups.
+ * Validation as for svdq_gemm_mxfp4, and SVDQ_E_INVALID for: N % 384 != 0; norm_q, norm_k or rotary_emb NULL; q_scale negative or not finite;
+ * with out_vt: ldvt < M or ldvt % 8.
+ * Alignment of the operands of svdq_gemm_mxfp4_qkv: those of svdq_gemm_mxfp4; norm_q, norm_k, rotary_emb 8 bytes; out_vt 16 bytes and ldvt 8
+ * elements (every 8-token piece of a V^T row is one 16-byte store).  Addressing reach: that of svdq_gemm_mxfp4 (the table and both outputs
+ * are addressed in 64 bits). */
+typedef struct svdq_gemm_mxfp4_qkv_args {
+    const void *act;          /* as svdq_gemm_mxfp4_args, through out                         */
+    const void *wgt;
+    const void *ascales;
+    const void *wscales;
+    const void *bias;
+    const void *lora_act_in;
+    const void *lora_up;
+    const float *lora_scales;
+    void *out;                /* [M, N] 16-bit, row stride ldo elements                       */
+    const void *norm_q;       /* [128] 16-bit                                                 */
+    const void *norm_k;       /* [128] 16-bit                                                 */
+    const void *rotary_emb;   /* [M_pad][128] fp32, pack_rotemb order                         */
+    void *out_vt;             /* [N/3][ldvt] 16-bit or NULL                                   */
+    int32_t M, M_pad, N, K, R;
+    int32_t ldo;              /* >= N, a multiple of 4                                        */
+    int32_t dtype;            /* SVDQ_BF16 | SVDQ_FP16                                        */
+    int32_t ldvt;             /* with out_vt: >= M, a multiple of 8                           */
+    float q_scale;            /* Q times this before its rounding; 0 = off                    */
+    int32_t reserved;
+} svdq_gemm_mxfp4_qkv_args;
+int svdq_gemm_mxfp4_qkv(const svdq_gemm_mxfp4_qkv_args *args, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Load-time re-layout of reference checkpoint tensors (NVIDIA fragment order -> CDNA4 order).
  * src and dst must not alias.  All but svdq_repack_qweight (4 -> 6 bits per code) and svdq_repack_wscales (x 32) are pure permutations of equal size.

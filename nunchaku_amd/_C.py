@@ -647,7 +647,8 @@ class _Ops:
 
     @staticmethod
     def gemm_mxfp4(act, wgt, out, ascales, wscales, lora_act_in=None, lora_up=None, bias=None, lora_scales=None, rows=None,
-                   qout=None, oscales=None, lora_down=None, lora_act_out=None, smooth_factor=None, lora_act_zeroed=False):
+                   qout=None, oscales=None, lora_down=None, lora_act_out=None, smooth_factor=None, lora_act_zeroed=False,
+                   norm_q=None, norm_k=None, rotary_emb=None, out_vt=None, q_scale=0.0):
         """MXFP4 W4A4 GEMM with the plain epilogue (``svdq_gemm_mxfp4``): ``act`` uint8 ``[M_pad, K/2]`` and ``ascales`` ``[K/128, M_pad, 4]`` as
         :meth:`quantize_mxfp4` writes them; ``wgt`` uint8 / int8 ``[N, K/2]``; ``wscales`` uint8 ``[K/32, N]`` (checkpoint layout, packed once per
         parameter) or marked as kernel layout (``[K/128, N, 4]`` behind the same shape); ``out`` 16-bit ``[M, N]`` with any row stride that is a
@@ -656,9 +657,21 @@ class _Ops:
         With ``qout`` the GELU_QUANT epilogue runs instead (``svdq_gemm_mxfp4_gelu_quant``): ``qout`` uint8 ``[M_pad, N/2]`` and ``oscales`` uint8
         ``[N/128, M_pad, 4]`` receive what :meth:`quantize_mxfp4` would make of ``g = gelu_tanh(...)`` with ``smooth_factor`` ``[N]`` and
         ``lora_down`` (the next layer's logical ``[N, R_next]`` factor, or marked as kernel layout), ``lora_act_out`` fp32 ``[M_pad, R_next]`` its
-        low-rank activations (cleared first unless ``lora_act_zeroed``); ``out`` is then optional and receives ``g``; without it ``rows`` is required."""
+        low-rank activations (cleared first unless ``lora_act_zeroed``); ``out`` is then optional and receives ``g``; without it ``rows`` is required.
+
+        With ``rotary_emb`` (float32 ``[M_pad, 128]``, ``pack_rotemb`` order) the RMSNorm + RoPE epilogue of a QKV projection runs
+        (``svdq_gemm_mxfp4_qkv``, ``N = 3 * H * 128``), admitted and refused as :meth:`gemm_w4a4` does for the INT4 one: it needs ``out``, ``norm_q``
+        and ``norm_k`` (``[128]`` in the dtype of ``out``); ``out_vt`` (``[N/3, tokens]``, unit column stride, 16-byte aligned rows) receives V
+        transposed instead of the V columns of ``out``; ``q_scale``: the Q third times this factor before its rounding (0 = off).  Without
+        ``rotary_emb`` the norm weights and ``q_scale`` are not looked at and ``out_vt`` is refused."""
         op, lib = "gemm_mxfp4", _lib.load()
-        fused = qout is not None
+        fused, qkv = qout is not None, rotary_emb is not None
+        if fused and (qkv or norm_q is not None or norm_k is not None or out_vt is not None):
+            raise ValueError(f"{op}: norm_q, norm_k, rotary_emb and out_vt (the RMSNorm+RoPE epilogue) do not combine with qout (GELU_QUANT)")
+        if out_vt is not None and not qkv:
+            raise ValueError(f"{op}: out_vt needs the RMSNorm+RoPE epilogue (rotary_emb, norm_q, norm_k)")
+        if qkv and (out is None or norm_q is None or norm_k is None):
+            raise ValueError(f"{op}: the RMSNorm+RoPE epilogue needs out, norm_q and norm_k")
         if fused:
             ref = next((t for t in (out, lora_up, bias, smooth_factor, lora_down) if t is not None), None)
             dtype = torch.bfloat16 if ref is None else ref.dtype
@@ -713,9 +726,24 @@ class _Ops:
                 raise ValueError(f"{op}: smooth_factor must be [N] in the 16-bit dtype of the launch")
             if R_next and not getattr(lora_down, "_svdq_amd", False):
                 lora_down = _cached_conversion(lora_down, "mxfp4_down", lambda src: src.t().contiguous())
+        if qkv:
+            if N % 384:
+                raise ValueError(f"{op}: N={N} must be a multiple of 384 (3 * heads * 128) for the RMSNorm+RoPE epilogue")
+            if rotary_emb.dtype != torch.float32 or rotary_emb.shape[-1] != 128 or rotary_emb.numel() != M_pad * 128 or not rotary_emb.is_contiguous():
+                raise ValueError(f"{op}: rotary_emb must be contiguous float32 [M_pad, 128] (pack_rotemb order)")
+            for name, t in (("norm_q", norm_q), ("norm_k", norm_k)):
+                if t.numel() != 128 or t.dtype != dtype or not t.is_contiguous():
+                    raise ValueError(f"{op}: {name} must be [128] in the dtype of out")
+            if out_vt is not None:
+                if out_vt.dim() != 2 or out_vt.stride(1) != 1 or out_vt.shape[0] * 3 != N or out_vt.dtype != dtype:
+                    raise ValueError(f"{op}: out_vt must be a [N/3, tokens] view with unit column stride in the dtype of out")
+                if out_vt.shape[1] < M:
+                    raise ValueError(f"{op}: out_vt has fewer columns than out has rows")
+                if out_vt.stride(0) % 8 or out_vt.data_ptr() % 16:
+                    raise ValueError(f"{op}: out_vt must start on 16 bytes with a row stride that is a multiple of 8")
         if not getattr(wscales, "_svdq_amd", False):
             wscales = _cached_conversion(wscales, "mxfp4_wscales", lambda src: src.reshape(K // 128, 4, N).permute(0, 2, 1).contiguous())
-        a = _lib.ARGS["svdq_gemm_mxfp4_gelu_quant_args" if fused else "svdq_gemm_mxfp4_args"]()
+        a = _lib.ARGS["svdq_gemm_mxfp4_gelu_quant_args" if fused else "svdq_gemm_mxfp4_qkv_args" if qkv else "svdq_gemm_mxfp4_args"]()
         a.act, a.wgt, a.ascales, a.wscales, a.bias = _ptr(act), _ptr(wgt), _ptr(ascales), _ptr(wscales), _ptr(bias)
         a.out = None if out is None else _ptr(out, laid_out=True)
         if R:
@@ -733,6 +761,11 @@ class _Ops:
                 a.lora_down, a.lora_act_out = _ptr(lora_down), _ptr(lora_act_out)
             a.R_next, a.lora_act_zeroed = _i32(op, "R_next", R_next), int(bool(lora_act_zeroed))
             _lib.check(lib.svdq_gemm_mxfp4_gelu_quant(C.byref(a), _stream()), op)
+        elif qkv:
+            a.norm_q, a.norm_k, a.rotary_emb, a.q_scale = _ptr(norm_q), _ptr(norm_k), _ptr(rotary_emb), float(q_scale)
+            if out_vt is not None:
+                a.out_vt, a.ldvt = _ptr(out_vt, laid_out=True), _i32(op, "out_vt.stride(0)", out_vt.stride(0))
+            _lib.check(lib.svdq_gemm_mxfp4_qkv(C.byref(a), _stream()), op)
         else:
             _lib.check(lib.svdq_gemm_mxfp4(C.byref(a), _stream()), op)
         del scales

@@ -16,6 +16,7 @@
 //
 // svdq_gemm_mxfp4_gelu_quant: the same loop (gemm_mxfp4_loop.inc) under the GELU_QUANT epilogue -- GELU, the MXFP4 requantisation for the next
 // layer and that layer's low-rank down projection (gemm_mxfp4_gelu_quant_kernel below).
+// svdq_gemm_mxfp4_qkv: the same loop under the RMSNorm + RoPE epilogue of a QKV projection, V optionally transposed (gemm_mxfp4_qkv_kernel below).
 #include <type_traits>
 
 #include "mxfp4_block.h"
@@ -215,6 +216,171 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp4_gelu_quant_kernel(Mxfp4Gelu
     }
 }
 
+// ---- the QKV variant: the attention projection of a block, N = 3 H 128.  Same loop, same low-rank-up MFMAs; the workgroup's 128 columns are one head
+// of Q (bn < H), of K (bn < 2 H) or of V, block-uniformly.  With h32 = acc + bias:
+//   Q, K   coef = rsqrt(sum_c h32_c^2 / 128 + 1e-6);  y_c = h32_c * ((coef * q_scale) * w_c);  pairs (2 j, 2 j + 1) rotated by the row's (sin, cos)_j;
+//          one rounding.  A lane holds 64 of its row's 128 columns, so the sum of squares finishes in ONE exchange between the half-waves, and the
+//          lane's columns 4 h + {0, 1} and 4 h + {2, 3} of every 8-column piece are whole pairs: the rotation crosses no lane.
+//   V      round16(h32), the plain kernel's value -- into `out`, or with out_vt transposed: both stage buffers are dead behind the loop, so a wave
+//          turns 32 rows x 128 columns at a time through its 12 KiB of them (column-major, 80 bytes a column: the 2-byte writes of the two
+//          half-waves, four columns apart, fall into different banks) and stores 16 bytes = 8 consecutive tokens a lane, 64 contiguous bytes a column.
+// The rotary table is pack_rotemb's: float (m >> 4) * 2048 + (c >> 3) * 128 + (m & 7) * 16 + ((c >> 1) & 3) * 4 + ((m >> 3) & 1) * 2 holds (sin, cos)
+// of row m, pair c >> 1 -- two 8-byte loads per 8-column piece, rows up to M_pad (the table has them all).  The norm vector (32 registers, 16-bit)
+// is loaded ahead of the bias; the rotary entries run one (row tile, block) = 16 registers ahead of the arithmetic, no further (as load_cols above).
+struct Mxfp4QkvParams : Mxfp4GemmParams {
+    const void *norm_q, *norm_k; // [128] 16-bit
+    const float *rotary_emb;     // [M_pad][128]
+    void *out_vt;                // [N / 3][ldvt] 16-bit or null
+    long long ldvt;
+    float q_scale;               // 1 = off
+};
+
+constexpr int MX_VT_COL = 80, MX_VT_WAVE = 2 * MX_STAGE / 4; // bytes a column (64 + 16), bytes of LDS a wave
+
+template <int DT>
+__global__ __launch_bounds__(256, 2) void gemm_mxfp4_qkv_kernel(Mxfp4QkvParams p) {
+    using T = typename Half<DT>::T;
+    using V8 = typename Half<DT>::V8;
+#include "gemm_mxfp4_loop.inc"
+    const int mw0 = m0 + wave * 64, heads = p.N / (3 * MX_TN);
+    if (bn < 2 * heads) { // ---- Q or K
+        const bool is_q = bn < heads;
+        const T *nw = (const T *)(is_q ? p.norm_q : p.norm_k) + 4 * h;
+        const float qs = is_q ? p.q_scale : 1.0f;
+        u16x4 wv[4][4];
+#pragma unroll
+        for (int ni = 0; ni < 4; ni++)
+#pragma unroll
+            for (int g = 0; g < 4; g++) wv[ni][g] = *reinterpret_cast<const u16x4 *>(nw + ni * 32 + g * 8);
+        const float *rrow[2];
+#pragma unroll
+        for (int mi = 0; mi < 2; mi++) {
+            const unsigned m = (unsigned)(mw0 + mi * 32 + r);
+            rrow[mi] = p.rotary_emb + (size_t)(m >> 4) * 2048 + (m & 7u) * 16u + ((m >> 3) & 1u) * 2u + 8 * h;
+        }
+        float2 rot[2][4][2]; // [block parity][piece][pair of the piece's lane columns]
+        auto load_rot = [&](int blk) { // block blk = 4 mi + ni
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const float *rp = rrow[blk >> 2] + (4 * (blk & 3) + g) * 128;
+                rot[blk & 1][g][0] = *reinterpret_cast<const float2 *>(rp);
+                rot[blk & 1][g][1] = *reinterpret_cast<const float2 *>(rp + 4);
+            }
+        };
+        load_rot(0);
+        if (p.bias) {
+#pragma unroll
+            for (int ni = 0; ni < 4; ni++)
+#pragma unroll
+                for (int g = 0; g < 4; g++) {
+                    const u16x4 bb = *reinterpret_cast<const u16x4 *>((const T *)p.bias + n0 + ni * 32 + g * 8 + 4 * h);
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        const float b = h2f(hfrom<T>(bb[e]));
+                        acc[ni][0][4 * g + e] += b;
+                        acc[ni][1][4 * g + e] += b;
+                    }
+                }
+        }
+        float coef[2];
+#pragma unroll
+        for (int mi = 0; mi < 2; mi++) {
+            float s0 = 0.f, s1 = 0.f; // two chains: the 64 dependent fused multiply-adds of one would be the epilogue's critical path
+#pragma unroll
+            for (int ni = 0; ni < 4; ni++)
+#pragma unroll
+                for (int i = 0; i < 16; i += 2) {
+                    s0 = __builtin_fmaf(acc[ni][mi][i], acc[ni][mi][i], s0);
+                    s1 = __builtin_fmaf(acc[ni][mi][i + 1], acc[ni][mi][i + 1], s1);
+                }
+            float s = s0 + s1;
+            s += __shfl_xor(s, 32); // the other 64 columns of the row (commutative: both halves hold the same sum)
+            coef[mi] = __builtin_amdgcn_rsqf(s * (1.0f / 128.0f) + 1e-6f) * qs;
+        }
+#pragma unroll
+        for (int mi = 0; mi < 2; mi++) {
+            const int m = mw0 + mi * 32 + r;
+            T *orow = (T *)p.out + (size_t)m * p.ldo + n0 + 4 * h;
+#pragma unroll
+            for (int ni = 0; ni < 4; ni++) {
+                const int blk = 4 * mi + ni;
+                if (blk + 1 < 8) load_rot(blk + 1);
+                asm volatile("" ::: "memory");
+#pragma unroll
+                for (int g = 0; g < 4; g++) {
+                    float y[4];
+#pragma unroll
+                    for (int e = 0; e < 4; e++) y[e] = acc[ni][mi][4 * g + e] * (coef[mi] * h2f(hfrom<T>(wv[ni][g][e])));
+                    u16x4 o;
+#pragma unroll
+                    for (int q = 0; q < 2; q++) {
+                        const float2 sc = rot[blk & 1][g][q]; // (sin, cos)
+                        o[2 * q] = hbits(f2h<T>(__builtin_fmaf(y[2 * q], sc.y, -(y[2 * q + 1] * sc.x))));
+                        o[2 * q + 1] = hbits(f2h<T>(__builtin_fmaf(y[2 * q], sc.x, y[2 * q + 1] * sc.y)));
+                    }
+                    if (m < p.M) *reinterpret_cast<u16x4 *>(orow + ni * 32 + g * 8) = o;
+                }
+            }
+        }
+        return;
+    }
+    // ---- V: the plain kernel's values
+    const bool vt = p.out_vt != nullptr;
+    if (vt) __syncthreads(); // every wave is through the last K-step's fragment reads: the stage buffers are free
+    mx_lds_u8 *W = (mx_lds_u8 *)lds + wave * MX_VT_WAVE;
+#pragma unroll
+    for (int mi = 0; mi < 2; mi++) {
+        const int m = mw0 + mi * 32 + r;
+        T *orow = (T *)p.out + (size_t)m * p.ldo;
+#pragma unroll
+        for (int ni = 0; ni < 4; ni++)
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const int c = ni * 32 + g * 8 + 4 * h;
+                u16x4 bb = {0, 0, 0, 0}, o;
+                if (p.bias) bb = *reinterpret_cast<const u16x4 *>((const T *)p.bias + n0 + c);
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    float v = acc[ni][mi][4 * g + e];
+                    if (p.bias) v += h2f(hfrom<T>(bb[e]));
+                    o[e] = hbits(f2h<T>(v));
+                }
+                if (!vt) {
+                    if (m < p.M) *reinterpret_cast<u16x4 *>(orow + n0 + c) = o;
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; e++) *(__attribute__((address_space(3))) unsigned short *)(W + (c + e) * MX_VT_COL + 2 * r) = o[e];
+                }
+            }
+        if (!vt) continue;
+        __syncthreads(); // (the waves share nothing here: the barrier orders a wave's own lanes' writes ahead of its reads, and costs three a tile)
+        const int mq = mw0 + mi * 32 + 8 * (lane & 3); // the lane's 8 tokens
+        const mx_lds_u8 *src = W + (lane >> 2) * MX_VT_COL + 16 * (lane & 3);
+        T *dst = (T *)p.out_vt + (size_t)(n0 - 2 * heads * MX_TN + (lane >> 2)) * p.ldvt + mq;
+        const int mt = m0 + __builtin_amdgcn_readfirstlane(wave) * 64 + mi * 32; // the row tile's first row, as a scalar: the two branches are wave-uniform
+        if (mt + 32 <= p.M) { // all 32 rows are tokens: eight reads, then eight stores
+            v4i t[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) t[j] = *(const mx_lds_v4i *)(src + 16 * j * MX_VT_COL);
+#pragma unroll
+            for (int j = 0; j < 8; j++) *reinterpret_cast<v4i *>(dst + (size_t)16 * j * p.ldvt) = t[j];
+        } else if (mt < p.M) { // the row tile M ends in: whole pieces as above, the piece that holds row M token by token
+#pragma unroll 1
+            for (int j = 0; j < 8; j++) {
+                const v4i t = *(const mx_lds_v4i *)(src + 16 * j * MX_VT_COL);
+                T *d = dst + (size_t)16 * j * p.ldvt;
+                if (mq + 8 <= p.M) *reinterpret_cast<v4i *>(d) = t;
+                else {
+#pragma unroll
+                    for (int e = 0; e < 8; e++)
+                        if (mq + e < p.M) d[e] = hfrom<T>((unsigned short)((unsigned)t[e >> 1] >> (16 * (e & 1))));
+                }
+            }
+        }
+        if (mi == 0) __syncthreads(); // the reads are through before the second row tile overwrites the columns
+    }
+}
+
 // clears lora_act_out ahead of the GELU_QUANT launch (a kernel, not hipMemsetAsync: the launch may be recorded into a graph)
 static __global__ __launch_bounds__(256) void gemm_mxfp4_clear(uint32_t *dst, size_t words) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) dst[i] = 0u;
@@ -224,7 +390,7 @@ static __global__ __launch_bounds__(256) void gemm_mxfp4_clear(uint32_t *dst, si
 
 using namespace svdq;
 
-// what both entries check of the fields they share (A: svdq_gemm_mxfp4_args or svdq_gemm_mxfp4_gelu_quant_args); 0 or the error code, nothing is launched.
+// what the entries check of the fields they share (A: svdq_gemm_mxfp4_args, svdq_gemm_mxfp4_gelu_quant_args or svdq_gemm_mxfp4_qkv_args); 0 or the error code, nothing is launched.
 // `rows`: the rows the grid covers.  fills the kernel's parameters
 template <typename A> static int mx_gemm_validate(const A *a, const char *fn, bool need_out, int rows, Mxfp4GemmParams &p, long long &grid) {
     if (!a) { set_error("%s: args is NULL", fn); return SVDQ_E_INVALID; }
@@ -270,6 +436,28 @@ extern "C" int svdq_gemm_mxfp4(const svdq_gemm_mxfp4_args *a, void *stream) {
     if (a->dtype == SVDQ_BF16) hipLaunchKernelGGL((gemm_mxfp4_kernel<SVDQ_BF16>), dim3((unsigned)grid), dim3(256), 0, st, p);
     else hipLaunchKernelGGL((gemm_mxfp4_kernel<SVDQ_FP16>), dim3((unsigned)grid), dim3(256), 0, st, p);
     return hip_check(hipGetLastError(), "svdq_gemm_mxfp4 launch");
+}
+
+extern "C" int svdq_gemm_mxfp4_qkv(const svdq_gemm_mxfp4_qkv_args *a, void *stream) {
+    const char *fn = "svdq_gemm_mxfp4_qkv";
+    Mxfp4QkvParams p;
+    long long grid;
+    if (const int rc = mx_gemm_validate(a, fn, true, a ? a->M : 0, p, grid)) return rc;
+    if (a->N % (3 * MX_TN)) { set_error("%s: N=%d must be a multiple of 384 (3 x heads x 128)", fn, a->N); return SVDQ_E_INVALID; }
+    if (!a->norm_q || !a->norm_k || !a->rotary_emb) { set_error("%s: norm_q, norm_k and rotary_emb are required", fn); return SVDQ_E_INVALID; }
+    if (((uintptr_t)a->norm_q | (uintptr_t)a->norm_k | (uintptr_t)a->rotary_emb) & 7) { set_error("%s: norm_q, norm_k and rotary_emb must be 8-byte aligned", fn); return SVDQ_E_INVALID; }
+    if (a->out_vt && (((uintptr_t)a->out_vt & 15) || a->ldvt < a->M || a->ldvt % 8)) {
+        set_error("%s: out_vt must be 16-byte aligned with ldvt=%d >= M=%d a multiple of 8", fn, a->ldvt, a->M);
+        return SVDQ_E_INVALID;
+    }
+    if (!(a->q_scale >= 0.f) || a->q_scale > 3.0e38f) { set_error("%s: q_scale must be finite and >= 0 (0 = off)", fn); return SVDQ_E_INVALID; }
+    // (addressing reach: the table's, out's and out_vt's row addresses are formed in 64 bits -- nothing beyond what the shared checks hold)
+    p.norm_q = a->norm_q; p.norm_k = a->norm_k; p.rotary_emb = (const float *)a->rotary_emb; p.out_vt = a->out_vt; p.ldvt = a->ldvt;
+    p.q_scale = a->q_scale == 0.f ? 1.0f : a->q_scale;
+    hipStream_t st = (hipStream_t)stream;
+    if (a->dtype == SVDQ_BF16) hipLaunchKernelGGL((gemm_mxfp4_qkv_kernel<SVDQ_BF16>), dim3((unsigned)grid), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((gemm_mxfp4_qkv_kernel<SVDQ_FP16>), dim3((unsigned)grid), dim3(256), 0, st, p);
+    return hip_check(hipGetLastError(), "svdq_gemm_mxfp4_qkv launch");
 }
 
 extern "C" int svdq_gemm_mxfp4_gelu_quant(const svdq_gemm_mxfp4_gelu_quant_args *a, void *stream) {

@@ -266,7 +266,7 @@ class SVDQW4A4Linear(nn.Module):
 
     def _int4_only(self, what: str):
         if self.precision == "mxfp4":
-            raise NotImplementedError(f"{what}: not implemented for MXFP4 layers (precision='mxfp4' runs the plain quantise + GEMM pair only)")
+            raise NotImplementedError(f"{what}: not implemented for MXFP4 layers (precision='mxfp4' runs the plain quantise + GEMM pair, and ops.fused's fused_gelu_mlp and fused_qkv_norm_rottary)")
 
     @classmethod
     def from_float(cls, weight: torch.Tensor, bias: torch.Tensor | None = None, smooth: torch.Tensor | None = None,

@@ -11,10 +11,12 @@ from .gemm import svdq_gemm_mxfp4, svdq_gemm_w4a4_cuda
 
 
 def _int4_only(what: str, *layers) -> None:
-    """the fused front ends and epilogues but fused_gelu_mlp exist for the INT4 kernels only: refuse an MXFP4 layer before anything is launched"""
+    """the fused front ends and epilogues but fused_gelu_mlp and fused_qkv_norm_rottary exist for the INT4 kernels only: refuse an MXFP4 layer
+    before anything is launched"""
     for lin in layers:
         if getattr(lin, "precision", "int4") == "mxfp4":
-            raise NotImplementedError(f"{what}: not implemented for MXFP4 layers (precision='mxfp4' runs the plain quantise + GEMM pair and fused_gelu_mlp)")
+            raise NotImplementedError(f"{what}: not implemented for MXFP4 layers (precision='mxfp4' runs the plain quantise + GEMM pair, "
+                                      "fused_gelu_mlp and fused_qkv_norm_rottary)")
 
 
 def fused_gelu_mlp(x: torch.Tensor, fc1, fc2, pad_size: int = 256, ln=None, quantized=None) -> torch.Tensor:
@@ -77,8 +79,10 @@ def fused_qkv_norm_rottary(x: torch.Tensor, proj, norm_q=None, norm_k=None, rota
     ``rotary_emb`` is the ``pack_rotemb`` tensor of the reference ([1, M_pad, 128] float32).
     ``out_vt`` ([out_features/3, tokens] view): V is written transposed there for ``ops.attention`` instead of
     into ``output`` (this library's form of the reference's ``output=(q, k, v)`` packed mode).  ``q_scale``: Q is emitted times this
-    factor (``ops.attention.q_prescale()``) for ``attention_packed(..., q_prescaled=True)``."""
-    _int4_only("fused_qkv_norm_rottary", proj)
+    factor (``ops.attention.q_prescale()``) for ``attention_packed(..., q_prescaled=True)``.  An MXFP4 ``proj`` takes the same two launches on
+    the MXFP4 kernels (``svdq_quantize_mxfp4``, the GEMM under its RMSNorm + RoPE epilogue); the tuple form of ``output`` and ``ln=`` are INT4 only."""
+    if getattr(proj, "precision", "int4") == "mxfp4":
+        return _fused_qkv_norm_rottary_mxfp4(x, proj, norm_q, norm_k, rotary_emb, output, out_vt, ln, quantized, q_scale)
     B, S, C_in = x.shape
     M = B * S
     x2 = x.reshape(M, C_in)
@@ -108,6 +112,23 @@ def fused_qkv_norm_rottary(x: torch.Tensor, proj, norm_q=None, norm_k=None, rota
         norm_q=None if norm_q is None else norm_q.weight, norm_k=None if norm_k is None else norm_k.weight,
         rotary_emb=rot, out_vt=out_vt, lora_scales=getattr(proj, "lora_scales", None), q_scale=q_scale,
     )
+    return output.view(B, S, -1)
+
+
+def _fused_qkv_norm_rottary_mxfp4(x, proj, norm_q, norm_k, rotary_emb, output, out_vt, ln, quantized, q_scale):
+    """:func:`fused_qkv_norm_rottary` on an MXFP4 layer: ``svdq_quantize_mxfp4``, then the GEMM under the RMSNorm + RoPE epilogue"""
+    if isinstance(output, tuple):
+        raise NotImplementedError("fused_qkv_norm_rottary(output=(q, k, v)): not implemented for MXFP4 layers (give out_vt= for the attention hand-off)")
+    B, S, C_in = x.shape
+    M = B * S
+    qx, ascales, lora_act = proj.quantize(x.reshape(M, C_in), ln=ln) if quantized is None else quantized  # (ln=: refused there)
+    if output is None:
+        output = torch.empty(M, proj.out_features, dtype=x.dtype, device=x.device)
+    proj._ensure_layout()
+    svdq_gemm_mxfp4(qx, proj.qweight, ascales, proj.wscales, out=output, lora_act_in=lora_act if proj.rank else None,
+                    lora_up=proj.proj_up if proj.rank else None, bias=proj.bias, lora_scales=proj.lora_scales, rows=M,
+                    norm_q=None if norm_q is None else norm_q.weight, norm_k=None if norm_k is None else norm_k.weight,
+                    rotary_emb=None if rotary_emb is None else rotary_emb.reshape(-1, rotary_emb.shape[-1]), out_vt=out_vt, q_scale=q_scale)
     return output.view(B, S, -1)
 
 

@@ -72,7 +72,9 @@ def gemm_awq_multi(x: T, weights, mode: str = "concat", out: T | None = None) ->
 def svdq_gemm_mxfp4(act: T, wgt: T, ascales: T, wscales: T, out: T | None = None, lora_act_in: T | None = None, lora_up: T | None = None,
                     bias: T | None = None, lora_scales: list[float] | None = None, rows: int | None = None,
                     qout: T | None = None, oscales: T | None = None, lora_down: T | None = None, lora_act_out: T | None = None,
-                    smooth_factor: T | None = None, lora_act_zeroed: bool = False) -> T | None:
+                    smooth_factor: T | None = None, lora_act_zeroed: bool = False,
+                    norm_q: T | None = None, norm_k: T | None = None, rotary_emb: T | None = None, out_vt: T | None = None,
+                    q_scale: float = 0.0) -> T | None:
     """MXFP4 W4A4 GEMM, plain epilogue: ``out[:rows] = A4 W4^T`` with both E8M0 block scales ``+ round16(lora_act_in * lora_scales) lora_up^T + bias``,
     one rounding to the 16-bit dtype of ``lora_up`` / ``bias`` / ``out`` (bfloat16 when none is given).  ``act`` / ``ascales`` as
     :func:`ops.quantize.svdq_quantize_mxfp4` returns them, ``wgt`` ``[N, K/2]``, ``wscales`` uint8 ``[K/32, N]``; ``rows``: the valid rows M
@@ -83,11 +85,20 @@ def svdq_gemm_mxfp4(act: T, wgt: T, ascales: T, wscales: T, out: T | None = None
     ``svdq_quantize_mxfp4(g, lora_down=lora_down, smooth=smooth_factor)`` returns -- codes and scales bit for bit, the operands of the next
     ``svdq_gemm_mxfp4`` as they are.  ``lora_act_out`` is summed over the N/128 column tiles with fp32 atomics: for N > 128 it (and the next GEMM's
     output through it) depends on the order of the adds; it is cleared first unless ``lora_act_zeroed``.  ``out``, if given, receives ``g``
-    (no ``out`` is allocated in this mode); returns ``out``."""
+    (no ``out`` is allocated in this mode); returns ``out``.
+
+    With ``rotary_emb`` (float32 ``[M_pad, 128]`` in ``pack_rotemb`` order) and ``norm_q`` / ``norm_k`` (``[128]``) the RMSNorm + RoPE epilogue of
+    a QKV projection runs, ``N = 3 * heads * 128``, keywords as in :func:`svdq_gemm_w4a4_cuda`: per head, the Q and K thirds are
+    ``rope(h * rsqrt(mean(h^2) + 1e-6) * norm)`` of that fp32 sum ``h`` with one rounding, Q times ``q_scale`` before it (0 = off); the V third
+    is the plain output, and with ``out_vt`` (``[N/3, tokens]``, rows on 16 bytes) it is written transposed there instead of into ``out``.
+    These keywords together with ``qout`` raise ``ValueError``."""
+    if qout is not None and any(t is not None for t in (norm_q, norm_k, rotary_emb, out_vt)):
+        raise ValueError("svdq_gemm_mxfp4: norm_q, norm_k, rotary_emb and out_vt (the RMSNorm+RoPE epilogue) do not combine with qout (GELU_QUANT)")
     M = act.shape[0] if rows is None else int(rows)
     if out is None and qout is None:
         ref = lora_up if lora_up is not None else bias
         out = torch.empty(M, wgt.shape[0], dtype=torch.bfloat16 if ref is None else ref.dtype, device=act.device)
     ops.gemm_mxfp4(act, wgt, out, ascales, wscales, lora_act_in, lora_up, bias, lora_scales, M,
-                   qout=qout, oscales=oscales, lora_down=lora_down, lora_act_out=lora_act_out, smooth_factor=smooth_factor, lora_act_zeroed=lora_act_zeroed)
+                   qout=qout, oscales=oscales, lora_down=lora_down, lora_act_out=lora_act_out, smooth_factor=smooth_factor, lora_act_zeroed=lora_act_zeroed,
+                   norm_q=norm_q, norm_k=norm_k, rotary_emb=rotary_emb, out_vt=out_vt, q_scale=q_scale)
     return out

@@ -2,12 +2,15 @@
 svdq_quantize_mxfp4 vs svdq_quantize_w4a4_act_fuse_lora.  One process on one device; every arm is captured into a graph of `--launches`
 launches and replayed (a timed window is 2 to 17 ms), the arms alternate, the figure is the median over `--rounds` replays per launch.  `--mlp`
 times fc1 of an MLP instead (M 4608, K 3072, N 12288): (a) the MXFP4 GELU_QUANT launch, (b) what produces the same operands without it -- plain
-svdq_gemm_mxfp4, torch's tanh GELU, svdq_quantize_mxfp4 with fc2's lora_down and smooth -- and (c) the INT4 GELU_QUANT launch.  At every
+svdq_gemm_mxfp4, torch's tanh GELU, svdq_quantize_mxfp4 with fc2's lora_down and smooth -- and (c) the INT4 GELU_QUANT launch.  `--qkv` times
+a QKV projection (M 4608, K 3072, N 9216): (a) the MXFP4 RMSNorm + RoPE launch with out_vt and q_scale, (b) plain svdq_gemm_mxfp4 plus the torch
+ops for the per-head norm, the rotation and the V transpose, (c) the INT4 RMSNORM_ROPE launch.  At every
 timed GEMM shape the MXFP4 output is also compared with the fp32 product of the dequantised operands (`mxfp4_max_err_over_max_ref`; the INT4 arm
 is only checked to be finite: its operands are another format, its result another number).  Prints one JSON line per row.
 
     python tools/bench_mxfp4_gemm.py [--rounds 15] [--launches 100] > profiles/mxfp4_gemm.txt
     python tools/bench_mxfp4_gemm.py --mlp > profiles/mxfp4_gelu_quant.txt
+    python tools/bench_mxfp4_gemm.py --qkv > profiles/mxfp4_qkv.txt
 
 Not measured here: hardware counters (a run of their own), end-to-end models (no model class runs MXFP4).
 """
@@ -119,15 +122,73 @@ def mlp(a):
     print(json.dumps(row), flush=True)
 
 
+QKV_SHAPE = (4608, 3072, 9216)  # (M, K, N): 24 heads
+
+
+def qkv(a):
+    from nunchaku_amd.models.embeddings import pack_rotemb
+    from nunchaku_amd.ops import svdq_gemm_mxfp4
+    from nunchaku_amd.ops.gemm import svdq_gemm_w4a4_cuda
+
+    M, K, N = QKV_SHAPE
+    int4, mx = layers(K, N)
+    for lin in (int4, mx):
+        lin._ensure_layout()
+    dev, H = torch.device("cuda"), N // 384
+    x = torch.randn(M, K, device=dev).bfloat16()
+    qi, qm = int4.quantize(x), mx.quantize(x)
+    ang = torch.rand(M, 64, device=dev) * 6.283185
+    nat = torch.stack([ang.sin(), ang.cos()], dim=-1)  # [M, 64, (sin, cos)]
+    rot = pack_rotemb(nat.reshape(1, M, 64, 1, 2)).reshape(M, 128)
+    nq, nk = (torch.rand(128, device=dev) + 0.5).bfloat16(), (torch.rand(128, device=dev) + 0.5).bfloat16()
+    out, out_i, hid = (torch.empty(M, N, dtype=torch.bfloat16, device=dev) for _ in range(3))
+    vt, vt_i, vt_u = (torch.empty(N // 3, M, dtype=torch.bfloat16, device=dev) for _ in range(3))
+    common = dict(lora_act_in=qm[2], lora_up=mx.proj_up, bias=mx.bias, rows=M)
+    sin, cos = nat[None, :, :, 0], nat[None, :, :, 1]  # [1, M, 64]
+
+    def fused():
+        svdq_gemm_mxfp4(qm[0], mx.qweight, qm[1], mx.wscales, out=out, norm_q=nq, norm_k=nk, rotary_emb=rot, out_vt=vt, q_scale=0.125, **common)
+
+    def unfused():  # the 16-bit torch ops a caller without the epilogue runs: per-head RMSNorm, rotation, the V^T copy attention reads
+        svdq_gemm_mxfp4(qm[0], mx.qweight, qm[1], mx.wscales, out=hid, **common)
+        res = []
+        for third, w, s in ((hid[:, :N // 3], nq, 0.125), (hid[:, N // 3:2 * N // 3], nk, 1.0)):
+            t = third.view(M, H, 128).float()
+            t = (t * torch.rsqrt(t.pow(2).mean(-1, keepdim=True) + 1e-6) * (w.float() * s)).view(M, H, 64, 2).permute(1, 0, 2, 3)
+            res.append(torch.stack([t[..., 0] * cos - t[..., 1] * sin, t[..., 0] * sin + t[..., 1] * cos], dim=-1).bfloat16())
+        vt_u.copy_(hid[:, 2 * N // 3:].t())
+        return res  # [H, M, 64, 2] each
+
+    def int4_fused():  # as ops.fused.fused_qkv_norm_rottary launches it
+        svdq_gemm_w4a4_cuda(act=qi[0], wgt=int4.qweight, out=out_i, ascales=qi[1], wscales=int4.wscales, lora_act_in=qi[2], lora_up=int4.proj_up, bias=int4.bias,
+                            norm_q=nq, norm_k=nk, rotary_emb=rot, out_vt=vt_i, lora_scales=getattr(int4, "lora_scales", None), q_scale=0.125)
+
+    fused()
+    ref = unfused()  # rounds the projection to bf16 before the norm, the fused launch does not: a few bf16 spacings apart at most
+    got = out.view(M, 3, H, 64, 2).permute(1, 2, 0, 3, 4).float()
+    err = max(float((got[i] - ref[i].float()).abs().max() / ref[i].float().abs().max()) for i in range(2))
+    assert err < 2.0 ** -5 and torch.equal(vt, vt_u), err
+    arms = {"mxfp4_fused": captured(fused, a.launches), "mxfp4_gemm_torch_norm_rope_vt": captured(unfused, a.launches), "int4_fused": captured(int4_fused, a.launches)}
+    med, span = alternate(arms, a.rounds, a.launches)
+    row = {"op": "qkv_rmsnorm_rope", "M": M, "K": K, "N": N, "max_err_over_max_ref_vs_unfused": round(err, 5), "vt_equal_to_unfused": True}
+    for k in arms:
+        row[k + "_us"], row[k + "_min_max_us"] = round(med[k], 2), [round(v, 2) for v in span[k]]
+    row["fused_over_unfused"], row["fused_over_int4"] = round(med["mxfp4_fused"] / med["mxfp4_gemm_torch_norm_rope_vt"], 3), round(med["mxfp4_fused"] / med["int4_fused"], 3)
+    print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--launches", type=int, default=100)
     ap.add_argument("--mlp", action="store_true")
+    ap.add_argument("--qkv", action="store_true")
     a = ap.parse_args()
     print(json.dumps({"device": torch.cuda.get_device_name(0), "rounds": a.rounds, "launches_per_replay": a.launches, "rank": RANK, "dtype": "bf16"}))
     if a.mlp:
         return mlp(a)
+    if a.qkv:
+        return qkv(a)
     for M, K, N in GEMM_SHAPES:
         int4, mx = layers(K, N)
         x = torch.randn(M, K, device="cuda").bfloat16()
