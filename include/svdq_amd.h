@@ -1538,6 +1538,50 @@ typedef struct svdq_gemm_mxfp4_qkv_args {
 } svdq_gemm_mxfp4_qkv_args;
 int svdq_gemm_mxfp4_qkv(const svdq_gemm_mxfp4_qkv_args *args, void *stream);
 
+/* svdq_gemm_mxfp4_glu_quant (appended like the four above: no version bump): the gated projection of a SwiGLU / GEGLU feed-forward whose second
+ * projection is MXFP4 too.  N = 2 * Hd: weight rows (and bias, wscales, lora_up rows) [0, Hd) are the value half, rows [Hd, 2 Hd) the gate half
+ * (diffusers' chunk(2, -1)); the ONE weight image of svdq_gemm_mxfp4 is read, the pairing of row c with row Hd + c happens in the kernel.  With
+ *   h32 = the fp32 sum svdq_gemm_mxfp4 rounds (product + low-rank term + bias[weight row]), no intermediate rounding,
+ *   v16 = round16(h32[m, c]),  g16 = round16(h32[m, Hd + c])     bit-equal to the columns svdq_gemm_mxfp4 writes
+ *   a   = round16(act(float(g16)))                               act_fn: SVDQ_GLU_SILU | SVDQ_GLU_GELU_ERF, the fp32 expressions of svdq_quantize_glu_halves
+ *   x   = round16(float(v16) * a)                                the 16-bit multiply; rows M .. M_pad - 1 count as zeros
+ * -- svdq_quantize_glu_halves's rounding points on svdq_gemm_mxfp4's output -- it writes what svdq_quantize_mxfp4(x, smooth_next, lora_down) would,
+ * bit for bit in the codes and scales:
+ *   qout / oscales   the block rule above on round16(x * rcp(smooth_next)): qout [M_pad][Hd/2], oscales uint32 [Hd/128][M_pad] -- the act / ascales
+ *                    operands of the next svdq_gemm_mxfp4 (K = Hd).  A workgroup owns 64 channels: 32 code bytes a row and one 16-bit half of a
+ *                    scale dword, which the neighbouring column tile completes.
+ *   lora_act_out     += x @ lora_down (un-smoothed x, fp32).  The Hd / 64 column tiles of a row block meet in fp32 atomics: the buffer must be
+ *                    zero before the launch -- cleared here by a small kernel unless lora_act_zeroed -- and for Hd > 64 the sums (and through
+ *                    them the next GEMM's output) depend on the order of the adds.  Codes, scales and out never do.
+ *   out              optional: x itself, 16-bit [M, ldo] (only columns < Hd of rows < M are written).
+ * M_pad / 256 * Hd / 64 workgroups (the padding rows of qout / oscales are written, as zeros).  Validation as for svdq_gemm_mxfp4 (out and ldo
+ * only when out is given, ldo >= Hd), and SVDQ_E_INVALID for: N not a multiple of 256 (Hd % 128 != 0); an unknown act_fn; qout or oscales NULL;
+ * R_next not a multiple of 16 in [0, 256]; lora_down and lora_act_out not both or neither, or not exactly when R_next > 0.  Alignment: qout,
+ * lora_down 16 bytes; smooth_next 8; oscales, lora_act_out 4.  Addressing reach: that of svdq_gemm_mxfp4 (the outputs are addressed in 64 bits). */
+typedef struct svdq_gemm_mxfp4_glu_quant_args {
+    const void *act;          /* as svdq_gemm_mxfp4_args, through lora_scales; N = 2 * Hd     */
+    const void *wgt;
+    const void *ascales;
+    const void *wscales;
+    const void *bias;
+    const void *lora_act_in;
+    const void *lora_up;
+    const float *lora_scales;
+    void *out;                /* [M, Hd] 16-bit x, row stride ldo elements, or NULL           */
+    void *qout;               /* out: [M_pad][Hd/2] bytes                                     */
+    void *oscales;            /* out: uint32 [Hd/128][M_pad]                                  */
+    const void *smooth_next;  /* [Hd] 16-bit, natural order; NULL = ones                      */
+    const void *lora_down;    /* next layer: [R_next][Hd] 16-bit, rank-major; NULL if R_next == 0 */
+    void *lora_act_out;       /* [M_pad][R_next] fp32; NULL if R_next == 0                    */
+    int32_t M, M_pad, N, K, R;
+    int32_t R_next;
+    int32_t ldo;              /* with out: >= Hd, a multiple of 4                             */
+    int32_t dtype;            /* SVDQ_BF16 | SVDQ_FP16                                        */
+    int32_t act_fn;           /* SVDQ_GLU_SILU | SVDQ_GLU_GELU_ERF                            */
+    int32_t lora_act_zeroed;  /* non-zero: lora_act_out is already zero on this stream        */
+} svdq_gemm_mxfp4_glu_quant_args;
+int svdq_gemm_mxfp4_glu_quant(const svdq_gemm_mxfp4_glu_quant_args *args, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Load-time re-layout of reference checkpoint tensors (NVIDIA fragment order -> CDNA4 order).
  * src and dst must not alias.  All but svdq_repack_qweight (4 -> 6 bits per code) and svdq_repack_wscales (x 32) are pure permutations of equal size.

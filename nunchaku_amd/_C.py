@@ -648,7 +648,7 @@ class _Ops:
     @staticmethod
     def gemm_mxfp4(act, wgt, out, ascales, wscales, lora_act_in=None, lora_up=None, bias=None, lora_scales=None, rows=None,
                    qout=None, oscales=None, lora_down=None, lora_act_out=None, smooth_factor=None, lora_act_zeroed=False,
-                   norm_q=None, norm_k=None, rotary_emb=None, out_vt=None, q_scale=0.0):
+                   norm_q=None, norm_k=None, rotary_emb=None, out_vt=None, q_scale=0.0, glu=None):
         """MXFP4 W4A4 GEMM with the plain epilogue (``svdq_gemm_mxfp4``): ``act`` uint8 ``[M_pad, K/2]`` and ``ascales`` ``[K/128, M_pad, 4]`` as
         :meth:`quantize_mxfp4` writes them; ``wgt`` uint8 / int8 ``[N, K/2]``; ``wscales`` uint8 ``[K/32, N]`` (checkpoint layout, packed once per
         parameter) or marked as kernel layout (``[K/128, N, 4]`` behind the same shape); ``out`` 16-bit ``[M, N]`` with any row stride that is a
@@ -663,9 +663,22 @@ class _Ops:
         (``svdq_gemm_mxfp4_qkv``, ``N = 3 * H * 128``), admitted and refused as :meth:`gemm_w4a4` does for the INT4 one: it needs ``out``, ``norm_q``
         and ``norm_k`` (``[128]`` in the dtype of ``out``); ``out_vt`` (``[N/3, tokens]``, unit column stride, 16-byte aligned rows) receives V
         transposed instead of the V columns of ``out``; ``q_scale``: the Q third times this factor before its rounding (0 = off).  Without
-        ``rotary_emb`` the norm weights and ``q_scale`` are not looked at and ``out_vt`` is refused."""
+        ``rotary_emb`` the norm weights and ``q_scale`` are not looked at and ``out_vt`` is refused.
+
+        With ``glu`` (``"silu"`` or ``"gelu"``, the erf form) and ``qout`` the GLU_QUANT epilogue of a gated projection runs
+        (``svdq_gemm_mxfp4_glu_quant``): ``wgt`` is ``[2 * Hd, K/2]``, value rows first (``bias`` ``[2 * Hd]``, ``lora_up`` ``[2 * Hd, R]``), and
+        ``x = value * act(gate)`` is what gets quantised: ``qout`` ``[M_pad, Hd/2]``, ``oscales`` ``[Hd/128, M_pad, 4]``, ``out`` (optional)
+        ``[M, Hd]``, ``smooth_factor`` ``[Hd]``, ``lora_down`` ``[Hd, R_next]``.  ``glu`` without ``qout``, or together with ``norm_q`` / ``norm_k``
+        / ``rotary_emb`` / ``out_vt``, is refused."""
         op, lib = "gemm_mxfp4", _lib.load()
         fused, qkv = qout is not None, rotary_emb is not None
+        if glu is not None:
+            if glu not in ("silu", "gelu"):
+                raise ValueError(f"{op}: glu={glu!r} (one of 'silu', 'gelu')")
+            if not fused:
+                raise ValueError(f"{op}: glu= (the GLU_QUANT epilogue) needs qout and oscales")
+            if qkv or norm_q is not None or norm_k is not None or out_vt is not None:
+                raise ValueError(f"{op}: norm_q, norm_k, rotary_emb and out_vt (the RMSNorm+RoPE epilogue) do not combine with glu= (GLU_QUANT)")
         if fused and (qkv or norm_q is not None or norm_k is not None or out_vt is not None):
             raise ValueError(f"{op}: norm_q, norm_k, rotary_emb and out_vt (the RMSNorm+RoPE epilogue) do not combine with qout (GELU_QUANT)")
         if out_vt is not None and not qkv:
@@ -691,8 +704,11 @@ class _Ops:
         M = out.shape[0] if rows is None else int(rows)
         if K % 128 or N % 128:
             raise ValueError(f"{op}: K={K} and N={N} must be multiples of 128")
-        if out is not None and (out.shape[0] < M or out.shape[1] != N):
-            raise ValueError(f"{op}: out must be [>= M, N]")
+        if glu is not None and N % 256:
+            raise ValueError(f"{op}: with glu= the weight is [2 * Hd, K/2] with Hd a multiple of 128, got {N} rows")
+        Nq = N // 2 if glu is not None else N  # the columns of out, and the K of the next GEMM: Hd under GLU_QUANT
+        if out is not None and (out.shape[0] < M or out.shape[1] != Nq):
+            raise ValueError(f"{op}: out must be [>= M, {'Hd' if glu is not None else 'N'}]")
         if ascales.dtype != torch.uint8 or ascales.numel() != (K // 32) * M_pad:
             raise ValueError(f"{op}: ascales must hold (K/32)*M_pad bytes")
         if wscales.dtype != torch.uint8 or wscales.numel() != (K // 32) * N:
@@ -709,20 +725,20 @@ class _Ops:
         if fused:
             if oscales is None:
                 raise ValueError(f"{op}: qout needs oscales")
-            if qout.dtype != torch.uint8 or qout.dim() != 2 or tuple(qout.shape) != (M_pad, N // 2) or not qout.is_contiguous():
-                raise ValueError(f"{op}: qout must be contiguous uint8 [M_pad, N/2] = [{M_pad}, {N // 2}]")
-            if oscales.dtype != torch.uint8 or oscales.numel() != (N // 32) * M_pad or not oscales.is_contiguous():
+            if qout.dtype != torch.uint8 or qout.dim() != 2 or tuple(qout.shape) != (M_pad, Nq // 2) or not qout.is_contiguous():
+                raise ValueError(f"{op}: qout must be contiguous uint8 [M_pad, N/2] = [{M_pad}, {Nq // 2}]")
+            if oscales.dtype != torch.uint8 or oscales.numel() != (Nq // 32) * M_pad or not oscales.is_contiguous():
                 raise ValueError(f"{op}: oscales must hold (N/32)*M_pad bytes")
             if (lora_down is None) != (lora_act_out is None):
                 raise ValueError(f"{op}: lora_down and lora_act_out come together or not at all")
             R_next = 0 if lora_down is None else lora_down.shape[-1]
             if R_next % 16 or R_next > 256:
                 raise ValueError(f"{op}: the next layer's rank R_next={R_next} must be a multiple of 16 up to 256")
-            if R_next and (lora_down.dtype != dtype or lora_down.numel() != N * R_next):
+            if R_next and (lora_down.dtype != dtype or lora_down.numel() != Nq * R_next):
                 raise ValueError(f"{op}: lora_down must be [N, R_next] in the 16-bit dtype of the launch")
             if R_next and (lora_act_out.dtype != torch.float32 or lora_act_out.numel() != M_pad * R_next or not lora_act_out.is_contiguous()):
                 raise ValueError(f"{op}: lora_act_out must hold M_pad*R_next float32")
-            if smooth_factor is not None and (smooth_factor.numel() != N or smooth_factor.dtype != dtype):
+            if smooth_factor is not None and (smooth_factor.numel() != Nq or smooth_factor.dtype != dtype):
                 raise ValueError(f"{op}: smooth_factor must be [N] in the 16-bit dtype of the launch")
             if R_next and not getattr(lora_down, "_svdq_amd", False):
                 lora_down = _cached_conversion(lora_down, "mxfp4_down", lambda src: src.t().contiguous())
@@ -743,7 +759,8 @@ class _Ops:
                     raise ValueError(f"{op}: out_vt must start on 16 bytes with a row stride that is a multiple of 8")
         if not getattr(wscales, "_svdq_amd", False):
             wscales = _cached_conversion(wscales, "mxfp4_wscales", lambda src: src.reshape(K // 128, 4, N).permute(0, 2, 1).contiguous())
-        a = _lib.ARGS["svdq_gemm_mxfp4_gelu_quant_args" if fused else "svdq_gemm_mxfp4_qkv_args" if qkv else "svdq_gemm_mxfp4_args"]()
+        a = _lib.ARGS["svdq_gemm_mxfp4_glu_quant_args" if glu is not None else "svdq_gemm_mxfp4_gelu_quant_args" if fused
+                      else "svdq_gemm_mxfp4_qkv_args" if qkv else "svdq_gemm_mxfp4_args"]()
         a.act, a.wgt, a.ascales, a.wscales, a.bias = _ptr(act), _ptr(wgt), _ptr(ascales), _ptr(wscales), _ptr(bias)
         a.out = None if out is None else _ptr(out, laid_out=True)
         if R:
@@ -753,14 +770,18 @@ class _Ops:
             scales = (C.c_float * (R // 16))(*[float(v) for v in lora_scales[:R // 16]])
             a.lora_scales = scales
         a.M, a.M_pad, a.N, a.K, a.R = _i32(op, "M", M), _i32(op, "M_pad", M_pad), _i32(op, "N", N), _i32(op, "K", K), _i32(op, "R", R)
-        a.ldo = _i32(op, "out.stride(0)", N if out is None else out.stride(0))
+        a.ldo = _i32(op, "out.stride(0)", Nq if out is None else out.stride(0))
         a.dtype = _DT[dtype]
         if fused:
             a.qout, a.oscales, a.smooth_next = _ptr(qout), _ptr(oscales), _ptr(smooth_factor)
             if R_next:
                 a.lora_down, a.lora_act_out = _ptr(lora_down), _ptr(lora_act_out)
             a.R_next, a.lora_act_zeroed = _i32(op, "R_next", R_next), int(bool(lora_act_zeroed))
-            _lib.check(lib.svdq_gemm_mxfp4_gelu_quant(C.byref(a), _stream()), op)
+            if glu is not None:
+                a.act_fn = _lib.GLU_SILU if glu == "silu" else _lib.GLU_GELU_ERF
+                _lib.check(lib.svdq_gemm_mxfp4_glu_quant(C.byref(a), _stream()), op)
+            else:
+                _lib.check(lib.svdq_gemm_mxfp4_gelu_quant(C.byref(a), _stream()), op)
         elif qkv:
             a.norm_q, a.norm_k, a.rotary_emb, a.q_scale = _ptr(norm_q), _ptr(norm_k), _ptr(rotary_emb), float(q_scale)
             if out_vt is not None:

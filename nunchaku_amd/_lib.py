@@ -144,12 +144,22 @@ def _mxfp4_args():
             ("ldo", C.c_int32), ("dtype", C.c_int32), ("ldvt", C.c_int32), ("q_scale", C.c_float), ("reserved", C.c_int32),
         ]
 
-    return QuantizeMxfp4Args, GemmMxfp4Args, GemmMxfp4GeluQuantArgs, GemmMxfp4QkvArgs
+    class GemmMxfp4GluQuantArgs(C.Structure):
+        """svdq_gemm_mxfp4_glu_quant_args"""
+        _fields_ = [
+            ("act", C.c_void_p), ("wgt", C.c_void_p), ("ascales", C.c_void_p), ("wscales", C.c_void_p), ("bias", C.c_void_p),
+            ("lora_act_in", C.c_void_p), ("lora_up", C.c_void_p), ("lora_scales", C.POINTER(C.c_float)), ("out", C.c_void_p),
+            ("qout", C.c_void_p), ("oscales", C.c_void_p), ("smooth_next", C.c_void_p), ("lora_down", C.c_void_p), ("lora_act_out", C.c_void_p),
+            ("M", C.c_int32), ("M_pad", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("R", C.c_int32), ("R_next", C.c_int32),
+            ("ldo", C.c_int32), ("dtype", C.c_int32), ("act_fn", C.c_int32), ("lora_act_zeroed", C.c_int32),
+        ]
+
+    return QuantizeMxfp4Args, GemmMxfp4Args, GemmMxfp4GeluQuantArgs, GemmMxfp4QkvArgs, GemmMxfp4GluQuantArgs
 
 
 # (ldx / ldo / ldvt: unbounded, 64-bit row addresses; reached through the table like the structs above)
 (ARGS["svdq_quantize_mxfp4_args"], ARGS["svdq_gemm_mxfp4_args"], ARGS["svdq_gemm_mxfp4_gelu_quant_args"],
- ARGS["svdq_gemm_mxfp4_qkv_args"]) = _mxfp4_args()
+ ARGS["svdq_gemm_mxfp4_qkv_args"], ARGS["svdq_gemm_mxfp4_glu_quant_args"]) = _mxfp4_args()
 
 
 class ResidualArgs(C.Structure):
@@ -369,6 +379,7 @@ EXPORTS = {
     "svdq_gemm_mxfp4": (C.c_int, [C.POINTER(ARGS["svdq_gemm_mxfp4_args"]), C.c_void_p]),
     "svdq_gemm_mxfp4_gelu_quant": (C.c_int, [C.POINTER(ARGS["svdq_gemm_mxfp4_gelu_quant_args"]), C.c_void_p]),
     "svdq_gemm_mxfp4_qkv": (C.c_int, [C.POINTER(ARGS["svdq_gemm_mxfp4_qkv_args"]), C.c_void_p]),
+    "svdq_gemm_mxfp4_glu_quant": (C.c_int, [C.POINTER(ARGS["svdq_gemm_mxfp4_glu_quant_args"]), C.c_void_p]),
     "svdq_attention": (C.c_int, [C.POINTER(AttentionArgs), C.c_void_p]),
     "svdq_gemv_awq": (C.c_int, [C.POINTER(GemvAwqArgs), C.c_void_p]),
     "svdq_gemv_awq_batched": (C.c_int, [C.POINTER(GemvAwqArgs), C.c_int32, C.c_void_p]),

@@ -17,8 +17,11 @@
 // svdq_gemm_mxfp4_gelu_quant: the same loop (gemm_mxfp4_loop.inc) under the GELU_QUANT epilogue -- GELU, the MXFP4 requantisation for the next
 // layer and that layer's low-rank down projection (gemm_mxfp4_gelu_quant_kernel below).
 // svdq_gemm_mxfp4_qkv: the same loop under the RMSNorm + RoPE epilogue of a QKV projection, V optionally transposed (gemm_mxfp4_qkv_kernel below).
+// svdq_gemm_mxfp4_glu_quant: the same loop under the GLU_QUANT epilogue of a gated projection, N = 2 Hd -- a workgroup's 128 tile columns are 64
+// value rows and the 64 gate rows Hd further down the weight (gemm_mxfp4_glu_quant_kernel below).
 #include <type_traits>
 
+#include "glu_act.h"
 #include "mxfp4_block.h"
 
 namespace svdq {
@@ -381,7 +384,153 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp4_qkv_kernel(Mxfp4QkvParams p
     }
 }
 
-// clears lora_act_out ahead of the GELU_QUANT launch (a kernel, not hipMemsetAsync: the launch may be recorded into a graph)
+// ---- the GLU_QUANT variant: the gated projection of a SwiGLU / GEGLU feed-forward, weight [2 Hd][K] with the value half in rows [0, Hd) and the
+// gate half in rows [Hd, 2 Hd) (p.N = 2 Hd).  Same loop, same low-rank-up MFMAs, but the workgroup's 128 tile columns are PAIRED (MX_WBASE, MX_WSKIP):
+// accumulator tiles ni = 0, 1 are value rows 64 bn .. 64 bn + 63, tiles ni = 2, 3 the gate rows Hd + 64 bn .. Hd + 64 bn + 63, so value c and gate c
+// of a row are the same element of tiles ni and ni + 2 of the same lane: the product crosses no lane and needs no LDS.  With h32 = acc + bias
+// (the bias by weight row):
+//   v16 = round16(h32 value), g16 = round16(h32 gate)     the plain kernel's output columns
+//   a = round16(act(g16)),  x = round16(v16 * a)           act = glu_silu | glu_gelu (glu_act.h): svdq_quantize_glu_halves's rounding points; rows >= M: 0
+//   the MXFP4 block quantiser on round16(x * rcp(smooth_next))   -> qout [M_pad][Hd / 2], oscales [Hd / 128][M_pad] dwords; x -> out (OUT16)
+//   lora_act_out[m, :] += x[m, 64 bn .. 64 bn + 63] @ down_next[64 bn .. 64 bn + 63, :]    (fp32 atomics, the last thing issued)
+// The 64 x-channels of a workgroup are HALF a K-step of the next GEMM: 32 code bytes a row (one 16-byte store a lane: half h keeps block h) and two
+// of the four scale bytes of dword (bn >> 1, m) -- one 16-bit store into half bn & 1 of it; the neighbouring tile completes the dword.
+// A block nb takes tiles nb and nb + 2 out of the accumulator and leaves 8 packed registers a row tile: every finished block frees 48 of 64.
+template <int DT, int ACT, bool OUT16>
+__global__ __launch_bounds__(256, 2) void gemm_mxfp4_glu_quant_kernel(Mxfp4GeluQuantParams p) {
+    using T = typename Half<DT>::T;
+    using V8 = typename Half<DT>::V8;
+    const int Hd = p.N >> 1;
+#define MX_WBASE (bn * 64)
+#define MX_WSKIP(c) (((c) >> 6) ? Hd - 64 : 0)
+#include "gemm_mxfp4_loop.inc"
+    const int mw0 = m0 + wave * 64; // the wave's rows mw0 + 32 mi + r, all < M_pad
+    const int c0 = bn * 64 + 4 * h; // the lane's x channels: c0 + 32 nb + 8 g + e
+    unsigned xp[2][2][8];           // x, two 16-bit values a register in the accumulator's order
+    unsigned pc[2][2][2], sb2[2] = {0, 0};
+#pragma unroll
+    for (int nb = 0; nb < 2; nb++) {
+        if (p.bias) { // value and gate bias of the lane's 16 channels of block nb: h32
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const u16x4 bv = *reinterpret_cast<const u16x4 *>((const T *)p.bias + c0 + 32 * nb + 8 * g);
+                const u16x4 bg = *reinterpret_cast<const u16x4 *>((const T *)p.bias + Hd + c0 + 32 * nb + 8 * g);
+#pragma unroll
+                for (int e = 0; e < 4; e++)
+#pragma unroll
+                    for (int mi = 0; mi < 2; mi++) {
+                        acc[nb][mi][4 * g + e] += h2f(hfrom<T>(bv[e]));
+                        acc[nb + 2][mi][4 * g + e] += h2f(hfrom<T>(bg[e]));
+                    }
+            }
+        }
+        float rs[16]; // 1 / smooth_next; without smoothing rcp(1) = 1 exactly and x * 1 = x, the quantiser's un-smoothed path
+#pragma unroll
+        for (int i = 0; i < 16; i++) rs[i] = 1.0f;
+        if (p.smooth_next) {
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const u16x4 sv = *reinterpret_cast<const u16x4 *>((const T *)p.smooth_next + c0 + 32 * nb + 8 * g);
+#pragma unroll
+                for (int e = 0; e < 4; e++) rs[4 * g + e] = __builtin_amdgcn_rcpf(h2f(hfrom<T>(sv[e])));
+            }
+        }
+#pragma unroll
+        for (int mi = 0; mi < 2; mi++) {
+            const bool live = mw0 + mi * 32 + r < p.M; // a padding row holds bias * act(bias): cut to zero, as the quantiser leaves it
+            float v[16], amax = 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; i += 2) {
+                const f32x2_t v16 = round16_pair<T>(acc[nb][mi][i], acc[nb][mi][i + 1]);
+                const f32x2_t g16 = round16_pair<T>(acc[nb + 2][mi][i], acc[nb + 2][mi][i + 1]);
+                f32x2_t a;
+                if constexpr (ACT == SVDQ_GLU_SILU) a = round16_pair<T>(glu_silu(g16[0]), glu_silu(g16[1]));
+                else a = round16_pair<T>(glu_gelu(g16[0]), glu_gelu(g16[1]));
+                f32x2_t t = round16_pair<T>(v16[0] * a[0], v16[1] * a[1]); // (the product of two 16-bit values is exact in fp32: one rounding)
+                if (!live) t = f32x2_t{0.f, 0.f};
+                xp[nb][mi][i >> 1] = (unsigned)hbits(f2h<T>(t[0])) | (unsigned)hbits(f2h<T>(t[1])) << 16; // (exact: t is a 16-bit value)
+                asm volatile("" : "+v"(xp[nb][mi][i >> 1])); // (pinned here, as g in the GELU_QUANT kernel: sunk to its use, the pack keeps both fp32 values alive)
+#pragma unroll
+                for (int e = 0; e < 2; e++) {
+                    v[i + e] = smooth_div16<T>(t[e], rs[i + e]);
+                    amax = mx_amax_acc(amax, v[i + e]);
+                }
+            }
+            const unsigned sb = mx_block_byte<T>(amax);
+            MX_BLOCK_CODES(v, sb, pc[mi][nb]);
+            sb2[mi] |= sb << (8 * nb);
+            if constexpr (OUT16) {
+                if (live) {
+                    T *orow = (T *)p.out + (size_t)(mw0 + mi * 32 + r) * p.ldo + c0 + 32 * nb;
+#pragma unroll
+                    for (int g = 0; g < 4; g++) *reinterpret_cast<uint2 *>(orow + 8 * g) = make_uint2(xp[nb][mi][2 * g], xp[nb][mi][2 * g + 1]);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0); // one (block, row tile) at a time, as in the GELU_QUANT kernel
+        }
+    }
+    // the row's 32 code bytes: the halves trade pieces so that lane h keeps block h -- dword q = piece q of half 0 | piece q of half 1 << 16 (as
+    // mx_trade_halves, for two blocks) -- and stores its 16 bytes; half 0 stores the two scale bytes
+#pragma unroll
+    for (int mi = 0; mi < 2; mi++) {
+        const int m = mw0 + mi * 32 + r;
+        unsigned dw[4];
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            const unsigned own = h ? pc[mi][1][t] : pc[mi][0][t];
+            const unsigned oth = (unsigned)__shfl_xor((int)(h ? pc[mi][0][t] : pc[mi][1][t]), 32);
+            const unsigned a = h ? oth : own, bq = h ? own : oth; // a: half 0's pieces, bq: half 1's
+            dw[2 * t] = (a & 0xffffu) | (bq << 16);
+            dw[2 * t + 1] = (a >> 16) | (bq & 0xffff0000u);
+        }
+        *reinterpret_cast<uint4 *>(p.qout + (size_t)m * (Hd / 2) + bn * 32 + 16 * h) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
+        if (h == 0) reinterpret_cast<unsigned short *>(p.oscales + (size_t)(bn >> 1) * p.M_pad + m)[bn & 1] = (unsigned short)sb2[mi];
+    }
+    // the next layer's low-rank down projection on the un-smoothed x, 32 ranks a pass on the 16-bit 32x32x16 MFMA: operands, order and atomics as in
+    // the GELU_QUANT kernel, over the tile's 64 channels (two blocks x two k-slots of 16)
+    const int mws = m0 + __builtin_amdgcn_readfirstlane(wave) * 64; // = mw0, as a scalar
+    for (int t2 = 0; t2 < p.R_next; t2 += 32) {
+        const bool rank_live = t2 + r < p.R_next; // a half-filled 32-rank tile: zeros beyond R_next
+        V8 wv[2][2];
+#pragma unroll
+        for (int nb = 0; nb < 2; nb++)
+#pragma unroll
+            for (int q = 0; q < 2; q++) {
+                u16x4 w0 = {0, 0, 0, 0}, w1 = {0, 0, 0, 0};
+                if (rank_live) {
+                    const T *src = (const T *)p.down_next + (size_t)(t2 + r) * Hd + c0 + nb * 32 + q * 16;
+                    w0 = *reinterpret_cast<const u16x4 *>(src);
+                    w1 = *reinterpret_cast<const u16x4 *>(src + 8);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; j++) { wv[nb][q][j] = hfrom<T>(w0[j]); wv[nb][q][4 + j] = hfrom<T>(w1[j]); }
+            }
+        v16f d[2];
+#pragma unroll
+        for (int mi = 0; mi < 2; mi++)
+#pragma unroll
+            for (int i = 0; i < 16; i++) d[mi][i] = 0.f;
+#pragma unroll
+        for (int nb = 0; nb < 2; nb++)
+#pragma unroll
+            for (int q = 0; q < 2; q++)
+#pragma unroll
+                for (int mi = 0; mi < 2; mi++) {
+                    const V8 xv = __builtin_bit_cast(V8, v4i{(int)xp[nb][mi][4 * q], (int)xp[nb][mi][4 * q + 1], (int)xp[nb][mi][4 * q + 2], (int)xp[nb][mi][4 * q + 3]});
+                    d[mi] = Half<DT>::mfma32(xv, wv[nb][q], d[mi]);
+                }
+#pragma unroll
+        for (int mi = 0; mi < 2; mi++) {
+            if (!rank_live || mws + mi * 32 >= p.M) continue;
+            float *base = p.lora_act_out + (size_t)(mws + mi * 32) * p.R_next; // D element i: row (i & 3) + 8 (i >> 2) + 4 h, column (rank) r
+            const unsigned off = (unsigned)(4 * h * p.R_next + t2 + r);
+#pragma unroll
+            for (int i = 0; i < 16; i++) unsafeAtomicAdd(base + (size_t)((i & 3) + 8 * (i >> 2)) * p.R_next + off, d[mi][i]);
+        }
+    }
+}
+
+// clears lora_act_out ahead of the GELU_QUANT / GLU_QUANT launch (a kernel, not hipMemsetAsync: the launch may be recorded into a graph)
 static __global__ __launch_bounds__(256) void gemm_mxfp4_clear(uint32_t *dst, size_t words) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) dst[i] = 0u;
 }
@@ -390,9 +539,10 @@ static __global__ __launch_bounds__(256) void gemm_mxfp4_clear(uint32_t *dst, si
 
 using namespace svdq;
 
-// what the entries check of the fields they share (A: svdq_gemm_mxfp4_args, svdq_gemm_mxfp4_gelu_quant_args or svdq_gemm_mxfp4_qkv_args); 0 or the error code, nothing is launched.
-// `rows`: the rows the grid covers.  fills the kernel's parameters
-template <typename A> static int mx_gemm_validate(const A *a, const char *fn, bool need_out, int rows, Mxfp4GemmParams &p, long long &grid) {
+// what the entries check of the fields they share (A: svdq_gemm_mxfp4_args, svdq_gemm_mxfp4_gelu_quant_args, svdq_gemm_mxfp4_glu_quant_args or
+// svdq_gemm_mxfp4_qkv_args); 0 or the error code, nothing is launched.  `rows`: the rows the grid covers; `out_div`: `out` has N / out_div columns.
+// fills the kernel's parameters
+template <typename A> static int mx_gemm_validate(const A *a, const char *fn, bool need_out, int rows, Mxfp4GemmParams &p, long long &grid, int out_div = 1) {
     if (!a) { set_error("%s: args is NULL", fn); return SVDQ_E_INVALID; }
     if (!a->act || !a->wgt || !a->ascales || !a->wscales || (need_out && !a->out)) {
         set_error("%s: act, wgt, ascales, wscales%s are required", fn, need_out ? " and out" : ", qout and oscales");
@@ -405,7 +555,7 @@ template <typename A> static int mx_gemm_validate(const A *a, const char *fn, bo
     }
     if (a->N <= 0 || a->N % 128) { set_error("%s: N=%d must be a positive multiple of 128", fn, a->N); return SVDQ_E_INVALID; }
     if (a->K <= 0 || a->K % 128) { set_error("%s: K=%d must be a positive multiple of 128", fn, a->K); return SVDQ_E_INVALID; }
-    if (a->out && (a->ldo < a->N || a->ldo % 4)) { set_error("%s: ldo=%d must be >= N and a multiple of 4", fn, a->ldo); return SVDQ_E_INVALID; }
+    if (a->out && (a->ldo < a->N / out_div || a->ldo % 4)) { set_error("%s: ldo=%d must be >= %s and a multiple of 4", fn, a->ldo, out_div == 1 ? "N" : "N / 2"); return SVDQ_E_INVALID; }
     if (a->R < 0 || a->R % 16 || a->R > 16 * MX_MAX_LORA_TILES) { set_error("%s: R=%d must be a multiple of 16 in [0, 256]", fn, a->R); return SVDQ_E_INVALID; }
     if (a->R > 0 && (!a->lora_act_in || !a->lora_up)) { set_error("%s: R > 0 needs lora_act_in and lora_up", fn); return SVDQ_E_INVALID; }
     if (((uintptr_t)a->act | (uintptr_t)a->wgt | (uintptr_t)a->lora_act_in | (uintptr_t)a->lora_up) & 15) {
@@ -489,4 +639,41 @@ extern "C" int svdq_gemm_mxfp4_gelu_quant(const svdq_gemm_mxfp4_gelu_quant_args 
         else hipLaunchKernelGGL((gemm_mxfp4_gelu_quant_kernel<SVDQ_FP16, false>), g, b, 0, st, p);
     }
     return hip_check(hipGetLastError(), "svdq_gemm_mxfp4_gelu_quant launch");
+}
+
+extern "C" int svdq_gemm_mxfp4_glu_quant(const svdq_gemm_mxfp4_glu_quant_args *a, void *stream) {
+    const char *fn = "svdq_gemm_mxfp4_glu_quant";
+    Mxfp4GeluQuantParams p;
+    long long grid; // M_pad / 256 * N / 128 = M_pad / 256 * Hd / 64
+    if (const int rc = mx_gemm_validate(a, fn, false, a ? a->M_pad : 0, p, grid, 2)) return rc;
+    if (a->N % 256) { set_error("%s: N=%d must be 2 * Hd with Hd a multiple of 128", fn, a->N); return SVDQ_E_INVALID; }
+    if (a->act_fn != SVDQ_GLU_SILU && a->act_fn != SVDQ_GLU_GELU_ERF) { set_error("%s: unknown act_fn %d", fn, a->act_fn); return SVDQ_E_INVALID; }
+    if (!a->qout || !a->oscales) { set_error("%s: qout and oscales are required", fn); return SVDQ_E_INVALID; }
+    if (a->R_next < 0 || a->R_next % 16 || a->R_next > 256) { set_error("%s: R_next=%d must be a multiple of 16 in [0, 256]", fn, a->R_next); return SVDQ_E_INVALID; }
+    if (!a->lora_down != !a->lora_act_out) { set_error("%s: lora_down and lora_act_out come together or not at all", fn); return SVDQ_E_INVALID; }
+    if ((a->R_next > 0) != (a->lora_down != nullptr)) { set_error("%s: R_next=%d %s lora_down and lora_act_out", fn, a->R_next, a->R_next ? "needs" : "takes no"); return SVDQ_E_INVALID; }
+    if (((uintptr_t)a->qout | (uintptr_t)a->lora_down) & 15) { set_error("%s: qout and lora_down must be 16-byte aligned", fn); return SVDQ_E_INVALID; }
+    if ((uintptr_t)a->smooth_next & 7) { set_error("%s: smooth_next must be 8-byte aligned", fn); return SVDQ_E_INVALID; }
+    if (((uintptr_t)a->oscales | (uintptr_t)a->lora_act_out) & 3) { set_error("%s: oscales and lora_act_out must be 4-byte aligned", fn); return SVDQ_E_INVALID; }
+    // (addressing reach of the outputs: every row address is formed in 64 bits -- nothing beyond what the shared checks hold)
+    p.smooth_next = a->smooth_next; p.down_next = a->lora_down; p.qout = (uint8_t *)a->qout; p.oscales = (uint32_t *)a->oscales;
+    p.lora_act_out = (float *)a->lora_act_out; p.R_next = a->R_next;
+    hipStream_t st = (hipStream_t)stream;
+    if (a->R_next > 0 && !a->lora_act_zeroed) {
+        const size_t words = (size_t)a->M_pad * a->R_next, blocks = (words + 1023) / 1024;
+        hipLaunchKernelGGL(gemm_mxfp4_clear, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, (uint32_t *)a->lora_act_out, words);
+    }
+    const dim3 g((unsigned)grid), b(256);
+    const int variant = (a->dtype == SVDQ_FP16 ? 4 : 0) | (a->act_fn == SVDQ_GLU_GELU_ERF ? 2 : 0) | (a->out ? 1 : 0);
+    switch (variant) {
+    case 0: hipLaunchKernelGGL((gemm_mxfp4_glu_quant_kernel<SVDQ_BF16, SVDQ_GLU_SILU, false>), g, b, 0, st, p); break;
+    case 1: hipLaunchKernelGGL((gemm_mxfp4_glu_quant_kernel<SVDQ_BF16, SVDQ_GLU_SILU, true>), g, b, 0, st, p); break;
+    case 2: hipLaunchKernelGGL((gemm_mxfp4_glu_quant_kernel<SVDQ_BF16, SVDQ_GLU_GELU_ERF, false>), g, b, 0, st, p); break;
+    case 3: hipLaunchKernelGGL((gemm_mxfp4_glu_quant_kernel<SVDQ_BF16, SVDQ_GLU_GELU_ERF, true>), g, b, 0, st, p); break;
+    case 4: hipLaunchKernelGGL((gemm_mxfp4_glu_quant_kernel<SVDQ_FP16, SVDQ_GLU_SILU, false>), g, b, 0, st, p); break;
+    case 5: hipLaunchKernelGGL((gemm_mxfp4_glu_quant_kernel<SVDQ_FP16, SVDQ_GLU_SILU, true>), g, b, 0, st, p); break;
+    case 6: hipLaunchKernelGGL((gemm_mxfp4_glu_quant_kernel<SVDQ_FP16, SVDQ_GLU_GELU_ERF, false>), g, b, 0, st, p); break;
+    default: hipLaunchKernelGGL((gemm_mxfp4_glu_quant_kernel<SVDQ_FP16, SVDQ_GLU_GELU_ERF, true>), g, b, 0, st, p); break;
+    }
+    return hip_check(hipGetLastError(), "svdq_gemm_mxfp4_glu_quant launch");
 }

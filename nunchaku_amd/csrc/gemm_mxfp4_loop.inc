@@ -2,6 +2,12 @@
 // low-rank term of the wave's 64 x 128 outputs (element i of lane (r, h): row 64 wave + 32 mi + r, column 32 ni + 8 (i >> 2) + 4 h + (i & 3)).
 // A fragment of a kernel body, not a function: moved into one, the plain kernel's register allocation is the compiler's to change.  It expects in
 // scope DT, T, V8 and `p` (Mxfp4GemmParams or a struct derived from it); it leaves tid, wave, lane, r, h, TN, bm, bn, m0, n0 and acc behind.
+// The weight-side row (of wgt, wscales, lora_up) behind tile column c is MX_WBASE + c + MX_WSKIP(c): n0 + c unless the including kernel defines
+// the two macros (the rows of one 32-column accumulator tile must be consecutive).  Both are undefined again at the end of this file.
+#ifndef MX_WBASE
+#define MX_WBASE n0
+#define MX_WSKIP(c) 0
+#endif
     __shared__ __attribute__((aligned(16))) uint8_t lds[2 * MX_STAGE];
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
@@ -24,7 +30,7 @@
 #pragma unroll
     for (int j = 0; j < 2; j++) {
         const unsigned pos = (unsigned)(wave * 2 + j) * 64u + lane, row = pos >> 2, blk = (pos & 3u) ^ ((row >> 2) & 3u);
-        vw[j] = (unsigned)(n0 + row) * (unsigned)KB + blk * 16u;
+        vw[j] = (unsigned)(MX_WBASE + row + MX_WSKIP(row)) * (unsigned)KB + blk * 16u;
     }
     auto stage_dma = [&](int ks, int buf) {
         mx_lds_u8 *S = (mx_lds_u8 *)lds + buf * MX_STAGE;
@@ -34,12 +40,12 @@
         for (int j = 0; j < 2; j++) __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (mx_lds_void *)(S + MX_A_BYTES + (wave * 2 + j) * 1024), 16, vw[j], ks * 64, 0, 0);
     };
     // the scale dwords of K-step ks: lane (r, h) takes those of its own rows / columns; behind the step's wait it moves block h to byte 0 (block 2 + h to byte 2)
-    const uint32_t *sa_ptr = p.ascales + m0 + wave * 64 + r, *sw_ptr = p.wscales + n0 + r;
+    const uint32_t *sa_ptr = p.ascales + m0 + wave * 64 + r, *sw_ptr = p.wscales + MX_WBASE + r;
     auto load_scales = [&](int ks, unsigned (&sa)[2], unsigned (&sw)[4]) {
 #pragma unroll
         for (int mi = 0; mi < 2; mi++) sa[mi] = sa_ptr[(size_t)ks * p.M_pad + 32 * mi];
 #pragma unroll
-        for (int ni = 0; ni < 4; ni++) sw[ni] = sw_ptr[(size_t)ks * p.N + 32 * ni];
+        for (int ni = 0; ni < 4; ni++) sw[ni] = sw_ptr[(size_t)ks * p.N + 32 * ni + MX_WSKIP(32 * ni)];
     };
 
     v16f acc[4][2];
@@ -99,7 +105,7 @@
     const int Rr = p.R;
     if (Rr > 0) {
         const float *la_base = p.lora_act + (size_t)(m0 + wave * 64 + r) * Rr + 8 * h;
-        const T *lu_base = (const T *)p.lora_up + (size_t)(n0 + r) * Rr + 8 * h;
+        const T *lu_base = (const T *)p.lora_up + (size_t)(MX_WBASE + r) * Rr + 8 * h;
         for (int rc = 0; rc < Rr; rc += 16) {
             const float sc = p.lora_scales[rc >> 4];
             V8 la[2], lu[4];
@@ -114,10 +120,12 @@
                 }
             }
 #pragma unroll
-            for (int ni = 0; ni < 4; ni++) lu[ni] = *reinterpret_cast<const V8 *>(lu_base + (size_t)ni * 32 * Rr + rc);
+            for (int ni = 0; ni < 4; ni++) lu[ni] = *reinterpret_cast<const V8 *>(lu_base + (size_t)(ni * 32 + MX_WSKIP(32 * ni)) * Rr + rc);
 #pragma unroll
             for (int ni = 0; ni < 4; ni++)
 #pragma unroll
                 for (int mi = 0; mi < 2; mi++) acc[ni][mi] = Half<DT>::mfma32(lu[ni], la[mi], acc[ni][mi]);
         }
     }
+#undef MX_WBASE
+#undef MX_WSKIP

@@ -29,15 +29,7 @@ struct GluParams {
     int M, K, R, mode; // mode: lora_act_add's (bit 0 = K is sliced over workgroups, bit 1 = Q31.32)
 };
 
-// (glu_silu: quantize_tail.h, shared with the convolution front end)
-// gelu(g) = g * 0.5 * (1 + erf(g sqrt(1/2))) with 1 + erf(z) taken as erfc(|z|) or 2 - erfc(|z|): the same function (within 2^-23 of the
-// literal form where that form is accurate), and accurate in the negative tail, where 1 + erf cancels (gelu(-6) = -6e-9 is an ordinary 16-bit number).
-__device__ __forceinline__ float glu_gelu(float g) {
-    const float z = g * 0.70710678118654752440f;
-    const float c = erfcf(__builtin_fabsf(z));
-    return g * (0.5f * (z < 0.f ? c : 2.0f - c));
-}
-
+// (glu_silu, glu_gelu: glu_act.h, shared with the convolution front end and the MXFP4 GEMM's GLU_QUANT epilogue)
 template <typename T, int ACT> __device__ __forceinline__ unsigned glu_pair(unsigned vd, unsigned gd) {
     unsigned out = 0;
 #pragma unroll

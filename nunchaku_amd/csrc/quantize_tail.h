@@ -14,6 +14,7 @@
 // K, KP, rt (the 32-row tile), kp (the chunk), active, and `p` with lora_down, act, ascales, lora_act, R and mode (lora_act_add's).
 #pragma once
 
+#include "glu_act.h" // glu_silu, glu_gelu
 #include "svdq_common.h"
 
 namespace svdq {
@@ -29,16 +30,6 @@ typedef __attribute__((address_space(3))) v2i lds_v2i;
 typedef __attribute__((address_space(3))) v16f lds_v16f;
 typedef __attribute__((address_space(3))) float lds_f;
 typedef __attribute__((address_space(3))) void lds_void;
-
-// silu(g) = g * rcp(1 + exp2(-log2e g)): the form of quantize_kernel's GLU front end, bit for bit, down to g = -44.  Below, 1 + e == e in fp32 and e
-// itself leaves the range at g = -88.7 although g e^g is an ordinary bf16 number down to g = -96: the exponent is carried 2^64 lower and put back
-// with a multiply, which rounds into the fp32 subnormals where v_rcp_f32 would flush.
-__device__ __forceinline__ float glu_silu(float g) {
-    const bool big = g < -44.0f;
-    const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * g - (big ? 64.0f : 0.0f));
-    const float sg = g * __builtin_amdgcn_rcpf(big ? e : 1.0f + e);
-    return big ? sg * 0x1p-64f : sg;
-}
 
 // clears lora_act ahead of a K-sliced launch (a kernel, not hipMemsetAsync: the launch may be recorded into a graph)
 static __global__ __launch_bounds__(256) void quantize_tail_clear(uint32_t *dst, size_t words) {

@@ -506,10 +506,28 @@ class AWQW4A16Linear(nn.Module):
 
 def fused_glu_feed_forward(net, x: torch.Tensor, act: str):
     """``net = [GLU(proj), Dropout, out]`` of a gated feed-forward with the activation, the product and ``out``'s quantiser as ONE launch
-    (:meth:`SVDQW4A4Linear.quantize_glu`), or None where that does not apply: ``out`` is not an :class:`SVDQW4A4Linear`, or ``x`` is not on the GPU."""
+    (:meth:`SVDQW4A4Linear.quantize_glu`), or None where that does not apply: ``out`` is not an :class:`SVDQW4A4Linear`, or ``x`` is not on the GPU.
+    Two MXFP4 layers run three launches -- ``proj.quantize``, the ``proj`` GEMM under its GLU_QUANT epilogue (``svdq_gemm_mxfp4(glu=act)``: the
+    ``[..., 2 * hidden]`` projection output is never written), ``out.forward_quant``; one MXFP4 and one INT4 layer do not combine."""
     proj, out = net[0].proj, net[2]
     if not isinstance(out, SVDQW4A4Linear) or not x.is_cuda:
         return None
+    mx = [getattr(lin, "precision", "int4") == "mxfp4" for lin in (proj, out)]
+    if mx[0] != mx[1]:
+        raise ValueError("fused_glu_feed_forward: proj and out must share one precision (an MXFP4 layer next to an INT4 layer)")
+    if all(mx):
+        lead, M, hidden, dev = x.shape[:-1], x.numel() // x.shape[-1], out.in_features, x.device
+        qx, ascales, lora_act = proj.quantize(x.reshape(M, x.shape[-1]))
+        out._ensure_layout()
+        M_pad = qx.shape[0]
+        q_hidden = torch.empty(M_pad, hidden // 2, dtype=torch.uint8, device=dev)
+        s_hidden = torch.empty(hidden // 128, M_pad, 4, dtype=torch.uint8, device=dev)
+        l_hidden = torch.empty(M_pad, out.rank, dtype=torch.float32, device=dev)
+        svdq_gemm_mxfp4(qx, proj.qweight, ascales, proj.wscales, lora_act_in=lora_act if proj.rank else None, lora_up=proj.proj_up if proj.rank else None,
+                        bias=proj.bias, lora_scales=proj.lora_scales, rows=M, qout=q_hidden, oscales=s_hidden, glu=act,
+                        lora_down=out.proj_down if out.rank else None, lora_act_out=l_hidden if out.rank else None, smooth_factor=out.smooth_factor)
+        output = torch.empty(M, out.out_features, dtype=x.dtype, device=dev)
+        return out.forward_quant(q_hidden, s_hidden, l_hidden, output=output).reshape(*lead, -1)
     y = proj(x)  # [..., 2 * hidden]: (value | gate)
     y2 = y.reshape(-1, y.shape[-1])
     output = torch.empty(y2.shape[0], out.out_features, dtype=y.dtype, device=y.device)

@@ -153,13 +153,16 @@ class NunchakuSDXLGEGLU(nn.Module):
 
 class NunchakuSDXLFeedForward(_DiffusersFeedForward if HAVE_DIFFUSERS else nn.Module):
     """reference: unet_sdxl.py:124-158.  ``net = [GEGLU(proj = SVDQW4A4Linear(dim, 8 * dim)), Dropout, SVDQW4A4Linear(4 * dim, dim)]``;
-    built from ``dim`` or from a diffusers ``FeedForward`` (whose GEGLU and linear give the sizes, dtype and device)."""
+    built from ``dim`` or from a diffusers ``FeedForward`` (whose GEGLU and linear give the sizes, dtype and device).
+    ``precision="mxfp4"`` builds both layers as MXFP4 (``dim`` a multiple of 128): ``fused_glu`` then runs the GEGLU in the first GEMM's GLU_QUANT
+    epilogue.  The attention, block and model classes stay INT4."""
 
     def __init__(self, ff, rank: int = SVD_RANK, precision: str = "int4", torch_dtype: torch.dtype = torch.bfloat16,
                  device: str | torch.device | None = None):
         nn.Module.__init__(self)
-        _check_precision(precision)
-        kw = dict(rank=rank, precision="int4")
+        if precision != "mxfp4":
+            _check_precision(precision)
+        kw = dict(rank=rank, precision="mxfp4" if precision == "mxfp4" else "int4")
         if isinstance(ff, int):
             dim = ff
             proj = SVDQW4A4Linear(dim, 8 * dim, bias=True, torch_dtype=torch_dtype, device=device, **kw)
@@ -171,7 +174,7 @@ class NunchakuSDXLFeedForward(_DiffusersFeedForward if HAVE_DIFFUSERS else nn.Mo
             proj, out = SVDQW4A4Linear.from_linear(net[0].proj, **kw), SVDQW4A4Linear.from_linear(net[2], **kw)
         self.net = nn.ModuleList([NunchakuSDXLGEGLU(proj), nn.Dropout(0.0), out])
 
-    # True: gelu, product and net[2]'s quantiser run as one launch (SVDQW4A4Linear.quantize_glu).  Off by default: that path has the 16-bit
+    # True: gelu, product and net[2]'s quantiser run as one launch (SVDQW4A4Linear.quantize_glu; on MXFP4 layers inside the first GEMM).  Off by default: that path has the 16-bit
     # rounding points of the torch sequence but the device library's erfc, so it is not bit-identical to F.gelu.
     fused_glu = False
 

@@ -189,12 +189,15 @@ class NunchakuZImageSwiGLU(nn.Module):
 class NunchakuZImageFeedForward(nn.Module):
     """reference: transformer_zimage.py:119-166 -- Z-Image's ``w2(silu(w1 x) * w3 x)`` as diffusers' SwiGLU ``FeedForward``, quantised the way
     ``NunchakuSDXLFeedForward`` is: ``net = [SwiGLU(proj = SVDQW4A4Linear(dim, 2 * hidden)), Dropout, SVDQW4A4Linear(hidden, dim)]``, no biases.
-    Built from ``(dim, hidden)`` or from a diffusers Z-Image ``FeedForward`` (whose ``w1`` / ``w2`` give the sizes, dtype and device)."""
+    Built from ``(dim, hidden)`` or from a diffusers Z-Image ``FeedForward`` (whose ``w1`` / ``w2`` give the sizes, dtype and device).
+    ``precision="mxfp4"`` builds both layers as MXFP4 (``dim`` and ``hidden`` in multiples of 128): ``fused_glu`` then runs the SwiGLU in the
+    first GEMM's GLU_QUANT epilogue.  The block and model classes stay INT4."""
 
     def __init__(self, ff, hidden: int | None = None, rank: int = SVD_RANK, precision: str = "int4", torch_dtype: torch.dtype = torch.bfloat16,
                  device: str | torch.device | None = None):
         super().__init__()
-        _check_precision(precision)
+        if precision != "mxfp4":
+            _check_precision(precision)
         if not isinstance(ff, int):
             w1, w2, w3 = ff.w1, ff.w2, ff.w3
             if (w1.in_features, w1.out_features) != (w3.in_features, w3.out_features) or w1.out_features != w2.in_features:
@@ -202,10 +205,10 @@ class NunchakuZImageFeedForward(nn.Module):
             ff, hidden, torch_dtype, device = w1.in_features, w2.in_features, w1.weight.dtype, w1.weight.device
         if hidden is None or hidden < 1:
             raise ValueError("NunchakuZImageFeedForward: hidden is required")
-        kw = dict(rank=rank, precision="int4", bias=False, torch_dtype=torch_dtype, device=device)
+        kw = dict(rank=rank, precision="mxfp4" if precision == "mxfp4" else "int4", bias=False, torch_dtype=torch_dtype, device=device)
         self.net = nn.ModuleList([NunchakuZImageSwiGLU(SVDQW4A4Linear(ff, 2 * hidden, **kw)), nn.Dropout(0.0), SVDQW4A4Linear(hidden, ff, **kw)])
 
-    # True: silu, product and net[2]'s quantiser run as one launch (SVDQW4A4Linear.quantize_glu).  Off by default: that path has the 16-bit
+    # True: silu, product and net[2]'s quantiser run as one launch (SVDQW4A4Linear.quantize_glu; on MXFP4 layers inside the first GEMM).  Off by default: that path has the 16-bit
     # rounding points of the torch sequence but the hardware's exp2 / rcp, so it is not bit-identical to F.silu.
     fused_glu = False
 

@@ -74,7 +74,7 @@ def svdq_gemm_mxfp4(act: T, wgt: T, ascales: T, wscales: T, out: T | None = None
                     qout: T | None = None, oscales: T | None = None, lora_down: T | None = None, lora_act_out: T | None = None,
                     smooth_factor: T | None = None, lora_act_zeroed: bool = False,
                     norm_q: T | None = None, norm_k: T | None = None, rotary_emb: T | None = None, out_vt: T | None = None,
-                    q_scale: float = 0.0) -> T | None:
+                    q_scale: float = 0.0, glu: str | None = None) -> T | None:
     """MXFP4 W4A4 GEMM, plain epilogue: ``out[:rows] = A4 W4^T`` with both E8M0 block scales ``+ round16(lora_act_in * lora_scales) lora_up^T + bias``,
     one rounding to the 16-bit dtype of ``lora_up`` / ``bias`` / ``out`` (bfloat16 when none is given).  ``act`` / ``ascales`` as
     :func:`ops.quantize.svdq_quantize_mxfp4` returns them, ``wgt`` ``[N, K/2]``, ``wscales`` uint8 ``[K/32, N]``; ``rows``: the valid rows M
@@ -91,7 +91,17 @@ def svdq_gemm_mxfp4(act: T, wgt: T, ascales: T, wscales: T, out: T | None = None
     a QKV projection runs, ``N = 3 * heads * 128``, keywords as in :func:`svdq_gemm_w4a4_cuda`: per head, the Q and K thirds are
     ``rope(h * rsqrt(mean(h^2) + 1e-6) * norm)`` of that fp32 sum ``h`` with one rounding, Q times ``q_scale`` before it (0 = off); the V third
     is the plain output, and with ``out_vt`` (``[N/3, tokens]``, rows on 16 bytes) it is written transposed there instead of into ``out``.
-    These keywords together with ``qout`` raise ``ValueError``."""
+    These keywords together with ``qout`` raise ``ValueError``.
+
+    With ``glu`` (``"silu"`` for SwiGLU, ``"gelu"`` for the erf GEGLU) and ``qout`` the GLU_QUANT epilogue of a gated projection runs: ``wgt`` is
+    ``[2 * Hd, K/2]`` with the value rows first (diffusers' ``chunk(2, -1)``), and with ``v``, ``g`` the two 16-bit column halves the plain launch
+    would write, ``x = round16(v * round16(act(g)))`` -- the rounding points of :func:`ops.quantize.svdq_quantize_glu_halves`; ``qout``
+    (``[M_pad, Hd/2]``) / ``oscales`` (``[Hd/128, M_pad, 4]``) / ``lora_act_out`` receive what ``svdq_quantize_mxfp4(x, lora_down=lora_down,
+    smooth=smooth_factor)`` returns (``smooth_factor`` ``[Hd]``, ``lora_down`` ``[Hd, R_next]``), codes and scales bit for bit; ``out``, if given,
+    receives ``x`` ``[M, Hd]``.  The ``[M, 2 * Hd]`` projection output is never written.  ``glu`` without ``qout``, or together with ``norm_q`` /
+    ``norm_k`` / ``rotary_emb`` / ``out_vt``, raises ``ValueError``."""
+    if glu is not None and (qout is None or any(t is not None for t in (norm_q, norm_k, rotary_emb, out_vt))):
+        raise ValueError("svdq_gemm_mxfp4: glu= (the GLU_QUANT epilogue) needs qout and does not combine with norm_q, norm_k, rotary_emb or out_vt")
     if qout is not None and any(t is not None for t in (norm_q, norm_k, rotary_emb, out_vt)):
         raise ValueError("svdq_gemm_mxfp4: norm_q, norm_k, rotary_emb and out_vt (the RMSNorm+RoPE epilogue) do not combine with qout (GELU_QUANT)")
     M = act.shape[0] if rows is None else int(rows)
@@ -100,5 +110,5 @@ def svdq_gemm_mxfp4(act: T, wgt: T, ascales: T, wscales: T, out: T | None = None
         out = torch.empty(M, wgt.shape[0], dtype=torch.bfloat16 if ref is None else ref.dtype, device=act.device)
     ops.gemm_mxfp4(act, wgt, out, ascales, wscales, lora_act_in, lora_up, bias, lora_scales, M,
                    qout=qout, oscales=oscales, lora_down=lora_down, lora_act_out=lora_act_out, smooth_factor=smooth_factor, lora_act_zeroed=lora_act_zeroed,
-                   norm_q=norm_q, norm_k=norm_k, rotary_emb=rotary_emb, out_vt=out_vt, q_scale=q_scale)
+                   norm_q=norm_q, norm_k=norm_k, rotary_emb=rotary_emb, out_vt=out_vt, q_scale=q_scale, glu=glu)
     return out

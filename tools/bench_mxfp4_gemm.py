@@ -4,13 +4,16 @@ launches and replayed (a timed window is 2 to 17 ms), the arms alternate, the fi
 times fc1 of an MLP instead (M 4608, K 3072, N 12288): (a) the MXFP4 GELU_QUANT launch, (b) what produces the same operands without it -- plain
 svdq_gemm_mxfp4, torch's tanh GELU, svdq_quantize_mxfp4 with fc2's lora_down and smooth -- and (c) the INT4 GELU_QUANT launch.  `--qkv` times
 a QKV projection (M 4608, K 3072, N 9216): (a) the MXFP4 RMSNorm + RoPE launch with out_vt and q_scale, (b) plain svdq_gemm_mxfp4 plus the torch
-ops for the per-head norm, the rotation and the V transpose, (c) the INT4 RMSNORM_ROPE launch.  At every
+ops for the per-head norm, the rotation and the V transpose, (c) the INT4 RMSNORM_ROPE launch.  `--glu` times the gated projection of a SwiGLU /
+GEGLU feed-forward at three (M, K, 2 Hd) shapes: (a) the MXFP4 GLU_QUANT launch, (b) plain svdq_gemm_mxfp4, torch's chunk / activation / product,
+svdq_quantize_mxfp4 with the second projection's lora_down and smooth, (c) the INT4 pair svdq_gemm_w4a4 + svdq_quantize_glu_halves.  At every
 timed GEMM shape the MXFP4 output is also compared with the fp32 product of the dequantised operands (`mxfp4_max_err_over_max_ref`; the INT4 arm
 is only checked to be finite: its operands are another format, its result another number).  Prints one JSON line per row.
 
     python tools/bench_mxfp4_gemm.py [--rounds 15] [--launches 100] > profiles/mxfp4_gemm.txt
     python tools/bench_mxfp4_gemm.py --mlp > profiles/mxfp4_gelu_quant.txt
     python tools/bench_mxfp4_gemm.py --qkv > profiles/mxfp4_qkv.txt
+    python tools/bench_mxfp4_gemm.py --glu > profiles/mxfp4_glu_quant.txt
 
 Not measured here: hardware counters (a run of their own), end-to-end models (no model class runs MXFP4).
 """
@@ -177,18 +180,68 @@ def qkv(a):
     print(json.dumps(row), flush=True)
 
 
+GLU_SHAPES = [(4096, 3840, 20480, "silu"), (4096, 640, 5120, "gelu"), (1024, 1280, 10240, "gelu")]  # (M, K, 2 Hd, act): Z-Image, SDXL 640 / 1280
+
+
+def glu(a):
+    from nunchaku_amd.ops import svdq_gemm_mxfp4, svdq_quantize_mxfp4
+
+    for M, K, N, act in GLU_SHAPES:
+        Hd = N // 2
+        (i1, m1), (i2, m2) = layers(K, N), layers(Hd, K)
+        for lin in (i1, i2, m1, m2):
+            lin._ensure_layout()
+        dev = torch.device("cuda")
+        x = torch.randn(M, K, device=dev).bfloat16()
+        qi, qm = i1.quantize(x), m1.quantize(x)
+        qh, sh, lh = torch.empty(M, Hd // 2, dtype=torch.uint8, device=dev), torch.empty(Hd // 128, M, 4, dtype=torch.uint8, device=dev), torch.empty(M, RANK, device=dev)
+        hid, hid_i = torch.empty(M, N, dtype=torch.bfloat16, device=dev), torch.empty(M, N, dtype=torch.bfloat16, device=dev)
+        common = dict(lora_act_in=qm[2], lora_up=m1.proj_up, bias=m1.bias, rows=M)
+        fn = torch.nn.functional.silu if act == "silu" else torch.nn.functional.gelu
+
+        def fused():
+            svdq_gemm_mxfp4(qm[0], m1.qweight, qm[1], m1.wscales, qout=qh, oscales=sh, lora_down=m2.proj_down, lora_act_out=lh, smooth_factor=m2.smooth_factor,
+                            glu=act, **common)
+
+        def unfused():
+            svdq_gemm_mxfp4(qm[0], m1.qweight, qm[1], m1.wscales, out=hid, **common)
+            v, g = hid.chunk(2, dim=-1)
+            return svdq_quantize_mxfp4(v * fn(g), lora_down=m2.proj_down, smooth=m2.smooth_factor)
+
+        def int4():  # as fused_glu_feed_forward launches it on INT4 layers
+            i1.forward_quant(*qi, hid_i)
+            return i2.quantize_glu(hid_i, act)
+
+        fused()
+        ref = unfused()  # torch's activation is another fp32 expression: the codes agree except next to a rounding boundary
+        agree = float((qh == ref[0]).float().mean())
+        assert agree > 0.98 and bool(lh.isfinite().all()) and bool(int4()[2].isfinite().all()), agree
+        arms = {"mxfp4_fused": captured(fused, a.launches), "mxfp4_gemm_torch_glu_quantize": captured(unfused, a.launches), "int4_gemm_quantize_glu": captured(int4, a.launches)}
+        med, span = alternate(arms, a.rounds, a.launches)
+        row = {"op": "glu_quant", "act": act, "M": M, "K": K, "N": N, "code_bytes_equal_to_unfused": round(agree, 4)}
+        for k in arms:
+            row[k + "_us"], row[k + "_min_max_us"] = round(med[k], 2), [round(v, 2) for v in span[k]]
+        row["fused_over_unfused"], row["fused_over_int4"] = round(med["mxfp4_fused"] / med["mxfp4_gemm_torch_glu_quantize"], 3), round(med["mxfp4_fused"] / med["int4_gemm_quantize_glu"], 3)
+        row["fused_tflops"] = round(2.0 * M * K * N / med["mxfp4_fused"] / 1e6, 1)
+        print(json.dumps(row), flush=True)
+        del arms, hid, hid_i
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--launches", type=int, default=100)
     ap.add_argument("--mlp", action="store_true")
     ap.add_argument("--qkv", action="store_true")
+    ap.add_argument("--glu", action="store_true")
     a = ap.parse_args()
     print(json.dumps({"device": torch.cuda.get_device_name(0), "rounds": a.rounds, "launches_per_replay": a.launches, "rank": RANK, "dtype": "bf16"}))
     if a.mlp:
         return mlp(a)
     if a.qkv:
         return qkv(a)
+    if a.glu:
+        return glu(a)
     for M, K, N in GEMM_SHAPES:
         int4, mx = layers(K, N)
         x = torch.randn(M, K, device="cuda").bfloat16()
